@@ -16,7 +16,11 @@ copies run beside them, on a copy stream ordered by events, into pinned double b
 the same in both legs.  The HBM-resident rate (no copies) is reported beside it as ``value_resident``; its leg is
 where the per-stage HIP-event times and the roofline of the dominant kernel are taken.
 
-Prints ONE JSON line on rank 0.  Besides the driver's contract it carries
+Prints ONE JSON line on rank 0.  A plain run (``bench.py --gpus N --steps K --warmup W``) does only what the headline needs: it
+builds the codec, warms up, times the K host-to-host steps of the default arithmetic and prints the line (metric, value, unit,
+ms_per_step, dtype, ...).  ``--dump-outputs DIR`` then writes what the last timed step handed its caller (a fixed sample of clouds: the
+reconstructed XYZ and the three files' contents) as float32 / float64 .npy files; the inputs are the same from run to run.
+Everything else is measured with ``--full`` only, which adds to the line
   roofline     -- the dominant kernel: algorithmic FLOPs per launch / its HIP-event duration against the
                   matrix-core peak of the arithmetic used (MI355X_MICROARCH.md: fp32 matrix 157.3 TFLOP/s;
                   bf16 dense 16x that, / 6 products for the three-way split = 419.5 fp32-equivalent);
@@ -24,7 +28,10 @@ Prints ONE JSON line on rank 0.  Besides the driver's contract it carries
                   stage table and roofline; ``precision_matched`` names the leg whose products are as wide as the reference's (f32);
   full_mode    -- the same clouds with octree_mode="full" (the decode that reconstructs all 64 centres) in the default arithmetic;
   cpu_baseline -- the CPU restatement of the reference loop (oracle/ref_pipeline.py), timed on this node's host
-                  cores on a bounded sample, with its bpp / D1-PSNR and a 1-thread figure, rank 0 at N=1 only.
+                  cores on a bounded sample, with its bpp / D1-PSNR and a 1-thread figure, rank 0 at N=1 only;
+  and the resident leg, with_files, f16x2_vs_f32, bpp / D1-PSNR and the `secondary` block (configs[2], [3], [4]).
+The other workloads (``--workload ...``) follow the same rule: CPU baselines, batch sweeps, other arithmetics, stage tables and
+agreement checks only with ``--full``.
 """
 import argparse
 import json
@@ -459,8 +466,9 @@ def timed(rk, fn, steps, sync, tag=None):
 # workloads
 # =====================================================================================================================
 def cpu_leg_allowed(args, rk):
-    """The CPU baseline runs on rank 0 at N = 1 only (with N > 1 the ranks would wait in a barrier for a leg that says nothing about them)."""
-    return rk.world == 1 and args.cpu_clouds > 0
+    """The CPU baseline runs with --full, on rank 0 at N = 1 only (with N > 1 the ranks would wait in a barrier for a leg that says nothing
+    about them)."""
+    return args.full and rk.world == 1 and args.cpu_clouds > 0
 
 
 def run_launch_stub(args, rk):
@@ -485,8 +493,8 @@ def bench_launch_check(args, rk):
                "scaling": "weak", "vs_baseline": None, "dtype": "none", "data": "synthetic",
                "config": {"workload": "launch-check (no GPU work)", "dist_backend": rk.backend}, "summary": s,
                "cpu_baseline": {"value": 1.0, "cores": 1, "kind": "port", "sample": "none"} if cpu_leg_allowed(args, rk) else None}
-    # the default line's secondary block, with stubs for the three workloads: every rank runs them, rank 0 alone emits, once
-    if not args.no_secondary:
+    # the --full line's secondary block, with stubs for the three workloads: every rank runs them, rank 0 alone emits, once
+    if args.full and not args.no_secondary:
         sec = run_secondaries(args, rk, res, specs=(("stub_a", "run_launch_stub", {}), ("stub_b", "run_launch_stub", {})))
         if res is not None:
             res["secondary"] = sec
@@ -503,6 +511,33 @@ def build_codec(rk, matmul, octree_mode):
     ae.pack(rk.dev)
     prob.pack(rk.dev)
     return codec.Codec(ae, prob, K=K_PATCH, ALPHA=ALPHA, N0=N0, octree_mode=octree_mode, matmul=matmul), ae, prob
+
+
+DUMP_CLOUDS, DUMP_SEED = 256, 0       # --dump-outputs: a fixed, seeded sample of the batch's clouds (~28 MB for 256)
+
+
+def dump_ipdae_outputs(directory, packed_host, out_host, B, s_stride, p_cap):
+    """What the last timed step of the host-to-host window handed its caller, for the clouds of a fixed seeded sample: the
+    reconstructed XYZ and the contents of the three files (.s.bin / .p.bin bytes as float32 0..255, zero past each file's end; .c.bin as
+    float32; the byte counts as float64)."""
+    import numpy as np
+    from pccx import codec
+    os.makedirs(directory, exist_ok=True)
+    h = codec.Compressed.from_packed(packed_host, B, s_stride, p_cap, N_POINTS)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(B, min(B, DUMP_CLOUDS), replace=False))
+
+    def file_bytes(rows, nbytes):
+        b = rows.numpy()[idx].astype(np.float32)
+        b[np.arange(b.shape[1])[None, :] >= nbytes[:, None]] = 0.0
+        return b
+    s_n, p_n = h.s_nbytes.numpy()[idx], h.p_nbytes.numpy()[idx]
+    arrays = {"reconstruction": out_host.numpy()[idx].astype(np.float32), "s_bin": file_bytes(h.s_bytes, s_n),
+              "p_bin": file_bytes(h.p_bytes, p_n), "c_bin": h.c.numpy()[idx].astype(np.float32),
+              "s_nbytes": s_n.astype(np.float64), "p_nbytes": p_n.astype(np.float64), "cloud_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    print("[bench] outputs of the last timed step (%d of %d clouds, %.1f MB) written to %s" %
+          (len(idx), B, sum(a.nbytes for a in arrays.values()) / 1e6, directory), file=sys.stderr, flush=True)
 
 
 def roofline_of(stages, steps, P, matmul, batch):
@@ -586,8 +621,10 @@ def bench_ipdae(args, rk):
     row = codec.packed_layout(1, s_stride, p_cap)[-1]                             # bytes per cloud
     nb_ = min(B, int(base.shape[0]))                # the unturned base shapes = the CPU leg's first clouds (cpu_baseline.same_clouds_as_gpu)
 
-    def measure(cd, with_files=False, keep_for_compare=False, rank_tag=None):
-        """Both legs of one (arithmetic mode, octree mode): resident (per-stage events) and host-to-host (the reference's window)."""
+    def measure(cd, with_files=False, keep_for_compare=False, rank_tag=None, lean=False):
+        """Both legs of one (arithmetic mode, octree mode): resident (per-stage events) and host-to-host (the reference's window).
+        lean (a plain run): the resident steps only warm up, the host-to-host leg alone is timed, and its last step's host buffers
+        are returned (host_packed, host_out) instead of being checked against the resident leg."""
         keep = {}
 
         # ---- resident leg: one stream, everything stays in HBM, per-stage events -------------------------------
@@ -597,17 +634,19 @@ def bench_ipdae(args, rk):
         for _ in range(args.warmup):
             comp, out = step_resident(0)
         sync()
-        timer = ops.StageTimer()
-        ops.set_timer(timer)
-        dt_res = timed(rk, lambda i: keep.__setitem__("r", step_resident(i)), args.steps, sync)
-        ops.set_timer(None)
-        comp, out = keep["r"]
-        stages = {k: (ms / n, n) for k, (ms, n) in timer.totals_ms().items()}
-        r = {"dt_res": dt_res, "stages": stages, "bits": float(comp.bits().sum()), "psnr_sum": float(codec.d1_psnr(clouds, out).sum()),
-             "chamfer_sum": float(codec.normalized_chamfer(clouds, out).sum())}
-        r["base_shapes"] = {"clouds": nb_, "bpp": float(comp.bits()[:nb_].sum()) / (nb_ * N_POINTS),
-                            "d1_psnr_db": float(codec.d1_psnr(clouds[:nb_], out[:nb_]).sum()) / nb_}
-        if rank_tag:
+        r = {}
+        if not lean:
+            timer = ops.StageTimer()
+            ops.set_timer(timer)
+            dt_res = timed(rk, lambda i: keep.__setitem__("r", step_resident(i)), args.steps, sync)
+            ops.set_timer(None)
+            comp, out = keep["r"]
+            stages = {k: (ms / n, n) for k, (ms, n) in timer.totals_ms().items()}
+            r = {"dt_res": dt_res, "stages": stages, "bits": float(comp.bits().sum()), "psnr_sum": float(codec.d1_psnr(clouds, out).sum()),
+                 "chamfer_sum": float(codec.normalized_chamfer(clouds, out).sum())}
+            r["base_shapes"] = {"clouds": nb_, "bpp": float(comp.bits()[:nb_].sum()) / (nb_ * N_POINTS),
+                                "d1_psnr_db": float(codec.d1_psnr(clouds[:nb_], out[:nb_]).sum()) / nb_}
+        if rank_tag and not lean:
             # the resident pipeline's shortcut, beside the figure above: decompress handed the Compressed object it came from takes the
             # integer CDF compress built instead of evaluating the probability model again (codec.decompress(reuse_cdf=True)); the
             # host-to-host window below never does (its decompress starts from bytes, as decompress.py:88-92)
@@ -665,6 +704,9 @@ def bench_ipdae(args, rk):
         sync()
         r["dt_host"] = timed(rk, step_host, args.steps, sync, tag=rank_tag)
         last = (args.steps - 1) % 2
+        if lean:
+            r["host_packed"], r["host_out"] = pin_comp[last], pin_out[last]      # what the last timed step handed its caller
+            return r
         r["host_equals_resident"] = bool(torch.equal(pin_out[last], out.cpu()))
         hc = codec.Compressed.from_packed(pin_comp[last], B, s_stride, p_cap, N_POINTS)
         r["host_bytes_equal_resident"] = bool(torch.equal(hc.s_nbytes, comp.s_nbytes.cpu()) and torch.equal(hc.p_nbytes, comp.p_nbytes.cpu()))
@@ -753,6 +795,36 @@ def bench_ipdae(args, rk):
                         "longest": cx.c[:, 3].cpu()}
         return r
 
+    pts = B * N_POINTS * args.steps
+
+    def headline(main):
+        """The fields of the line that a plain run and a --full run share: the host-to-host leg of the default arithmetic."""
+        return {
+            "metric": "points/sec compress+decompress (ModelNet40-shaped 8192 K=256)",
+            "value": rk.world * pts / main["dt_host"], "unit": "points/s",
+            "n_gpus": rk.world, **rk.info, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * main["dt_host"] / args.steps,
+            "rank_ms_per_step": rk.rank_ms("host", args.steps),      # each rank's own time for the same steps (before the closing barrier)
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": MODE_DTYPE[args.matmul], "data": "synthetic",
+            "copy_engine": "HSA_ENABLE_SDMA=" + os.environ.get("HSA_ENABLE_SDMA", "unset"),
+            "window": "host-to-host: cloud in HBM -> .s/.p/.c bytes on the host (compress.py:85-154) -> XYZ on the host "
+                      "(decompress.py:77-118); kernels on one stream, copies overlapped on a copy stream",
+            "config": {"workload": "IPDAE K=256 d=16 L=7, 8192-pt CAD-like synthetic clouds (configs[1])",
+                       "clouds_per_gpu_per_step": B, "distinct_clouds_per_gpu": B, "base_shapes_per_gpu": int(base.shape[0]), "points_per_cloud": N_POINTS,
+                       "patches_per_cloud": S_PATCH, "octree_mode": args.octree_mode, "sharding": f"file-sharded x{rk.world}",
+                       "weights": "seeded random", "matmul": args.matmul},
+        }
+
+    if not args.full:
+        # a plain run: the headline leg alone, then the line (everything else is --full's)
+        cd, _, _ = build_codec(rk, args.matmul, args.octree_mode)
+        main = measure(cd, rank_tag="host", lean=True)
+        if rk.rank == 0:
+            res = headline(main)
+            if args.dump_outputs:
+                dump_ipdae_outputs(args.dump_outputs, main["host_packed"], main["host_out"], B, s_stride, p_cap)
+            print(json.dumps(res), flush=True)
+        return
+
     res_by_mode = {}
     for mode in modes:
         cd, _, _ = build_codec(rk, mode, args.octree_mode)
@@ -772,36 +844,23 @@ def bench_ipdae(args, rk):
         torch.cuda.empty_cache()
 
     main = res_by_mode[args.matmul]
-    pts = B * N_POINTS * args.steps
     summ = rk.summaries([main["bits"], B * N_POINTS, main["psnr_sum"], main["chamfer_sum"], B, main["dt_host"]])
     if rk.rank == 0:
         rf, per_step_ms, tfl = roofline_of(main["stages"], args.steps, P, args.matmul, B)
-        dtype = MODE_DTYPE[args.matmul]
-        res = {
-            "metric": "points/sec compress+decompress (ModelNet40-shaped 8192 K=256)",
-            "value": rk.world * pts / main["dt_host"], "unit": "points/s",
-            "n_gpus": rk.world, **rk.info, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * main["dt_host"] / args.steps,
-            "rank_ms_per_step": rk.rank_ms("host", args.steps),      # each rank's own time for the same steps (before the closing barrier)
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
-            "copy_engine": "HSA_ENABLE_SDMA=" + os.environ.get("HSA_ENABLE_SDMA", "unset"),
-            "window": "host-to-host: cloud in HBM -> .s/.p/.c bytes on the host (compress.py:85-154) -> XYZ on the host "
-                      "(decompress.py:77-118); kernels on one stream, copies overlapped on a copy stream",
+        res = headline(main)
+        res.update({
             "value_resident": rk.world * pts / main["dt_res"], "ms_per_step_resident": 1e3 * main["dt_res"] / args.steps,
             "resident_cdf_reuse": {"value": rk.world * pts / main["dt_res_reuse"], "ms_per_step": 1e3 * main["dt_res_reuse"] / args.steps,
                                    "decoded_equals_recompute": main["reuse_equals_recompute"],
                                    "note": "resident pipeline only: decompress takes the integer CDF of the Compressed object it is handed instead "
                                            "of running the probability model a second time; `value` (from bytes) always recomputes"} if "dt_res_reuse" in main else None,
             "host_window_checks": {k: main[k] for k in ("host_equals_resident", "host_bytes_equal_resident", "d2h_bytes_per_step")},
-            "config": {"workload": "IPDAE K=256 d=16 L=7, 8192-pt CAD-like synthetic clouds (configs[1])",
-                       "clouds_per_gpu_per_step": B, "distinct_clouds_per_gpu": B, "base_shapes_per_gpu": int(base.shape[0]), "points_per_cloud": N_POINTS,
-                       "patches_per_cloud": S_PATCH, "octree_mode": args.octree_mode, "sharding": f"file-sharded x{rk.world}",
-                       "weights": "seeded random", "matmul": args.matmul},
             "roofline": rf,
             "stage_ms_per_step": {k: round(v, 4) for k, v in sorted(per_step_ms.items(), key=lambda kv: -kv[1])},
             "mfma_stage_tflops": tfl,
             "bpp": summ["bpp"], "d1_psnr_db": summ["d1_psnr_db"], "chamfer": summ["chamfer"], "summary_files": summ["files"],
             "base_shapes": main["base_shapes"],
-        }
+        })
         def leg_record(r, mode, octree_mode):
             """a secondary leg in full: host-to-host value + resident value, its own window checks, stage table and roofline"""
             rf2, ps2, tfl2 = roofline_of(r["stages"], args.steps, P, mode, B)
@@ -942,11 +1001,12 @@ def run_s3dis(args, rk):
     bits = psnr_sum = blocks = pts = 0.0
     flat = torch.cat([large.split_blocks(pc)[0] for pc in rooms])
     for ids, c in keep["parts"]:
-        bits += float(c.bits().sum())
-        psnr_sum += float(codec.d1_psnr(flat[ids], cd.decompress(c)).sum())
         blocks += len(ids)
-        pts += len(ids) * flat.shape[1]
-    summ = rk.summaries([bits, pts, psnr_sum, 0.0, blocks, dt])
+        if args.full:
+            bits += float(c.bits().sum())
+            psnr_sum += float(codec.d1_psnr(flat[ids], cd.decompress(c)).sum())
+            pts += len(ids) * flat.shape[1]
+    summ = rk.summaries([bits, pts, psnr_sum, 0.0, blocks, dt]) if args.full else None
     if rk.rank == 0:
         # the dominant kernel is the fused encoder, as in the headline workload: its launches here cover `blocks_per_launch` blocks
         # (the last one of a step fewer), so the FLOPs of a launch are taken from the mean number of patches per launch
@@ -971,8 +1031,8 @@ def run_s3dis(args, rk):
                        "sharding": f"block-sharded x{rk.world}", "matmul": args.matmul, "blocks_per_launch": args.batch},
             "roofline": rf, "stage_ms_per_step": {k_: round(v, 4) for k_, v in sorted(per_step_ms.items(), key=lambda kv: -kv[1])},
             "cpu_baseline": cpu, "gpu_over_cpu": (n_pts * args.steps / dt / cpu["value"]) if cpu and "value" in cpu else None,
-            "bpp_padded_blocks": summ["bpp"], "d1_psnr_db_blockwise": summ["d1_psnr_db"],
-            "blocks": int(summ["files"])})
+            "bpp_padded_blocks": summ["bpp"] if summ else None, "d1_psnr_db_blockwise": summ["d1_psnr_db"] if summ else None,
+            "blocks": int(summ["files"]) if summ else int(blocks)})
     return None
 
 
@@ -1006,12 +1066,14 @@ def run_pppf(args, rk):
         model(patches)
     dt = timed(rk, lambda i: keep.__setitem__("o", model(patches)), args.steps, torch.cuda.synchronize)
     # the stage table comes from passes of their own AFTER the timed ones (HIP events around every stage, not inside the timed region)
-    timer = ops.StageTimer()
-    ops.set_timer(timer)
-    for _ in range(args.steps):
-        model(patches)
-    ops.set_timer(None)
-    stage_ms = {k_: round(ms / args.steps, 4) for k_, (ms, n_) in sorted(timer.totals_ms().items(), key=lambda kv: -kv[1][0])}
+    stage_ms = None
+    if args.full:
+        timer = ops.StageTimer()
+        ops.set_timer(timer)
+        for _ in range(args.steps):
+            model(patches)
+        ops.set_timer(None)
+        stage_ms = {k_: round(ms / args.steps, 4) for k_, (ms, n_) in sorted(timer.totals_ms().items(), key=lambda kv: -kv[1][0])}
     flop_ref = families.pppf_flops_per_patch(model)                       # the reference's count: stacks on every grouped row
     flop = families.pppf_flops_per_patch(model, executed=True, n_points=Kp)  # what runs here: stacks on the source rows only
     if rk.rank == 0:
@@ -1024,7 +1086,7 @@ def run_pppf(args, rk):
         # agreement of the quoted arithmetic with the other two on the TIMED patches (the headline's f16x2_vs_f32, for this family): one
         # forward each, outside every timed region
         agree = None
-        if args.matmul == "f16x2" and "h2" in (model._packed or {}):
+        if args.full and args.matmul == "f16x2" and "h2" in (model._packed or {}):
             import pccx as _pccx
             try:
                 got = [t.clone() for t in keep["o"]]
@@ -1117,7 +1179,7 @@ def run_pppe_train(args, rk):
                 # the pieces by themselves (HIP events): selection on the side stream, and copy + replay with the tables ready
                 ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
                 sel_ms = rep_ms = lat_ms = 0.0
-                nrep = max(3, min(steps, 10))
+                nrep = max(3, min(steps, 10)) if args.full else 0
                 for _ in range(nrep):
                     torch.cuda.synchronize()
                     with torch.cuda.stream(gstep._side):
@@ -1138,8 +1200,8 @@ def run_pppe_train(args, rk):
                     lat_ms += 1e3 * (time.perf_counter() - t0)
                 extra = {"stage_ms_per_step": {"graph_replay (forward + backward + clip + Adam, one hipGraph)": round(rep_ms / nrep, 4),
                                                "selection (FPS + kNN tables of the next batch, side stream, overlapped)": round(sel_ms / nrep, 4)},
-                         "latency_ms_isolated_step": round(lat_ms / nrep, 4),
-                         "pipelining": "selection of batch i+1 on a side stream under the replay of step i (GraphedTrainStep(prefetch=True))"}
+                         "latency_ms_isolated_step": round(lat_ms / nrep, 4)} if nrep else {}
+                extra["pipelining"] = "selection of batch i+1 on a side stream under the replay of step i (GraphedTrainStep(prefetch=True))"
             else:
                 dt = timed(rk, lambda i: keep.__setitem__("o", gstep(sync=False)), steps, torch.cuda.synchronize)
             keep["o"] = tuple(float(t) for t in keep["o"])
@@ -1153,7 +1215,7 @@ def run_pppe_train(args, rk):
     Bt = args.train_batch
     dt, loss, model, sd0, x, starts, extra = run(Bt, args.steps, args.warmup)
     sweep = {}
-    if not args.one_mode:
+    if args.full and not args.one_mode:
         for b_ in (4, 16, 64):
             if b_ == Bt:
                 sweep[str(b_)] = {"clouds_per_s": rk.world * Bt * args.steps / dt, "ms_per_step": 1e3 * dt / args.steps}
@@ -1165,7 +1227,7 @@ def run_pppe_train(args, rk):
         for v in sweep.values():
             v["patches_per_s"] = v["clouds_per_s"] * 512
     other = None
-    if not args.one_mode:
+    if args.full and not args.one_mode:
         # the step in the OTHER arithmetic beside the quoted one (bf16 autocast <-> fp32): the reference's CUDA branch is fp16 autocast with a
         # GradScaler (three more mantissa bits than bf16), so the fp32 step is the conservative figure to read the bf16 one against
         torch.cuda.empty_cache()
@@ -1229,11 +1291,13 @@ def run_ipdae_train(args, rk):
         return train_ipdae.IpdaeTrainer(ae.to(rk.dev), prob.to(rk.dev), N=N_POINTS, K=K, lr=5e-4, lamda=1e-6, rate_loss_enable_step=0,
                                         autocast=autocast)
     keep = {}
-    tr = fresh()
-    for i in range(max(args.warmup, 1)):
-        tr.step(x[i % n_clouds:i % n_clouds + 1], starts[i % n_clouds])
-    dt_e = timed(rk, lambda i: keep.__setitem__("e", tr.step(x[i % n_clouds:i % n_clouds + 1], starts[i % n_clouds])), args.steps,
-                 torch.cuda.synchronize)
+    dt_e = None
+    if args.full:
+        tr = fresh()
+        for i in range(max(args.warmup, 1)):
+            tr.step(x[i % n_clouds:i % n_clouds + 1], starts[i % n_clouds])
+        dt_e = timed(rk, lambda i: keep.__setitem__("e", tr.step(x[i % n_clouds:i % n_clouds + 1], starts[i % n_clouds])), args.steps,
+                     torch.cuda.synchronize)
     tg = fresh()
     gstep = tg.graphed(x[:1], starts[0], warmup=max(args.warmup, 1))
     dstarts = torch.from_numpy(starts.astype(np.int32)).to(rk.dev)                       # the start indices live on the device, like the clouds
@@ -1257,7 +1321,7 @@ def run_ipdae_train(args, rk):
     peak = BF16_DENSE_PEAK_TFLOPS if autocast else F32_MATRIX_PEAK_TFLOPS
     return {"metric": "clouds/sec, IPDAE training step (train.py --model AE: forward+backward+Adam)", "value": rk.world * args.steps / dt,
             "unit": "clouds/s", "patches_per_s": rk.world * 64 * args.steps / dt, "n_gpus": rk.world, **rk.info, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "ms_per_step_eager": 1e3 * dt_e / args.steps, "higher_is_better": True,
+            "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "ms_per_step_eager": 1e3 * dt_e / args.steps if dt_e else None, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "bf16 autocast" if autocast else "f32", "data": "synthetic",
             "config": {"workload": "IPDAE training step (train.py:156-256, --model AE), batch 1 x 8192 points, K=256 (64 patches), d=16, L=7",
                        "parallelism": f"{rk.world} independent replica(s)", "weights": "seeded random",
@@ -1311,12 +1375,19 @@ def main():
     ap.add_argument("--no-files", action="store_true",
                     help="ipdae: skip the leg with the three .bin files of every cloud written to / read from tmpfs inside the window")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="ipdae: skip the secondary block (configs[2] PPPF forward, [3] room-scale blocks, [4] training step) of the default line")
+                    help="ipdae --full: skip the secondary block (configs[2] PPPF forward, [3] room-scale blocks, [4] training step) of the line")
     ap.add_argument("--secondary-budget", type=float, default=300.0, help="seconds after which a hung secondary leg is abandoned (the line is still printed)")
     ap.add_argument("--secondary-cpu-budget", type=float, default=3.0, help="seconds of CPU work per secondary workload's cpu_baseline")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (production); gloo only to rehearse the N>1 path on one GPU / on CPU")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: other arithmetics and octree mode, resident leg, stage tables and rooflines, "
+                         "with_files, agreement checks, CPU baselines, the secondary workloads (a plain run times the headline leg only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="ipdae: write what the last timed step computed (a fixed sample of clouds) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "ipdae":
+        ap.error("--dump-outputs is implemented for --workload ipdae (the headline) only")
 
     from pccx import launch
     if args.gpus > 1 and not launch.launched_by_torchrun_or_us():

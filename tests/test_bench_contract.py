@@ -39,3 +39,34 @@ def test_flop_counts_follow_the_layer_shapes():
     assert bench.FLOP_PN == K * (131 * 128 + 128 * 256 + 256 * 512 + 512 * d) * 2            # AE.py:17
     assert bench.FLOP_DEC == (d * 256 + 256 * 1024 + 1024 * k * 128) * 2 + k * (144 * 128 + 128 * 64 + 64 * 32 + 32 * 3) * 2   # AE.py:19-27
     assert set(bench.MODE_DTYPE) == {"f32", "bf16x3", "f16x2"}
+
+
+def test_dump_outputs_sample_and_dtypes(tmp_path):
+    """--dump-outputs: the last step's host buffers -> float32 / float64 .npy files for a fixed seeded sample of clouds, file bytes
+    zeroed past each file's end, well under 64 MB at the default batch."""
+    import numpy as np
+    import torch
+    from pccx import codec
+    B, s_stride, p_cap = 1024, 1025, 2064
+    g = torch.Generator().manual_seed(5)
+    packed = torch.randint(0, 256, (codec.packed_layout(B, s_stride, p_cap)[-1],), dtype=torch.uint8, generator=g)
+    h = codec.Compressed.from_packed(packed, B, s_stride, p_cap, bench.N_POINTS)
+    h.s_nbytes.copy_(torch.randint(1, s_stride + 1, (B,), generator=g, dtype=torch.int32))
+    h.p_nbytes.copy_(torch.randint(1, p_cap + 1, (B,), generator=g, dtype=torch.int32))
+    h.c.copy_(torch.rand(B, 4, generator=g))                        # random bytes would hold NaNs there
+    out = torch.rand(B, bench.N_POINTS, 3, generator=g)
+    for d in ("a", "b"):
+        bench.dump_ipdae_outputs(str(tmp_path / d), packed, out, B, s_stride, p_cap)
+    got = {f.name: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert set(got) == {n + ".npy" for n in ("reconstruction", "s_bin", "p_bin", "c_bin", "s_nbytes", "p_nbytes", "cloud_index")}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    idx = got["cloud_index.npy"].astype(np.int64)
+    assert len(idx) == min(B, bench.DUMP_CLOUDS) and np.all(np.diff(idx) > 0)
+    for name, a in got.items():                                      # the sample does not depend on the run
+        assert np.array_equal(a, np.load(tmp_path / "b" / name))
+    assert np.array_equal(got["reconstruction.npy"], out.numpy()[idx])
+    for b_, i in enumerate(idx[:16]):
+        n = int(h.s_nbytes[i])
+        assert np.array_equal(got["s_bin.npy"][b_, :n], h.s_bytes[i, :n].numpy()) and not got["s_bin.npy"][b_, n:].any()
+        assert got["p_nbytes.npy"][b_] == int(h.p_nbytes[i])

@@ -106,7 +106,7 @@ def test_bench_self_launch_two_ranks_gloo():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["PCCX_ASSERT_PARENT_GPU_FREE"] = "1"                    # the parent exits non-zero if torch / the HIP library got imported
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--workload",
-                        "launch-check", "--steps", "3"], env=env, capture_output=True, text=True, timeout=300)
+                        "launch-check", "--steps", "3", "--full"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]      # gloo itself prints a connection note on stdout
     assert len(lines) == 1, r.stdout
@@ -118,7 +118,7 @@ def test_bench_self_launch_two_ranks_gloo():
     assert s["files"] == 3 and abs(s["bpp"] - 3000.0 / (3 * 8192)) < 1e-12
     assert abs(s["d1_psnr_db"] - (30.0 + 31.0) / 3) < 1e-12
     assert abs(s["points_per_s"] - 3 * 8192 / 1.5) < 1e-9      # sum of points / MAX of seconds
-    # the secondary block of the default line (stubs here: no GPU): every rank ran the legs, rank 0 emitted them ONCE, inside the one
+    # the secondary block of the --full line (stubs here: no GPU): every rank ran the legs, rank 0 emitted them ONCE, inside the one
     # line; with N > 1 no leg carries a CPU baseline (bench.cpu_leg_allowed) and every rank's NUMA placement is listed
     sec = j["secondary"]
     assert set(sec) == {"stub_a", "stub_b", "wall_s"} and sec["stub_a"]["n_gpus"] == 2
@@ -127,10 +127,28 @@ def test_bench_self_launch_two_ranks_gloo():
     assert r.stdout.count('"secondary"') == 1
     # ... and at N = 1 the same command carries the CPU legs
     r1 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--dist-backend", "gloo", "--workload",
-                         "launch-check", "--steps", "2"], env=env, capture_output=True, text=True, timeout=300)
+                         "launch-check", "--steps", "2", "--full"], env=env, capture_output=True, text=True, timeout=300)
     assert r1.returncode == 0, r1.stderr[-2000:]
     j1 = json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][0])
     assert j1["cpu_baseline"] is not None and j1["secondary"]["stub_b"]["cpu_baseline"] is not None and j1["n_gpus"] == 1
+
+
+def test_bench_plain_run_is_the_headline_only_gloo():
+    """Without --full the same command times its steps and prints the line: no secondary block, no CPU leg, at N = 1 and N = 2."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    for n in (1, 2):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--dist-backend", "gloo", "--workload",
+                            "launch-check", "--steps", "4", "--warmup", "1"], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        j = json.loads(lines[0])
+        assert j["n_gpus"] == n and j["steps"] == 4 and j["ms_per_step"] >= 0
+        assert "secondary" not in j and j["cpu_baseline"] is None
 
 
 def test_launcher_propagates_a_failing_rank(tmp_path):

@@ -1,7 +1,7 @@
 O=$GRAFT_REPO_ROOT/gpurun_out/r4z; mkdir -p $O
 run() { # name, env...
   n=$1; shift
-  env "$@" timeout -k 10 200 python3 bench.py --one-mode --cpu-clouds 0 --steps 10 --warmup 3 > $O/sdma_$n.json 2> $O/sdma_$n.err
+  env "$@" timeout -k 10 200 python3 bench.py --full --one-mode --cpu-clouds 0 --steps 10 --warmup 3 > $O/sdma_$n.json 2> $O/sdma_$n.err
   python3 - <<PY
 import json
 d=json.loads([l for l in open("$O/sdma_$n.json") if l.startswith("{")][-1])
