@@ -368,7 +368,9 @@ PCCX_API int pccx_stream_sizes_host(int B, const char *dir, const char *names, c
  * pccx_pack_linear (HOST pointers): W (N,K) row-major -> pccx_packed_linear_floats(N,K) floats.
  * pccx_linear: x (M, ldx>=K), wp packed (device), bias (N) or NULL, out (M, ldo>=N); `relu` is a flag word: bit 0 = ReLU,
  * bit 1 = the autocast form of train_pppe_pcd_ae.py:193-217 (operands and result rounded to bf16, products on the bf16
- * matrix cores, fp32 accumulate; pccx_linear_dw takes the same bit 1 in `flags`). */
+ * matrix cores, fp32 accumulate; pccx_linear_dw takes the same bit 1 in `flags`); bit 4 (16), with bit 1 only: operands rounded to
+ * bf16 as above, the result stored in fp32 unrounded -- for a caller that adds the bias itself and then rounds once (the role-swapped
+ * layers of pccx/train.py, whose bias runs along the output's rows). */
 PCCX_API size_t pccx_packed_linear_floats(int N, int K);
 PCCX_API int pccx_pack_linear(const float *W_host, int N, int K, float *wp_host);
 PCCX_API int pccx_linear(const float *x, int M, int K, int ldx, const float *wp, const float *bias,

@@ -148,8 +148,8 @@ __global__ __launch_bounds__(256, 2) void linear_kernel(const float *__restrict_
         for (int m = 0; m < MTB; ++m) {
             const int c = 16 * (mt0 + m) + 4 * g;
             f32x4 v = acc[nt][m];
-            if (BF16) v = round_bf16x4(v);
-            if (relu) v = relu4(v);
+            if (BF16 && !(relu & 2)) v = round_bf16x4(v);         // relu bit 1: operands-only rounding (pccx_linear flags bit 4)
+            if (relu & 1) v = relu4(v);
             if (MOM == 1) acc[nt][m] = row < M ? v : f32x4{0.f, 0.f, 0.f, 0.f};  // what is stored, for the moments below
             if (MOM == 2) {
                 // d = relu'(y) dY and d xhat in place of the accumulators (acc[nt][m] <- d xhat; the d's go to a second array)
@@ -280,8 +280,10 @@ extern "C" int pccx_linear(const float *x, int M, int K, int ldx, const float *w
     const bool vec = ldx % 4 == 0 && ldo % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)out % 16 == 0);
     // columns per wave: every column block re-reads the wave's x rows, so wide layers take 16 column tiles per wave (a 512 -> 1024
     // layer on 8.4 M rows re-read its 17 GB input 16 times with 4 tiles per wave: 114 ms, bandwidth-bound)
-    const bool bf16 = (relu & 2) != 0;                     // flags: bit 0 = ReLU, bit 1 = autocast (bf16 operands and result)
-    relu &= 1;
+    // flags: bit 0 = ReLU, bit 1 = autocast (bf16 operands and result), bit 4 = with bit 1: bf16 operands, result left in fp32 (the
+    // caller adds what the layer adds and rounds once -- pccx/train.py's role-swapped layers, whose bias runs along the output rows)
+    const bool bf16 = (relu & 2) != 0;
+    relu = (relu & 1) | (bf16 && (relu & 16) ? 2 : 0);      // kernel word: bit 0 = ReLU, bit 1 = keep the fp32 result
     const int mtb = pccx_linear_col_tiles(M, MT);
     dim3 grid((M + 127) / 128, (MT + mtb - 1) / mtb);
     PCCX_CHECK_ARG(grid.y <= 65535, "pccx_linear: N=%d too large", N);

@@ -81,13 +81,20 @@ def _zeros(shape, dtype, device):
 ops.zeros_hook = _zeros       # the Chamfer backward's two gradient buffers come from the step's arena too
 
 
-def _sums(C, device):
-    """2*C doubles of column-sum scratch and the flag the reduction takes: 4 when the step's arena has cleared them already"""
+def _sums(C, device, private=False):
+    """2*C doubles of column-sum scratch and the flag the reduction takes: 4 when the step's arena has cleared them already.
+    Without a live arena slice the sums are ONE process-wide tensor per channel count, reused by the next call: a caller that parks its
+    sums for another Function (_MOMENTS, _BWD_SUMS) asks for private=True and then gets a tensor of its own -- otherwise a Linear with
+    bias and N == K behind a BatchNorm overwrote the sums its dX GEMM had just produced for that BatchNorm with dZ's column sums."""
     n = int(_lib.load().pccx_train_sums_doubles(C))          # eight replicas of the 2 C sums (csrc/train.hip: PCCX_SUM_REPLICAS)
     if _ARENA is not None:
         t, pre = _ARENA.zeros(n, torch.float64, device)
         if pre:
             return t, 4
+        if private:
+            return t, 0                                      # a fresh torch.zeros (StepArena.zeros' fall-back)
+    if private:
+        return torch.empty(n, device=device, dtype=torch.float64), 0
     t = _SCRATCH.get((C, str(device)))
     if t is None:
         t = _SCRATCH[(C, str(device))] = torch.empty(n, device=device, dtype=torch.float64)
@@ -113,11 +120,15 @@ def _linear_raw(x, wp, bias, N, K, flags=0):
     return out
 
 
-_MOMENTS = {}              # address of a LinearFn output produced WITH its column moments -> (shape, sums); consumed by the BnReluFn that
-                           # takes that tensor next, emptied at the start of every forward
+_MOMENTS = {}              # address of a LinearFn output produced WITH its column moments -> (shape, sums, out, version); consumed by the
+                           # BnReluFn that takes that tensor next, emptied at the start of every forward
 _BN_OF = {}                # address of a BnReluFn output y -> (shape, y, z, mean, rstd): the LinearFn that consumes y keeps it, and its
                            # backward produces dY together with the BatchNorm backward's two column sums (pccx_linear_bnback)
-_BWD_SUMS = {}             # address of such a dY -> (shape, sums); consumed by that BnReluFn's backward
+_BWD_SUMS = {}             # address of such a dY -> (shape, sums, dY, version); consumed by that BnReluFn's backward
+# Every entry holds its tensor, so the caching allocator cannot hand the address to another tensor while the entry lives (a LinearFn
+# output dropped before its BatchNorm, outside forward_train, left an entry a later tensor of the same shape matched), and an entry counts
+# only while the tensor's version is the one recorded: when a BatchNorm output has a second consumer, autograd sums the two dY -- in place
+# into one of them where it may -- and the sums of one consumer alone no longer describe that (the BatchNorm then reduces dY itself).
 _FOLD_MOMENTS = os.environ.get("PCCX_NO_MOMENT_FOLD") != "1"      # experiment knob: 0 = every BatchNorm reduces its input itself
 
 
@@ -128,6 +139,28 @@ def _is_wide(M, N, K):
     45 GB/s.  With the ROLES SWAPPED the weight matrix is the row operand the kernels stream at full rate: y^T = W x^T is pccx_linear
     over N rows with the (few) activations packed as its weights, and dX^T = W^T dZ^T is pccx_linear_dw over the same N rows."""
     return 8 < M <= 256 and M % 4 == 0 and N >= 1024 and N >= 8 * M and K % 4 == 0 and N * K >= (1 << 21)
+
+
+def _parked(table, t):
+    """the sums parked in _MOMENTS / _BWD_SUMS for exactly this tensor, unchanged since they were made, or None"""
+    e = table.pop(t.data_ptr(), None)
+    if e is None or e[0] != tuple(t.shape) or e[3] != e[2]._version:
+        return None
+    return e[1]
+
+
+def _linear_path(x, W2):
+    """The kernel path of LinearFn.forward for rows x (M, K) (contiguous) and weights W2 (N, K): "skinny" (pccx_linear_skinny: a few rows,
+    16-byte loads of x and W rows -- row stride and base addresses are checked here, a (1, K) view keeps an arbitrary stride(0), a tensor
+    with a storage offset can be misaligned), "wide" (_is_wide: the roles of rows and weights swapped) or "generic" (pccx_linear, which
+    picks its vector or scalar variant from the alignment itself; with want_moments it is pccx_linear_moments)."""
+    M, (N, K) = x.shape[0], W2.shape
+    ldx = K if M == 1 else x.stride(0)
+    if M <= 8 and K % 4 == 0 and ldx % 4 == 0 and ldx >= K and x.data_ptr() % 16 == 0 and W2.data_ptr() % 16 == 0:
+        return "skinny"
+    if x.is_cuda and _is_wide(M, N, K) and x.stride(0) == K:
+        return "wide"
+    return "generic"
 
 
 class LinearFn(torch.autograd.Function):
@@ -144,32 +177,32 @@ class LinearFn(torch.autograd.Function):
         bn_in = _BN_OF.get(x.data_ptr()) if _FOLD_MOMENTS else None
         ctx.bn_in = bn_in if (bn_in is not None and bn_in[0] == tuple(x.shape)) else None
         N, K = W2.shape
-        # a few rows: a weight stream, not matrix work (csrc/train.hip).  The kernels take 16-byte loads of x rows and W rows: row stride and
-        # base addresses are checked HERE (a (1, K) view keeps an arbitrary stride(0), a tensor with a storage offset can be misaligned) and
-        # anything else takes the generic layer, as before round 3.
-        ldx = K if x.shape[0] == 1 else x.stride(0)
-        ctx.wide = False
-        ctx.skinny = (x.shape[0] <= 8 and K % 4 == 0 and ldx % 4 == 0 and ldx >= K and x.data_ptr() % 16 == 0 and W2.data_ptr() % 16 == 0)
+        # a few rows: a weight stream, not matrix work (csrc/train.hip); anything the skinny kernels cannot load takes the generic layer
+        path = _linear_path(x, W2)
+        ctx.skinny, ctx.wide = path == "skinny", path == "wide"
         if ctx.skinny:
             out = torch.empty(x.shape[0], N, device=x.device, dtype=torch.float32)
-            _lib.call("pccx_linear_skinny", x.data_ptr(), x.shape[0], K, ldx, W2.data_ptr(), b.data_ptr() if b is not None else None,
-                      N, ctx.flags, out.data_ptr(), N, _stream())
+            _lib.call("pccx_linear_skinny", x.data_ptr(), x.shape[0], K, K if x.shape[0] == 1 else x.stride(0), W2.data_ptr(),
+                      b.data_ptr() if b is not None else None, N, ctx.flags, out.data_ptr(), N, _stream())
             return out
-        ctx.wide = x.is_cuda and _is_wide(x.shape[0], N, K) and x.stride(0) == K
         if ctx.wide:
-            yT = _linear_raw(W2, _packed(x, False), None, x.shape[0], K, ctx.flags)     # (N, M) = W x^T
+            # (N, M) = W x^T.  The bias runs along the rows of this product, so under autocast the GEMM rounds its operands only (flags bit
+            # 4) and the layer rounds ONCE after the bias, like the generic layer: rounding W x^T first moved a row whose bias cancels most
+            # of the product by up to half a bf16 ulp of the product -- many ulps of the output -- and made it depend on the batch size
+            keep = 16 if (ctx.flags & 2 and b is not None) else 0
+            yT = _linear_raw(W2, _packed(x, False), None, x.shape[0], K, ctx.flags | keep)
             out = yT.t().contiguous()
             if b is not None:
                 out += b
                 if ctx.flags & 2:
-                    out = out.bfloat16().float()                                        # the autocast layer rounds AFTER its bias
+                    out = out.bfloat16().float()
             return out
         if want_moments and b is None and _FOLD_MOMENTS and x.is_cuda:
-            sums, pre = _sums(N, x.device)
+            sums, pre = _sums(N, x.device, private=True)
             out = torch.empty(x.shape[0], N, device=x.device, dtype=torch.float32)
             _lib.call("pccx_linear_moments", x.data_ptr(), x.shape[0], K, x.stride(0), _packed(W2, False).data_ptr(), N, ctx.flags | pre,
                       out.data_ptr(), N, sums.data_ptr(), _stream())
-            _MOMENTS[out.data_ptr()] = (tuple(out.shape), sums)
+            _MOMENTS[out.data_ptr()] = (tuple(out.shape), sums, out, out._version)
             return out
         return _linear_raw(x, _packed(W2, False), b, N, K, ctx.flags)
 
@@ -195,11 +228,11 @@ class LinearFn(torch.autograd.Function):
             # x is the output of a train-mode BatchNorm-ReLU: dX is that layer's dY, and the GEMM's epilogue accumulates the two column
             # sums its backward needs from the rows it has just produced (13 col_reduce4<1> launches per step otherwise)
             _, y_, z_, mean_, rstd_ = ctx.bn_in
-            sums, pre = _sums(K, dz.device)
+            sums, pre = _sums(K, dz.device, private=True)
             dx = torch.empty(M, K, device=dz.device, dtype=torch.float32)
             _lib.call("pccx_linear_bnback", dz.data_ptr(), M, N, dz.stride(0), _packed(W2, True).data_ptr(), K, ctx.flags | pre, dx.data_ptr(), K,
                       y_.data_ptr(), z_.data_ptr(), mean_.data_ptr(), rstd_.data_ptr(), sums.data_ptr(), _stream())
-            _BWD_SUMS[dx.data_ptr()] = (tuple(dx.shape), sums)
+            _BWD_SUMS[dx.data_ptr()] = (tuple(dx.shape), sums, dx, dx._version)
         elif ctx.needs_input_grad[0]:
             dx = _linear_raw(dz, _packed(W2, True), None, K, N, ctx.flags)                                       # dX = dZ . W
         dW, _ = _zeros(tuple(W2.shape), torch.float32, dz.device)
@@ -222,9 +255,9 @@ class BnReluFn(torch.autograd.Function):
         mean = torch.empty(Cc, device=z.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
         y = torch.empty_like(z)
-        mom = _MOMENTS.pop(z.data_ptr(), None)
-        if mom is not None and mom[0] == tuple(z.shape):
-            sums, pre = mom[1], 4 | 8                # the producing GEMM's epilogue accumulated the moments: no reduction pass here
+        mom = _parked(_MOMENTS, z)
+        if mom is not None:
+            sums, pre = mom, 4 | 8                   # the producing GEMM's epilogue accumulated the moments: no reduction pass here
         else:
             sums, pre = _sums(Cc, z.device)
         # moments, then ONE kernel that finalises them (mean, rstd, running statistics) and applies the layer (csrc/train.hip)
@@ -245,9 +278,9 @@ class BnReluFn(torch.autograd.Function):
         M, Cc = z.shape
         dz = torch.empty_like(z)
         gg, gb = torch.empty_like(gamma), torch.empty_like(gamma)                    # written by the apply kernel's first workgroup
-        bs = _BWD_SUMS.pop(dy.data_ptr(), None)
-        if bs is not None and bs[0] == tuple(dy.shape):
-            sums, pre = bs[1], 4 | 8                 # the GEMM that produced dY accumulated the two sums in its epilogue
+        bs = _parked(_BWD_SUMS, dy)
+        if bs is not None:
+            sums, pre = bs, 4 | 8                    # the GEMM that produced dY accumulated the two sums in its epilogue
         else:
             sums, pre = _sums(Cc, z.device)
         _lib.call("pccx_bn_relu_train_backward", dy.data_ptr(), y.data_ptr(), z.data_ptr(), M, Cc, mean.data_ptr(), rstd.data_ptr(),
