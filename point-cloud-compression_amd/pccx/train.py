@@ -13,6 +13,7 @@ on the bf16 matrix cores with fp32 accumulation and rounds its result to bf16; B
 clipping and Adam stay fp32 on fp32 master weights, as under autocast; the backward GEMMs (dX, dW) round their operands the same
 way.  bf16 has fp32's exponent range, so no GradScaler is needed (the reference's scaler guards fp16).  Correctness-first.
 """
+import contextlib
 import math
 import os
 
@@ -22,7 +23,7 @@ from . import _lib, families, ops
 from .ops import _stream
 
 _SCRATCH = {}
-_AUTOCAST = False          # set by train_step(autocast=True) around forward + backward
+_AUTOCAST = False          # True while the forward of an autocast step runs (step_scope): the Linear layers take their bf16 form
 
 
 class StepArena:
@@ -68,7 +69,88 @@ class StepArena:
 
 
 _EAGER_ARENA = StepArena()
-_ARENA = None              # the arena of the step in progress (train_step / GraphedTrainStep set it), or None outside a step
+_ARENA = None              # the arena of the step in progress (step_scope installs it), or None outside a step
+
+
+@contextlib.contextmanager
+def step_scope(device, arena=None, autocast=False, params=(), begin=True, end=True):
+    """The process-wide state of one training iteration, set on entry and restored on EVERY way out of the block; the only code that
+    assigns _AUTOCAST or _ARENA.  Entry: every .grad of `params` is dropped (optimizer.zero_grad()), the arena is installed and begun --
+    ONE clear for everything the step accumulates into -- and _AUTOCAST is set.  arena=None is an eager step: _EAGER_ARENA on a CUDA
+    device (looked up now: a caller may have swapped in a fresh one), no arena on the CPU.  The block receives forward_done(), to call
+    in front of loss.backward(): autocast off (the backward layers carry their arithmetic in ctx.flags).  The arena stays installed
+    through backward AND the optimiser step: Adam's norm accumulator comes from it.  Exit: _AUTOCAST False, _ARENA None, arena ended.
+    A step cut in two (GraphedTrainStep(data_parallel=True): forward + backward | gradient all-reduce | clip + Adam) enters twice:
+    end=False leaves the arena open after the first half -- unless the block raises, which always ends it -- and begin=False installs
+    it again for the second without dropping the gradients or clearing what the first half accumulated."""
+    global _AUTOCAST, _ARENA
+    device = torch.device(device)
+    if arena is None and device.type == "cuda":
+        arena = _EAGER_ARENA
+
+    def forward_done():
+        global _AUTOCAST
+        _AUTOCAST = False
+
+    try:
+        _ARENA = arena
+        if begin:
+            for p in params:
+                p.grad = None
+            if arena is not None:
+                arena.begin(device)
+        _AUTOCAST = bool(autocast)
+        yield forward_done
+    except BaseException:
+        end = True
+        raise
+    finally:
+        _AUTOCAST = False
+        _ARENA = None
+        if arena is not None and end:
+            arena.end(device)
+
+
+def capture_step(device, opt, warmup, warm, body, opt_body=None, debug_dot=None):
+    """Capture one training iteration as a hipGraph: `warmup` calls of warm() -- real optimisation steps, which also size the arena and
+    the scratch buffers -- on a side stream that waited for the current one, then body() under capture.  opt_body: the iteration is cut
+    in two at the data-parallel gradient exchange and opt_body() (clip + Adam) becomes a second graph in the first one's pool.
+    -> (graph, what body() returned, the captured gradients, the second graph or None, the gradients present between the two halves
+    or None).  The captured gradients are graph-pool tensors at the addresses the optimiser's table holds; the table is uploaded here."""
+    if warmup > 0:
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                warm()
+        torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph, graph_opt, between = torch.cuda.CUDAGraph(), None, None
+    if debug_dot:                           # hipGraphDebugDotPrint of the captured step (nodes and edges), for diagnostics
+        graph.enable_debug_mode()
+    # thread_local, below: only THIS thread's calls are checked against the capture.  In the default (global) mode a
+    # call from any thread invalidates it -- and under a process group the RCCL watchdog thread polls the events of earlier
+    # collectives (hipEventQuery) whenever it likes: a captured data-parallel step then died at random with "operation not permitted
+    # when stream is capturing" raised in the WATCHDOG and hipErrorStreamCaptureInvalidated here (found by the one-rank RCCL test,
+    # about one run in ten; it would have hit the N-GPU --graph runs the same way).
+    mode = dict(capture_error_mode="thread_local")
+    with torch.cuda.graph(graph, **mode):
+        out = body()
+    if opt_body is not None:
+        between = [p.grad for p in opt.params if p.grad is not None]         # fixed addresses: what the all-reduce averages
+        graph_opt = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph_opt, pool=graph.pool(), **mode):
+            opt_body()
+    if debug_dot:
+        graph.debug_dump(debug_dot)
+    kept = opt._keep
+    opt.flush_table()
+    # Leave no python handle on the captured iteration: the parameters' .grad are graph-pool tensors the replays own.  Eager
+    # iterations on the same model / optimiser may alternate with replays (the optimiser's step counter lives on the device
+    # and both advance it).
+    for p in opt.params:
+        p.grad = None
+    return graph, out, kept, graph_opt, between
 
 
 def _zeros(shape, dtype, device):
@@ -130,6 +212,7 @@ _BWD_SUMS = {}             # address of such a dY -> (shape, sums, dY, version);
 # only while the tensor's version is the one recorded: when a BatchNorm output has a second consumer, autograd sums the two dY -- in place
 # into one of them where it may -- and the sums of one consumer alone no longer describe that (the BatchNorm then reduces dY itself).
 _FOLD_MOMENTS = os.environ.get("PCCX_NO_MOMENT_FOLD") != "1"      # experiment knob: 0 = every BatchNorm reduces its input itself
+_BN_COUNTED = None         # True while forward_train runs and has advanced every num_batches_tracked of the model in one launch
 
 
 def _is_wide(M, N, K):
@@ -343,7 +426,7 @@ class GatherFn(torch.autograd.Function):
         B, N, Cc = ctx.shape
         dg = dg.contiguous()
         M = idx[0].numel()
-        df, pre = _zeros((B, N, Cc), torch.float32, dg.device)
+        df, _ = _zeros((B, N, Cc), torch.float32, dg.device)
         _lib.call("pccx_gather_backward_acc", dg.data_ptr(), Cc, idx.contiguous().data_ptr(), B, M, N, Cc, df.data_ptr(), 4, _stream())
         return df, None
 
@@ -443,10 +526,6 @@ def forward_train(model, x, starts, tables=None):
     caller has them already (then `starts` is not looked at).
     -> (coarse (B,512,3), fine (B,N,3), cond (B,512), y_q (B,d))."""
     global _BN_COUNTED
-    enc, dec = model.encoder, model.decoder
-    B = x.shape[0]
-    sa = enc.sa_modules
-    outs, new_xyz = [], None
     _MOMENTS.clear()
     _BN_OF.clear()
     _BWD_SUMS.clear()
@@ -455,12 +534,9 @@ def forward_train(model, x, starts, tables=None):
         with ops.stage("selection"):
             tables = selection_tables(model, x, starts) if tables is None else tables
         with ops.stage("forward"):
-            return _forward_train_body(model, tables, enc, dec, B, sa)
+            return _forward_train_body(model, tables)
     finally:
         _BN_COUNTED = None
-
-
-_BN_COUNTED = None
 
 
 def _advance_bn_counters(model, device):
@@ -480,7 +556,9 @@ def _advance_bn_counters(model, device):
     return True
 
 
-def _forward_train_body(model, tables, enc, dec, B, sa):
+def _forward_train_body(model, tables):
+    enc, dec = model.encoder, model.decoder
+    sa, B = enc.sa_modules, tables[0][0].shape[0]
     outs = []
     for br, tb in zip(sa[0].branches, tables):
         _, f = _sa_train(br, tb, None)
@@ -702,7 +780,7 @@ class GraphedTrainStep:
                                  "the smooth-L1 backward still reads its upstream gradient on the host")
         dev = batch_x.device
         self.model, self.opt, self.grad_clip, self.loss_type, self.autocast = model, opt, grad_clip, loss_type, autocast
-        self.data_parallel, self.graph_opt = bool(data_parallel), None
+        self.data_parallel = bool(data_parallel)
         self.arena = StepArena()            # this step's accumulation buffers: sized by the warm-up iterations, cleared by the graph's first node
         opt.make_capturable(dev)
         as_dev = lambda s_: torch.as_tensor(s_).to(device=dev, dtype=torch.int32).contiguous().clone()
@@ -727,69 +805,21 @@ class GraphedTrainStep:
             self._side, self._upload = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
             self._sel_done, self._copied = torch.cuda.Event(), torch.cuda.Event()
             self._copied.record(torch.cuda.current_stream())
-        if warmup > 0:
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(warmup):
-                    self._body()
-            torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        if debug_dot:                       # hipGraphDebugDotPrint of the captured step (nodes and edges), for diagnostics
-            self.graph.enable_debug_mode()
-        # capture_error_mode="thread_local": only THIS thread's calls are checked against the capture.  In the default (global) mode a
-        # call from any thread invalidates it -- and under a process group the RCCL watchdog thread polls the events of earlier
-        # collectives (hipEventQuery) whenever it likes: a captured data-parallel step then died at random with "operation not permitted
-        # when stream is capturing" raised in the WATCHDOG and hipErrorStreamCaptureInvalidated here (found by the one-rank RCCL test,
-        # about one run in ten; it would have hit the N-GPU --graph runs the same way).
-        mode = dict(capture_error_mode="thread_local")
-        if self.data_parallel:
-            with torch.cuda.graph(self.graph, **mode):
-                self.out = self._fwd_bwd()
-            self._dp_grads = [p.grad for p in opt.params if p.grad is not None]      # fixed addresses: what the all-reduce averages
-            self.graph_opt = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_opt, pool=self.graph.pool(), **mode):
-                self._opt_step()
-        else:
-            with torch.cuda.graph(self.graph, **mode):
-                self.out = self._body()
-        if debug_dot:
-            self.graph.debug_dump(debug_dot)
-        self._grads = opt._keep            # the captured gradients: graph-pool tensors at the addresses the table holds
-        opt.flush_table()
-        # Leave no python handle on the captured iteration: the parameters' .grad are graph-pool tensors the replays own.  Eager
-        # iterations on the same model / optimiser may alternate with replays (the optimiser's step counter lives on the device
-        # and both advance it).
-        for p in opt.params:
-            p.grad = None
+        halves = (self._fwd_bwd, self._opt_step) if self.data_parallel else (self._body, None)
+        self.graph, self.out, self._grads, self.graph_opt, self._dp_grads = capture_step(dev, opt, warmup, self._body, *halves, debug_dot)
 
     def _fwd_bwd(self):
-        global _AUTOCAST, _ARENA
-        for p in self.opt.params:
-            p.grad = None
-        _AUTOCAST = bool(self.autocast)
-        _ARENA = self.arena
-        self.arena.begin(self.x.device)
-        try:
+        with step_scope(self.x.device, self.arena, self.autocast, self.opt.params, end=False) as forward_done:
             coarse, fine, cond, y_q = forward_train(self.model, self.x, self.starts, tables=self.tables)
             fbpp = estimate_bits_per_point(self.model, y_q, cond.detach())
             loss, dist, rate = rd_loss(fine, self.x, fbpp, self.lam, self.loss_type)
-            _AUTOCAST = False
+            forward_done()
             loss.backward()
-        finally:
-            _AUTOCAST = False
-            _ARENA = None
         return loss.detach(), dist, rate
 
     def _opt_step(self):
-        global _ARENA
-        _ARENA = self.arena                                          # Adam's norm accumulator comes from the same cleared buffer
-        try:
+        with step_scope(self.x.device, self.arena, begin=False):
             self.opt.step(max_norm=self.grad_clip)
-        finally:
-            _ARENA = None
-            self.arena.end(self.x.device)
 
     def _body(self):
         out = self._fwd_bwd()
@@ -884,18 +914,11 @@ def train_step(model, opt, batch_x, starts, lam=1.0, grad_clip=1.0, data_paralle
     parameters as the reference's optimizer does; returns (loss, dist, rate) as python floats.
     data_parallel=True averages the gradients over the ranks of the default process group (bucketed
     all-reduce, dist.allreduce_mean_) between backward and the clipped Adam step."""
-    global _AUTOCAST, _ARENA
-    for p in opt.params:
-        p.grad = None
-    _AUTOCAST = bool(autocast)              # the Linear layers of forward (and, through ctx.flags, of backward) take the bf16 form
-    _ARENA = _EAGER_ARENA if batch_x.is_cuda else None
-    if _ARENA is not None:
-        _ARENA.begin(batch_x.device)        # ONE clear for everything this step accumulates into (StepArena)
-    try:
+    with step_scope(batch_x.device, None, autocast, opt.params) as forward_done:
         coarse, fine, cond, y_q = forward_train(model, batch_x, starts)
         fbpp = estimate_bits_per_point(model, y_q, cond.detach())
         loss, dist, rate = rd_loss(fine.float(), batch_x.float(), fbpp, lam, loss_type)      # :205 casts back to fp32 for the loss
-        _AUTOCAST = False
+        forward_done()
         if data_parallel:
             # gradient averaging overlapped with backward: each bucket is all-reduced on a side stream as soon as its last gradient is
             # written (dist.GradBuckets); the clipped Adam step waits for the last bucket
@@ -908,9 +931,4 @@ def train_step(model, opt, batch_x, starts, lam=1.0, grad_clip=1.0, data_paralle
         else:
             loss.backward()
         opt.step(max_norm=grad_clip)
-    finally:
-        _AUTOCAST = False
-        if _ARENA is not None:
-            _ARENA.end(batch_x.device)
-        _ARENA = None
     return float(loss.detach()), float(dist), float(rate)

@@ -197,23 +197,12 @@ class IpdaeTrainer:
         with torch.randint inside farthest_point_sample_batch, pn_kit.py:321)"""
         if batch_x.dim() != 3 or batch_x.shape[1] != self.N or batch_x.shape[2] != 3:
             raise _lib.PccxError(f"train_ipdae: batch must be (B, {self.N}, 3), got {tuple(batch_x.shape)}")
-        for p in self.opt.params:
-            p.grad = None                                                             # :173 optimizer.zero_grad()
         lam = 0.0 if self.global_step < self.rate_loss_enable_step else self.lamda    # :218-221
-        train._AUTOCAST = self.autocast
-        train._ARENA = train._EAGER_ARENA if batch_x.is_cuda else None
-        if train._ARENA is not None:
-            train._ARENA.begin(batch_x.device)
-        try:
+        with train.step_scope(batch_x.device, None, self.autocast, self.opt.params) as forward_done:     # :173 optimizer.zero_grad()
             loss, fbpp, bpp = forward_loss(self.ae, self.prob, batch_x, starts, lam, self.S, self.K, self.N, self.N0)
-            train._AUTOCAST = False
+            forward_done()
             loss.backward()                                                           # :229
             self.opt.step(max_norm=None)                                              # :230
-        finally:
-            train._AUTOCAST = False
-            if train._ARENA is not None:
-                train._ARENA.end(batch_x.device)
-            train._ARENA = None
         self.global_step += 1                                                         # :236
         if self.global_step % self.lr_decay_steps == 0:                               # :250-254
             self.lr *= self.lr_decay
@@ -241,23 +230,12 @@ class GraphedIpdaeStep:
         self.starts = torch.as_tensor(starts).to(device=dev, dtype=torch.int32).contiguous().clone()
         self.lam = torch.zeros((), device=dev, dtype=torch.float32)
         self.warm_out = None
-        if warmup > 0:
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(warmup):
-                    self._set_lam()
-                    self.warm_out = self._body()                     # (loss, fbpp, bpp) of the last warm-up iteration, device scalars
-                    self._advance()
-            torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):        # see pccx.train.GraphedTrainStep on the mode
-            self.out = self._body()
-        self._grads = tr.opt._keep
-        tr.opt.flush_table()
-        for p in tr.opt.params:
-            p.grad = None
+
+        def warm():
+            self._set_lam()
+            self.warm_out = self._body()                             # (loss, fbpp, bpp) of the last warm-up iteration, device scalars
+            self._advance()
+        self.graph, self.out, self._grads, _, _ = train.capture_step(dev, tr.opt, warmup, warm, self._body)
 
     def _set_lam(self):
         self.lam.fill_(0.0 if self.tr.global_step < self.tr.rate_loss_enable_step else self.tr.lamda)
@@ -271,20 +249,11 @@ class GraphedIpdaeStep:
 
     def _body(self):
         tr = self.tr
-        for p in tr.opt.params:
-            p.grad = None
-        train._AUTOCAST = tr.autocast
-        train._ARENA = self.arena
-        self.arena.begin(self.x.device)
-        try:
+        with train.step_scope(self.x.device, self.arena, tr.autocast, tr.opt.params) as forward_done:
             loss, fbpp, bpp = forward_loss(tr.ae, tr.prob, self.x, self.starts, self.lam, tr.S, tr.K, tr.N, tr.N0)
-            train._AUTOCAST = False
+            forward_done()
             loss.backward()
             tr.opt.step(max_norm=None)
-        finally:
-            train._AUTOCAST = False
-            train._ARENA = None
-            self.arena.end(self.x.device)
         return loss.detach(), fbpp.detach(), bpp.detach()
 
     def __call__(self, batch_x=None, starts=None, sync=True):

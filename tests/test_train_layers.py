@@ -118,6 +118,30 @@ def test_linear_path_dispatch_without_a_gpu():
     assert train._is_wide(12, 2048, 1024) and train._is_wide(256, 2048, 1024) and not train._is_wide(260, 2048, 1024)
 
 
+def test_step_scope_restores_the_module_state_when_the_step_raises():
+    """Whatever happens inside a step, pccx.train is left as outside one: no arena installed, the arena ended, autocast off, also for
+    the first half of a step cut in two (end=False), whose arena would otherwise stay open for a second half that never comes."""
+    with _train_state() as train:
+        for end in (True, False):
+            arena, p = train.StepArena(), torch.nn.Parameter(torch.zeros(2))
+            p.grad = torch.ones(2)
+            with pytest.raises(ZeroDivisionError):
+                with train.step_scope("cpu", arena, autocast=True, params=[p], end=end) as forward_done:
+                    assert train._ARENA is arena and train._AUTOCAST is True and arena.active and p.grad is None
+                    forward_done()
+                    assert train._AUTOCAST is False and train._ARENA is arena
+                    1 / 0
+            assert train._ARENA is None and train._AUTOCAST is False and arena.active is False
+        with train.step_scope("cpu", arena, autocast=True, end=False):              # no exception: the first half leaves the arena open ...
+            pass
+        assert train._ARENA is None and train._AUTOCAST is False and arena.active is True
+        with train.step_scope("cpu", arena, params=[p], begin=False):                # ... and the second half ends it
+            assert train._ARENA is arena and arena.active
+        assert train._ARENA is None and arena.active is False
+        with train.step_scope("cpu"):                                                # an eager step on the CPU runs without an arena
+            assert train._ARENA is None
+
+
 def _linear_ref(x, W, b, gz, autocast):
     """float64 forward / dX / dW / db of z = x W^T + b; autocast: the bf16 form, the forward rounded once after the bias"""
     r = _bf if autocast else (lambda a: a.astype(np.float64))
