@@ -317,6 +317,35 @@ PCCX_API int pccx_ae_decode_h2(const float *latent_q, int P, int d, int k, const
                                const float *nrm_center, const float *nrm_longest, int S, double margin, float *pc_out,
                                void *stream);
 
+/* ---- duplicate patches (csrc/patch_groups.hip) ---------------------------------------------------------------------------
+ * In octree_mode "reference" a cloud has at most 8 distinct patch centres (the bug-compatible decode reads one byte of the
+ * stream; rows np-1 .. 63 repeat the last centre), so most of a batch's patches are copies of an earlier patch of their cloud.
+ * pccx_patch_groups finds them on the device: key row of patch p = floats_a words of keys_a row p followed by floats_b words of
+ * keys_b row p (keys_b may be NULL with floats_b = 0), compared as uint32 words.  rep (B*S) int32: the smallest patch of p's cloud
+ * with an equal key row (rep[p] == p: a representative); uniq (B*S) int32: the representatives in ascending order; n_uniq: their
+ * count, 1 int32 ON THE DEVICE -- nothing returns to the host.  workspace: pccx_patch_groups_workspace_ints(B) int32.  1 <= S <= 1024.
+ * The *_list entry points below take uniq / n_uniq (or rep), do the listed patches only and leave the rows of the others as they
+ * were; NULL lists mean every patch, bit for bit the entry point without the suffix.  pccx_replicate_rows then overwrites, in up to
+ * three (P, row_floats) arrays (a1, a2 may be NULL), every row p with rep[p] != p by row rep[p]. */
+PCCX_API size_t pccx_patch_groups_workspace_ints(int B);
+PCCX_API int pccx_patch_groups(const float *keys_a, int floats_a, const float *keys_b, int floats_b, int B, int S, int32_t *rep,
+                               int32_t *uniq, int32_t *n_uniq, int32_t *workspace, void *stream);
+PCCX_API int pccx_replicate_rows(const int32_t *rep, int64_t P, int row_floats, float *a0, float *a1, float *a2, void *stream);
+/* pccx_knn for the queries with rep[b*M + m] == b*M + m only (rep over the (B, M) queries; NULL = all). */
+PCCX_API int pccx_knn_list(const float *q, int B, int M, const float *ref, int N, int K, float *dists, int64_t *idx, float *nn,
+                           float patch_scale, const int32_t *rep, void *stream);
+PCCX_API int pccx_patch_knn16_list(const float *patches, int P, int K, void *nbr, const int32_t *uniq, const int32_t *n_uniq,
+                                   void *stream);
+PCCX_API int pccx_ae_encode_h2_tables_list(const float *patches, int P, int K, const float *enc_blob, const float *h2_blob, int d,
+                                           int L, float *latent_raw, float *latent, float *latent_q, const void *tables,
+                                           const int32_t *uniq, const int32_t *n_uniq, void *stream);
+/* The decoder over the listed patches (keys: centre row + latent_q row): each result lands in its own patch's place of patches_out /
+ * pc_out; pccx_replicate_rows with row_floats = 3 k fills the places of the copies. */
+PCCX_API int pccx_ae_decode_h2_list(const float *latent_q, int P, int d, int k, const float *dec_blob, const float *h2_blob,
+                                    float *workspace, float *patches_out, float scale, const float *centres,
+                                    const float *nrm_center, const float *nrm_longest, int S, double margin, float *pc_out,
+                                    const int32_t *uniq, const int32_t *n_uniq, void *stream);
+
 /* AE.ConditionalProbabilityModel.forward (AE.py:107-123) + pn_kit.pmf_to_cdf (pn_kit.py:452-461)
  * + torchac's float-CDF -> 16-bit conversion.  centres: (B,S,3), S % 16 == 0.  Any of the outputs
  * may be NULL: pmf (B,S,d,L) f32; cdf (B,S,d,L+1) f32; cdf_int (B,S,d,L+1) int32 holding uint16. */

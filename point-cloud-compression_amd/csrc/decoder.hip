@@ -18,17 +18,22 @@
 #include "common.h"
 #include "mfma_chain.h"
 
+// uniq / n_uniq (patch_groups.hip; null = every patch): slot `patch` of the tiles holds patch uniq[patch], *n_uniq slots are live;
+// `ntiles` stays the host's tile count of all P patches, the stride of the fragment arrays
 __global__ __launch_bounds__(256, 2) void dec_head_kernel(const float *__restrict__ latent_q, int P, int d, int ntiles,
-                                                          const float *__restrict__ blob, f32x4 *__restrict__ h2p)
+                                                          const float *__restrict__ blob, f32x4 *__restrict__ h2p,
+                                                          const int *__restrict__ uniq, const int *__restrict__ n_uniq)
 {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int g = lane >> 4, n = lane & 15;
     const int tile = blockIdx.x * 4 + w;
-    if (tile >= ntiles) return;                                   // whole wave exits
+    if (uniq) P = *n_uniq;
+    if (tile >= (P + 15) / 16) return;                            // whole wave exits
     const int patch = tile * 16 + n;
+    const size_t src = patch < P ? (uniq ? (size_t)uniq[patch] : (size_t)patch) : 0;
     f32x4 in[1][1];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) in[0][0][r] = (patch < P && 4 * g + r < d) ? latent_q[(size_t)patch * d + 4 * g + r] : 0.f;
+    for (int r = 0; r < 4; ++r) in[0][0][r] = (patch < P && 4 * g + r < d) ? latent_q[src * d + 4 * g + r] : 0.f;
     f32x4 a1[1][16];
 #pragma unroll
     for (int mt = 0; mt < 16; ++mt) a1[0][mt] = *(const f32x4 *)(blob + DEC_H_B1 + 16 * mt + 4 * g);
@@ -49,9 +54,10 @@ __global__ __launch_bounds__(256, 2) void dec_head_kernel(const float *__restric
 }
 
 // the head for decoder_h2.hip (same kernel, same fp32 result; that file adds its own operand preparation)
-int pccx_dec_head_launch(const float *latent_q, int P, int d, int ntiles, const float *dec_blob, float *h2p, hipStream_t st)
+int pccx_dec_head_launch(const float *latent_q, int P, int d, int ntiles, const float *dec_blob, float *h2p, const int32_t *uniq,
+                         const int32_t *n_uniq, hipStream_t st)
 {
-    hipLaunchKernelGGL(dec_head_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, st, latent_q, P, d, ntiles, dec_blob, (f32x4 *)h2p);
+    hipLaunchKernelGGL(dec_head_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, st, latent_q, P, d, ntiles, dec_blob, (f32x4 *)h2p, uniq, n_uniq);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }
@@ -410,7 +416,7 @@ extern "C" int pccx_ae_decode(const float *latent_q, int P, int d, int k, const 
     hipStream_t st = (hipStream_t)stream;
     const int ntiles = (P + 15) / 16;
     hipLaunchKernelGGL(dec_head_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, st, latent_q, P, d, ntiles, dec_blob,
-                       (f32x4 *)workspace);
+                       (f32x4 *)workspace, (const int *)nullptr, (const int *)nullptr);
     PCCX_CHECK_LAUNCH();
     hipLaunchKernelGGL(dec_main_kernel<false>, dim3(dec_grid(ntiles, k)), dim3(256), 0, st, (const f32x4 *)workspace, latent_q, P, d,
                        k, ntiles, dec_blob, (const float *)nullptr, patches_out, scale, centres, nrm_center, nrm_longest,
@@ -509,7 +515,7 @@ extern "C" int pccx_ae_decode_b3(const float *latent_q, int P, int d, int k, con
     const int ntiles = (P + 15) / 16;
     f32x4 *h2p = (f32x4 *)workspace;
     uint4 *h3 = (uint4 *)(workspace + (size_t)64 * ntiles * 64 * 4);
-    hipLaunchKernelGGL(dec_head_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, st, latent_q, P, d, ntiles, dec_blob, h2p);
+    hipLaunchKernelGGL(dec_head_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, st, latent_q, P, d, ntiles, dec_blob, h2p, (const int *)nullptr, (const int *)nullptr);
     PCCX_CHECK_LAUNCH();
     const size_t items = (size_t)32 * ntiles;
     hipLaunchKernelGGL(b3_split_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, (const f32x4 *)h2p, h3, 1, 64, ntiles,

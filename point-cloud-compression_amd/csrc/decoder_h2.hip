@@ -13,7 +13,8 @@
 #include "common.h"
 #include "mfma_chain.h"
 
-int pccx_dec_head_launch(const float *latent_q, int P, int d, int ntiles, const float *dec_blob, float *h2p, hipStream_t st);   // decoder.hip
+int pccx_dec_head_launch(const float *latent_q, int P, int d, int ntiles, const float *dec_blob, float *h2p, const int32_t *uniq,
+                         const int32_t *n_uniq, hipStream_t st);   // decoder.hip
 
 #ifndef DEC_GROUP
 #define DEC_GROUP 64                       // patch blocks per group of the block order (as decoder.hip)
@@ -22,20 +23,23 @@ int pccx_dec_head_launch(const float *latent_q, int P, int d, int ntiles, const 
 // one wave per tile of 16 patches: the patch scales, then the two fp16 planes of the head activation
 // h2p: [64 kt][ntiles][64 lanes] f32x4 (lane (g, n): channels 16 kt + 4 g + r of patch n); h3: [32 t][ntiles][2][64 lanes] uint4
 __global__ __launch_bounds__(256) void dec_h2_prep_kernel(const f32x4 *__restrict__ h2p, const float *__restrict__ latent_q, int P, int d,
-                                                          int ntiles, float sig_h, uint4 *__restrict__ h3, float *__restrict__ pscale)
+                                                          int ntiles, float sig_h, uint4 *__restrict__ h3, float *__restrict__ pscale,
+                                                          const int *__restrict__ uniq, const int *__restrict__ n_uniq)
 {
     const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
     const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (tile >= ntiles) return;
+    if (uniq) P = *n_uniq;                                    // the live slots (dec_head_kernel); ntiles stays the stride
+    if (tile >= (P + 15) / 16) return;
     float m = 0.f;
     for (int kt = 0; kt < 64; ++kt) {
         const f32x4 v = h2p[((size_t)kt * ntiles + tile) * 64 + lane];
         m = fmaxf(fmaxf(m, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
     }
     const int patch = tile * 16 + n;
+    const size_t src = patch < P ? (uniq ? (size_t)uniq[patch] : (size_t)patch) : 0;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-        if (patch < P && 4 * g + r < d) m = fmaxf(m, fabsf(latent_q[(size_t)patch * d + 4 * g + r]));
+        if (patch < P && 4 * g + r < d) m = fmaxf(m, fabsf(latent_q[src * d + 4 * g + r]));
     m = fmaxf(m, __shfl_xor(m, 16));
     m = fmaxf(m, __shfl_xor(m, 32));
     const int rexp = (int)(__float_as_uint(m) >> 23) - 127;
@@ -71,7 +75,8 @@ __global__ __launch_bounds__(256, 2) void dec_main_h2_kernel(const uint4 *__rest
                                                              const float *__restrict__ hb, float *__restrict__ patches_out,
                                                              float inv_scale_div, const float *__restrict__ centres,
                                                              const float *__restrict__ nrm_center, const float *__restrict__ nrm_longest, int S,
-                                                             float one_minus_margin, float *__restrict__ pc_out)
+                                                             float one_minus_margin, float *__restrict__ pc_out,
+                                                             const int *__restrict__ uniq, const int *__restrict__ n_uniq)
 {
     static_assert(NT == 2 || NT == 4, "two or four patch tiles per wave");
     constexpr int NP = NT / 2;                                // tile pairs: inv_mlp runs once per pair
@@ -79,7 +84,11 @@ __global__ __launch_bounds__(256, 2) void dec_main_h2_kernel(const uint4 *__rest
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int g = lane >> 4, n = lane & 15;
     constexpr int GRP = DEC_GROUP * 2 / NT;
-    const int nblk = (ntiles + 4 * NT - 1) / (4 * NT);
+    // uniq / n_uniq (patch_groups.hip; null = every patch): tile slot s holds patch uniq[s], *n_uniq slots are live.  `ntiles` stays the
+    // host's count over all P patches (the stride of h3); ntl counts the live tiles.  A patch's result does not depend on its tile mates
+    // (its only data-dependent scale is its own pscale), so neither on its slot.
+    const int ntl = ((uniq ? *n_uniq : P) + 15) / 16;
+    const int nblk = (ntl + 4 * NT - 1) / (4 * NT);
     const int grp = blockIdx.x / (GRP * k), rem = blockIdx.x % (GRP * k);
     const int p = rem / GRP, blk = grp * GRP + rem % GRP;
     if (blk >= nblk) return;                                  // whole workgroup (before any barrier)
@@ -95,7 +104,7 @@ __global__ __launch_bounds__(256, 2) void dec_main_h2_kernel(const uint4 *__rest
     float sn[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-        tq[nt] = tile0 + nt < ntiles ? tile0 + nt : ntiles - 1;
+        tq[nt] = tile0 + nt < ntl ? tile0 + nt : ntl - 1;
         sn[nt] = pscale[tq[nt] * 16 + n];
     }
     f32x4 acc[NP][2][8];
@@ -193,6 +202,9 @@ __global__ __launch_bounds__(256, 2) void dec_main_h2_kernel(const uint4 *__rest
     asm volatile("" : "+v"(lane_t));
     const int g_t = lane_t >> 4, n_t = lane_t & 15;
     const int tile0_t = blk * 4 * NT + NT * wu;
+    const int *nu_t = n_uniq;                                  // the live count again, read after the loop like everything else here
+    asm volatile("" : "+s"(nu_t));
+    const int P_t = uniq ? __builtin_amdgcn_readfirstlane(*nu_t) : P, ntl_t = (P_t + 15) / 16;
     const float *meta = hb + DEC_H2_META;                      // the six layer multipliers: wave-uniform, read after the loop, kept in SGPRs
     asm volatile("" : "+s"(meta));                             // (the laundered pointer loses its address space: two FLAT loads per workgroup,
                                                                //  once; mfma_chain.h's opaque_uniform keeps it global but costs two spilled VGPRs here)
@@ -202,7 +214,7 @@ __global__ __launch_bounds__(256, 2) void dec_main_h2_kernel(const uint4 *__rest
     float sn_t[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-        const int tt = tile0_t + nt < ntiles ? tile0_t + nt : ntiles - 1;
+        const int tt = tile0_t + nt < ntl_t ? tile0_t + nt : ntl_t - 1;
         sn_t[nt] = pscale[tt * 16 + n_t];
     }
     const WStreamT<CH, NB> ws_t{ws.g, swt, DEC_H2_STREAM_CHUNKS, lane_t, wu, false};       // the same ring, addressed from the tail's lane id
@@ -221,9 +233,10 @@ __global__ __launch_bounds__(256, 2) void dec_main_h2_kernel(const uint4 *__rest
 #pragma unroll
                 for (int t = 0; t < 4; ++t) h2_split8(relu4(acc[pr][nt][2 * t]), relu4(acc[pr][nt][2 * t + 1]), rho0, i0[nt][t]);
                 const int patch = (tile0_t + 2 * pr + nt) * 16 + n_t;
+                const int src = patch < P_t ? (uniq ? uniq[patch] : patch) : 0;
                 f32x4 lat;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) lat[r] = (patch < P && 4 * g_t + r < d) ? latent_q[(size_t)patch * d + 4 * g_t + r] : 0.f;
+                for (int r = 0; r < 4; ++r) lat[r] = (patch < P_t && 4 * g_t + r < d) ? latent_q[(size_t)src * d + 4 * g_t + r] : 0.f;
                 h2_split8(lat, zero, sn_t[2 * pr + nt] * sig_q, i0[nt][4]);
             }
             f32x4 m0[2][8];
@@ -265,8 +278,9 @@ __global__ __launch_bounds__(256, 2) void dec_main_h2_kernel(const uint4 *__rest
         if (g_t == 0) {
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
-                const int tile = tile0_t + 2 * pr + nt, patch = tile * 16 + n_t;
-                if (tile < ntiles && patch < P) {
+                const int tile = tile0_t + 2 * pr + nt, slot = tile * 16 + n_t;
+                if (tile < ntl_t && slot < P_t) {
+                    const int patch = uniq ? uniq[slot] : slot;          // cloud, centre row and output slot are the ORIGINAL patch's
                     const float un = __fmul_rn(inv_out, __fdiv_rn(1.0f, sn_t[2 * pr + nt]));       // undo the operand scales (exact)
                     float v[3] = {__fmul_rn(m3[nt][0][0], un), __fmul_rn(m3[nt][0][1], un), __fmul_rn(m3[nt][0][2], un)};
                     if (patches_out) {
@@ -306,13 +320,17 @@ extern "C" size_t pccx_ae_decode_h2_workspace_floats(int P)
     return (size_t)(64 + 64) * ntiles * 64 * 4 + ntiles * 16;     // fp32 fragments of dec_head, their two fp16 planes, the patch scales
 }
 
-extern "C" int pccx_ae_decode_h2(const float *latent_q, int P, int d, int k, const float *dec_blob, const float *h2_blob, float *workspace,
-                                 float *patches_out, float scale, const float *centres, const float *nrm_center, const float *nrm_longest,
-                                 int S, double margin, float *pc_out, void *stream)
+// uniq / n_uniq: null, or the representatives of pccx_patch_groups over (centre row, latent_q row) and their count (both on the device).
+// Head, preparation and main then run over those patches only, 16 of them per tile in list order; each result is written to its patch's
+// own place in patches_out / pc_out, and pccx_replicate_rows (k * 3 floats per row) fills the places of the copies.
+extern "C" int pccx_ae_decode_h2_list(const float *latent_q, int P, int d, int k, const float *dec_blob, const float *h2_blob, float *workspace,
+                                      float *patches_out, float scale, const float *centres, const float *nrm_center, const float *nrm_longest,
+                                      int S, double margin, float *pc_out, const int32_t *uniq, const int32_t *n_uniq, void *stream)
 {
     if (P == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
     PCCX_CHECK_ARG(latent_q && dec_blob && h2_blob && workspace, "pccx_ae_decode_h2: null pointer");
     PCCX_CHECK_ARG(patches_out || pc_out, "pccx_ae_decode_h2: need patches_out and/or pc_out");
+    PCCX_CHECK_ARG(!uniq == !n_uniq, "pccx_ae_decode_h2_list: uniq and n_uniq come together");
     PCCX_CHECK_ARG(P >= 0 && d >= 1 && d <= 16 && k >= 1 && k <= 65535, "pccx_ae_decode_h2: unsupported P=%d d=%d k=%d", P, d, k);
     PCCX_CHECK_ARG(!pc_out || (centres && nrm_center && nrm_longest && S >= 1 && scale != 0.f),
                    "pccx_ae_decode_h2: pc_out needs centres, center, longest, S >= 1 and scale != 0");
@@ -321,18 +339,26 @@ extern "C" int pccx_ae_decode_h2(const float *latent_q, int P, int d, int k, con
     float *h2p = workspace;
     uint4 *h3 = (uint4 *)(workspace + (size_t)64 * ntiles * 64 * 4);
     float *pscale = workspace + (size_t)128 * ntiles * 64 * 4;
-    const int rc = pccx_dec_head_launch(latent_q, P, d, ntiles, dec_blob, h2p, st);
+    const int rc = pccx_dec_head_launch(latent_q, P, d, ntiles, dec_blob, h2p, uniq, n_uniq, st);
     if (rc != PCCX_OK) return rc;
-    hipLaunchKernelGGL(dec_h2_prep_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, st, (const f32x4 *)h2p, latent_q, P, d, ntiles, 32768.0f, h3, pscale);
+    hipLaunchKernelGGL(dec_h2_prep_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, st, (const f32x4 *)h2p, latent_q, P, d, ntiles, 32768.0f, h3, pscale, uniq, n_uniq);
     PCCX_CHECK_LAUNCH();
     // four patch tiles per wave unless PCCX_DEC_H2_NT=2 asks for the two-tile form (same results; read per call for A/B and tests)
     const char *e = getenv("PCCX_DEC_H2_NT");
     if (e && atoi(e) == 2)
         hipLaunchKernelGGL((dec_main_h2_kernel<2>), dim3(dec_h2_grid(ntiles, k, 2)), dim3(256), 0, st, (const uint4 *)h3, (const float *)pscale, latent_q, P,
-                           d, k, ntiles, h2_blob, patches_out, scale, centres, nrm_center, nrm_longest, S > 0 ? S : 1, (float)(1.0 - margin), pc_out);
+                           d, k, ntiles, h2_blob, patches_out, scale, centres, nrm_center, nrm_longest, S > 0 ? S : 1, (float)(1.0 - margin), pc_out, uniq, n_uniq);
     else
         hipLaunchKernelGGL((dec_main_h2_kernel<4>), dim3(dec_h2_grid(ntiles, k, 4)), dim3(256), 0, st, (const uint4 *)h3, (const float *)pscale, latent_q, P,
-                           d, k, ntiles, h2_blob, patches_out, scale, centres, nrm_center, nrm_longest, S > 0 ? S : 1, (float)(1.0 - margin), pc_out);
+                           d, k, ntiles, h2_blob, patches_out, scale, centres, nrm_center, nrm_longest, S > 0 ? S : 1, (float)(1.0 - margin), pc_out, uniq, n_uniq);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
+}
+
+extern "C" int pccx_ae_decode_h2(const float *latent_q, int P, int d, int k, const float *dec_blob, const float *h2_blob, float *workspace,
+                                 float *patches_out, float scale, const float *centres, const float *nrm_center, const float *nrm_longest,
+                                 int S, double margin, float *pc_out, void *stream)
+{
+    return pccx_ae_decode_h2_list(latent_q, P, d, k, dec_blob, h2_blob, workspace, patches_out, scale, centres, nrm_center, nrm_longest, S, margin,
+                                  pc_out, nullptr, nullptr, stream);
 }

@@ -65,7 +65,8 @@ template <bool NT2>
 __global__ __launch_bounds__(512, 1) void sa_pn_forward_h2_kernel(const float *__restrict__ x, int npatches, int K, const float *__restrict__ blob,
                                                                   const float *__restrict__ h2, int d, float spread, float half_spread,
                                                                   float *__restrict__ latent_raw, float *__restrict__ latent,
-                                                                  float *__restrict__ latent_q, const unsigned char *__restrict__ nbr_tab)
+                                                                  float *__restrict__ latent_q, const unsigned char *__restrict__ nbr_tab,
+                                                                  const int *__restrict__ uniq, const int *__restrict__ n_uniq)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     f32x4 *sw1 = (f32x4 *)smem;
@@ -100,7 +101,10 @@ __global__ __launch_bounds__(512, 1) void sa_pn_forward_h2_kernel(const float *_
         if (tid0 == 0) *srmax = 0u;
     }
     __syncthreads();
-  for (size_t P = blockIdx.x; P < (size_t)npatches; P += gridDim.x) {
+  // uniq / n_uniq (patch_groups.hip): the patches to do, counted on the device; null = all of them.  Every index is wave-uniform.
+  const int nlist = uniq ? *n_uniq : npatches;
+  for (int slot = blockIdx.x; slot < nlist; slot += gridDim.x) {
+    const size_t P = uniq ? (size_t)uniq[slot] : (size_t)slot;
     const int lane = fresh_lane(), tid = wu * 64 + lane;
     const float *xp = x + P * (size_t)K * 3;
     {   // the patch's power-of-two normalisation
@@ -407,13 +411,17 @@ extern "C" int pccx_ae_encode_h2_ws(const float *patches, int P, int K, const fl
 
 // the fused kernel alone, on neighbour tables the caller has filled with pccx_patch_knn16 (the two launches of pccx_ae_encode_h2_ws as
 // two calls: what a host that times or schedules the kernels separately uses -- bench.py's stage table)
-extern "C" int pccx_ae_encode_h2_tables(const float *patches, int P, int K, const float *enc_blob, const float *h2_blob, int d, int L,
-                                        float *latent_raw, float *latent, float *latent_q, const void *workspace, void *stream)
+// uniq / n_uniq: null, or the representatives of pccx_patch_groups and their count (both on the device): only their latent rows are written
+// (pccx_replicate_rows then fills the rows of the copies), from tables pccx_patch_knn16_list wrote for the same list
+extern "C" int pccx_ae_encode_h2_tables_list(const float *patches, int P, int K, const float *enc_blob, const float *h2_blob, int d, int L,
+                                             float *latent_raw, float *latent, float *latent_q, const void *workspace, const int32_t *uniq,
+                                             const int32_t *n_uniq, void *stream)
 {
     if (P == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
     PCCX_CHECK_ARG(patches && enc_blob && h2_blob && latent_raw && latent && latent_q && workspace, "pccx_ae_encode_h2_tables: null pointer");
     PCCX_CHECK_ARG(P >= 0 && pccx_ae_encode_h2_fused_ok(K), "pccx_ae_encode_h2_tables: K=%d does not fit the fused kernel (pccx_ae_encode_h2_fused_ok)", K);
     PCCX_CHECK_ARG(d >= 1 && d <= 16 && L >= 1, "pccx_ae_encode_h2_tables: unsupported d=%d L=%d", d, L);
+    PCCX_CHECK_ARG(!uniq == !n_uniq, "pccx_ae_encode_h2_tables_list: uniq and n_uniq come together");
     PCCX_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "pccx_ae_encode_h2_tables: the tables must be 16-byte aligned");
     const float spread = (float)((double)L - 0.2);
     const float half = (float)(((double)L - 0.2) / 2);
@@ -425,12 +433,18 @@ extern "C" int pccx_ae_encode_h2_tables(const float *patches, int P, int K, cons
     if (nt2) {
         PCCX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&sa_pn_forward_h2_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL(sa_pn_forward_h2_kernel<true>, dim3(grid), dim3(512), fh_lds_bytes(K), (hipStream_t)stream, patches, P, K, enc_blob, h2_blob, d,
-                           spread, half, latent_raw, latent, latent_q, (const unsigned char *)workspace);
+                           spread, half, latent_raw, latent, latent_q, (const unsigned char *)workspace, uniq, n_uniq);
     } else {
         PCCX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&sa_pn_forward_h2_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL(sa_pn_forward_h2_kernel<false>, dim3(grid), dim3(512), fh_lds_bytes(K), (hipStream_t)stream, patches, P, K, enc_blob, h2_blob, d,
-                           spread, half, latent_raw, latent, latent_q, (const unsigned char *)workspace);
+                           spread, half, latent_raw, latent, latent_q, (const unsigned char *)workspace, uniq, n_uniq);
     }
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
+}
+
+extern "C" int pccx_ae_encode_h2_tables(const float *patches, int P, int K, const float *enc_blob, const float *h2_blob, int d, int L,
+                                        float *latent_raw, float *latent, float *latent_q, const void *workspace, void *stream)
+{
+    return pccx_ae_encode_h2_tables_list(patches, P, K, enc_blob, h2_blob, d, L, latent_raw, latent, latent_q, workspace, nullptr, nullptr, stream);
 }

@@ -47,7 +47,8 @@ __device__ __forceinline__ int block_scan_find(int h, int remaining, int *s_wsum
 
 __global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ q, int M, const float *__restrict__ ref,
                                                   int N, int K, int Kp, float *__restrict__ dists,
-                                                  int64_t *__restrict__ idx, float *__restrict__ nn, float patch_scale)
+                                                  int64_t *__restrict__ idx, float *__restrict__ nn, float patch_scale,
+                                                  const int *__restrict__ rep)
 {
     extern __shared__ unsigned char smem_raw[];
     unsigned long long *sel = (unsigned long long *)smem_raw;   // [Kp]
@@ -59,6 +60,7 @@ __global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ q, i
 
     const int tid = threadIdx.x;
     const int m = blockIdx.x, b = blockIdx.y;
+    if (rep && rep[b * M + m] != b * M + m) return;             // a copy of an earlier query of this cloud: see knn_fast_kernel
     const float *rp = ref + (size_t)b * N * 3;
     const float qx = q[((size_t)b * M + m) * 3], qy = q[((size_t)b * M + m) * 3 + 1], qz = q[((size_t)b * M + m) * 3 + 2];
 
@@ -243,13 +245,14 @@ __device__ __forceinline__ void knn_level(const unsigned (&key)[KNN_PPT], int *h
 
 __global__ __launch_bounds__(256, 4) void knn_fast_kernel(const float *__restrict__ q, int M, const float *__restrict__ ref,
                                                        int N, int K, float *__restrict__ dists, int64_t *__restrict__ idx,
-                                                       float *__restrict__ nn, float patch_scale)
+                                                       float *__restrict__ nn, float patch_scale, const int *__restrict__ rep)
 {
     __shared__ int hist[KNN_BINS];
     __shared__ unsigned long long selA[256], selB[KNN_CAPB];
     __shared__ int s_wsum[4], s_found[3], s_cnt[2];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int m = blockIdx.x, b = blockIdx.y;
+    if (rep && rep[b * M + m] != b * M + m) return;                       // a copy of an earlier query of this cloud (patch_groups.hip): its rows stay unwritten
     const float *rp = ref + (size_t)b * N * 3;
     const size_t qo = ((size_t)b * M + m) * 3;
     const float qx = q[qo], qy = q[qo + 1], qz = q[qo + 2];
@@ -373,8 +376,10 @@ __global__ __launch_bounds__(256, 4) void knn_fast_kernel(const float *__restric
     }
 }
 
-extern "C" int pccx_knn(const float *q, int B, int M, const float *ref, int N, int K, float *dists, int64_t *idx,
-                        float *nn, float patch_scale, void *stream)
+// rep: null, or the (B * M) table of pccx_patch_groups over the queries -- only queries with rep[p] == p are computed, the output rows
+// of the others are left as they were (their results equal their representative's: same query, same cloud)
+extern "C" int pccx_knn_list(const float *q, int B, int M, const float *ref, int N, int K, float *dists, int64_t *idx,
+                             float *nn, float patch_scale, const int32_t *rep, void *stream)
 {
     if (B == 0 || M == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
     PCCX_CHECK_ARG(q && ref && (dists || idx || nn), "pccx_knn: null pointer (q, ref and at least one of dists / idx / nn are needed)");
@@ -389,12 +394,18 @@ extern "C" int pccx_knn(const float *q, int B, int M, const float *ref, int N, i
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if (N <= 256 * KNN_PPT && K <= 256)
         hipLaunchKernelGGL(knn_fast_kernel, dim3(M, B), dim3(256), 0, (hipStream_t)stream, q, M, ref, N, K, dists, idx, nn,
-                           patch_scale);
+                           patch_scale, rep);
     else
         hipLaunchKernelGGL(knn_kernel, dim3(M, B), dim3(256), shmem, (hipStream_t)stream, q, M, ref, N, K, Kp, dists, idx, nn,
-                           patch_scale);
+                           patch_scale, rep);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
+}
+
+extern "C" int pccx_knn(const float *q, int B, int M, const float *ref, int N, int K, float *dists, int64_t *idx,
+                        float *nn, float patch_scale, void *stream)
+{
+    return pccx_knn_list(q, B, M, ref, N, K, dists, idx, nn, patch_scale, nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------------------

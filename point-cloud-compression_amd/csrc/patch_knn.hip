@@ -24,13 +24,16 @@ __device__ __forceinline__ unsigned pk_umed3(unsigned a, unsigned b, unsigned c)
 
 template <typename IDX>
 __global__ __launch_bounds__(256) void patch_knn16_kernel(const float *__restrict__ x, int npatches, int K, unsigned char *__restrict__ nbr_bytes,
-                                                          size_t patch_stride)
+                                                          size_t patch_stride, const int *__restrict__ uniq, const int *__restrict__ n_uniq)
 {
     extern __shared__ __attribute__((aligned(16))) float sx[];      // [3K]
     const int tid = threadIdx.x;
     unsigned jmask = 15u;
     while ((int)jmask < K - 1) jmask = 2u * jmask + 1u;
-    for (size_t P = blockIdx.x; P < (size_t)npatches; P += gridDim.x) {
+    // uniq / n_uniq (patch_groups.hip): the patches to do, counted on the device; null = all of them.  A patch's table stays in its own slot.
+    const int nlist = uniq ? *n_uniq : npatches;
+    for (int slot = blockIdx.x; slot < nlist; slot += gridDim.x) {
+        const size_t P = uniq ? (size_t)uniq[slot] : (size_t)slot;
         const float *xp = x + P * (size_t)K * 3;
         for (int i = tid; i < 3 * K; i += 256) sx[i] = xp[i];
         __syncthreads();
@@ -147,24 +150,37 @@ extern "C" size_t pccx_patch_knn16_bytes(int P, int K)
 // patch_stride: bytes between the tables of consecutive patches (>= K * 16 * index bytes, a multiple of 16).  The unfused
 // SetAbstraction kernels park each patch's table at the head of that patch's own slice of the feature map, which they overwrite
 // only after reading it (encoder.hip).
-int pccx_patch_knn16_strided(const float *patches, int P, int K, void *nbr, size_t patch_stride, hipStream_t stream)
+static int patch_knn16_launch(const float *patches, int P, int K, void *nbr, size_t patch_stride, hipStream_t stream, const int32_t *uniq,
+                              const int32_t *n_uniq)
 {
     // 8 workgroups of 4 waves per CU fill the 32 wave slots; no state is kept between patches, so the grid is one workgroup per
     // patch up to 64 per CU
     const int grid = P < 256 * 64 ? P : 256 * 64;
     if (K <= 256)
-        hipLaunchKernelGGL(patch_knn16_kernel<uint8_t>, dim3(grid), dim3(256), (size_t)K * 12, stream, patches, P, K, (unsigned char *)nbr, patch_stride);
+        hipLaunchKernelGGL(patch_knn16_kernel<uint8_t>, dim3(grid), dim3(256), (size_t)K * 12, stream, patches, P, K, (unsigned char *)nbr, patch_stride, uniq, n_uniq);
     else
-        hipLaunchKernelGGL(patch_knn16_kernel<uint16_t>, dim3(grid), dim3(256), (size_t)K * 12, stream, patches, P, K, (unsigned char *)nbr, patch_stride);
+        hipLaunchKernelGGL(patch_knn16_kernel<uint16_t>, dim3(grid), dim3(256), (size_t)K * 12, stream, patches, P, K, (unsigned char *)nbr, patch_stride, uniq, n_uniq);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }
 
-extern "C" int pccx_patch_knn16(const float *patches, int P, int K, void *nbr, void *stream)
+int pccx_patch_knn16_strided(const float *patches, int P, int K, void *nbr, size_t patch_stride, hipStream_t stream)
+{
+    return patch_knn16_launch(patches, P, K, nbr, patch_stride, stream, nullptr, nullptr);
+}
+
+// uniq / n_uniq: null, or the representatives of pccx_patch_groups and their count (both on the device): only their tables are written
+extern "C" int pccx_patch_knn16_list(const float *patches, int P, int K, void *nbr, const int32_t *uniq, const int32_t *n_uniq, void *stream)
 {
     if (P == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
     PCCX_CHECK_ARG(patches && nbr, "pccx_patch_knn16: null pointer");
+    PCCX_CHECK_ARG(!uniq == !n_uniq, "pccx_patch_knn16_list: uniq and n_uniq come together");
     PCCX_CHECK_ARG(P >= 0 && K >= 16 && K <= 1024 && K % 16 == 0, "pccx_patch_knn16: need K %% 16 == 0, 16 <= K <= 1024 (K=%d)", K);
     PCCX_CHECK_ARG(((uintptr_t)nbr & 15) == 0, "pccx_patch_knn16: the table must be 16-byte aligned");
-    return pccx_patch_knn16_strided(patches, P, K, nbr, (size_t)K * 16 * (size_t)pccx_patch_knn16_index_bytes(K), (hipStream_t)stream);
+    return patch_knn16_launch(patches, P, K, nbr, (size_t)K * 16 * (size_t)pccx_patch_knn16_index_bytes(K), (hipStream_t)stream, uniq, n_uniq);
+}
+
+extern "C" int pccx_patch_knn16(const float *patches, int P, int K, void *nbr, void *stream)
+{
+    return pccx_patch_knn16_list(patches, P, K, nbr, nullptr, nullptr, stream);
 }

@@ -80,6 +80,13 @@ _SIGNATURES = {
     "pccx_pack_ae_decoder_h2": [_P] * 14 + [C.c_int, C.c_int, _P],
     "pccx_ae_decode_h2_workspace_floats": [C.c_int],
     "pccx_ae_decode_h2": [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_float, _P, _P, _P, C.c_int, C.c_double, _P, _P],
+    "pccx_patch_groups_workspace_ints": [C.c_int],
+    "pccx_patch_groups": [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P],
+    "pccx_replicate_rows": [_P, C.c_int64, C.c_int, _P, _P, _P, _P],
+    "pccx_knn_list": [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, C.c_float, _P, _P],
+    "pccx_patch_knn16_list": [_P, C.c_int, C.c_int, _P, _P, _P, _P],
+    "pccx_ae_encode_h2_tables_list": [_P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P],
+    "pccx_ae_decode_h2_list": [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_float, _P, _P, _P, C.c_int, C.c_double, _P, _P, _P, _P],
     "pccx_prob_forward": [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P],
     "pccx_range_encode": [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, _P],
     "pccx_range_decode": [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P],
@@ -169,7 +176,7 @@ _SIGNATURES = {
     "pccx_adam_step_dev": [_P, _P, _P, _P, C.c_int64, _P, C.c_float, _P, C.c_float, C.c_float, C.c_float, _P],
     "pccx_quantize_st": [_P, C.c_int64, C.c_float, C.c_float, C.c_int, _P, _P, _P],
 }
-_RESTYPES = {"pccx_planes_floats_h2": C.c_size_t, "pccx_packed_linear_h2_floats": C.c_size_t, "pccx_planes_gemm_weight_floats_h2": C.c_size_t,
+_RESTYPES = {"pccx_patch_groups_workspace_ints": C.c_size_t, "pccx_planes_floats_h2": C.c_size_t, "pccx_packed_linear_h2_floats": C.c_size_t, "pccx_planes_gemm_weight_floats_h2": C.c_size_t,
              "pccx_streams_packed_bytes": C.c_size_t, "pccx_sort_keys_workspace_bytes": C.c_size_t, "pccx_train_sums_doubles": C.c_size_t, "pccx_ae_encoder_h2_blob_floats": C.c_size_t, "pccx_ae_decoder_h2_blob_floats": C.c_size_t,
              "pccx_ae_encode_h2_workspace_bytes": C.c_size_t, "pccx_ae_decode_h2_workspace_floats": C.c_size_t,
              "pccx_patch_knn16_bytes": C.c_size_t, "pccx_ae_encode_b3_workspace_bytes": C.c_size_t, "pccx_ae_encoder_blob_floats": C.c_size_t, "pccx_ae_decoder_blob_floats": C.c_size_t,

@@ -167,11 +167,14 @@ def stream_sizes(directory, names, threads=0):
 
 class Codec:
     def __init__(self, ae, prob, K=256, ALPHA=2, N0=1024, octree_mode="reference", margin=0.01, matmul=None,
-                 decoder_matmul=None, sa_matmul=None, pn_matmul=None):
+                 decoder_matmul=None, sa_matmul=None, pn_matmul=None, group_duplicates=True):
         """matmul: how the three transforms (SetAbstraction, PointNet, decoder) form their fp32 products --
         "f32" = v_mfma_f32_16x16x4_f32 (bit-for-bit a k-ordered fmaf chain), "bf16x3" = each fp32 operand split exactly into
         three bf16 pieces, six products per pair on the bf16 matrix cores, fp32 accumulate (fp32-level error, 2.6x the
-        rate).  None = pccx.DEFAULT_MATMUL.  The per-stage arguments override it."""
+        rate).  None = pccx.DEFAULT_MATMUL.  The per-stage arguments override it.
+        group_duplicates: transform each distinct patch of a cloud once and copy the result to its duplicates (ops.patch_groups; in
+        octree_mode "reference" a cloud has at most 8 distinct centres among its 64).  Same bytes, same
+        reconstruction either way; False computes every patch."""
         from . import DEFAULT_MATMUL
         matmul = matmul or DEFAULT_MATMUL
         self.ae, self.prob = ae, prob
@@ -183,6 +186,7 @@ class Codec:
         self.K, self.ALPHA, self.N0 = K, ALPHA, N0
         self.k = K // ALPHA                                  # compress.py:46
         self.octree_mode = octree_mode
+        self.group_duplicates = bool(group_duplicates)
         self.margin = margin
         if ae.K != K or ae.k != self.k:
             raise ValueError("AE was built for a different K / k")
@@ -209,11 +213,15 @@ class Codec:
         with stage("octree_decode"):
             rec, _ = ops.octree_decode(oc["bytes"], oc["nbytes"], self.octree_mode, S)   # compress.py:100
         scale = float((N / self.N0) ** (1 / 3))
+        # equal centres of one cloud select the same patch and encode to the same latent rows: one transform per distinct centre.
+        # With keep_extras the search still runs for every centre, so that extras["patches"] / ["knn_idx"] are complete arrays.
+        groups = ops.patch_groups(rec) if self.group_duplicates else None
         with stage("knn_patches"):
             nn = ops.knn_points(rec, pcn, self.K, patch_scale=scale,                 # compress.py:105-108 (KNN_Patching keeps the
-                                return_dists=False, return_idx=keep_extras)          # patches; the indices only for diagnostics)
+                                return_dists=False, return_idx=keep_extras,          # patches; the indices only for diagnostics)
+                                rep=None if keep_extras or groups is None else groups.rep)
         patches = nn.knn.view(B * S, self.K, 3)
-        raw, latent, q = self.ae.encode(patches, sa_matmul=self.sa_matmul, pn_matmul=self.pn_matmul)                                     # compress.py:113-127
+        raw, latent, q = self.ae.encode(patches, sa_matmul=self.sa_matmul, pn_matmul=self.pn_matmul, groups=groups)                      # compress.py:113-127
         with stage("prob"):
             cdf_int = self.prob.run(rec, ("cdf_int",))["cdf_int"]                    # compress.py:131-134
         with stage("range_encode"):
@@ -247,7 +255,7 @@ class Codec:
         with stage("ae_decode"):
             return self.ae.decode(q.view(B * S, d), rec.view(B * S, 3), comp.c[:, :3].contiguous(),
                                   comp.c[:, 3].contiguous(), S=S, scale=scale, margin=self.margin,
-                                  matmul=self.decoder_matmul)
+                                  matmul=self.decoder_matmul, group=self.group_duplicates)
 
 
 def d1_psnr(orig, recon):

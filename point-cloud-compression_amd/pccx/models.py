@@ -351,7 +351,7 @@ class AE(nn.Module):
         else:
             raise ValueError(f"pn_matmul={matmul!r}: expected 'f32', 'bf16x3' or 'f16x2'")
 
-    def encode(self, patches, sa_matmul=None, pn_matmul=None, fused=True):
+    def encode(self, patches, sa_matmul=None, pn_matmul=None, fused=True, groups=None):
         """patches (BS,K,3), centred and scaled -> (latent_raw, latent, latent_quantized), each (BS,d).
         = ae.sa + ae.pn + sigmoid spread + round (compress.py:113-127, AE.py:37-45).
         sa_matmul / pn_matmul: "f32" (exact-fp32 MFMA), "bf16x3" (fp32 products of three bf16 pieces per operand on the
@@ -359,9 +359,21 @@ class AE(nn.Module):
         both split modes: fp32-level error, a latent within ~1e-6 of a rounding boundary may round the other way);
         None = pccx.DEFAULT_MATMUL.  "f16x2" exists as the fused kernel only (it holds every K up to 1024): with fused=False or different modes
         for the two modules, an "f16x2" request runs the bf16x3 kernels.  fused=False forces the
-        two-kernel path (feature map through HBM)."""
+        two-kernel path (feature map through HBM).
+        groups (ops.patch_groups over the patches' centres): the patches with groups.rep[p] != p are copies of patch rep[p] (their rows of
+        `patches` need not even be filled in).  The fused f16x2 kernels then transform the representatives only; every path ends by copying
+        the representatives' three latent rows to their copies, so the results are complete (P, d) arrays either way."""
         x = _f32c(patches, "AE.encode")
+        outs = self._encode(x, sa_matmul, pn_matmul, fused, groups)
+        if groups is not None:
+            from .ops import replicate_rows
+            replicate_rows(groups, *outs)
+        return outs
+
+    def _encode(self, x, sa_matmul, pn_matmul, fused, groups):
         P, K, _ = x.shape
+        if groups is not None and groups.rep.numel() != P:
+            raise _lib.PccxError(f"AE.encode: groups of {groups.rep.numel()} patches for {P} patches")
         if not self.fused_d:
             return self.encode_generic(x)
         outs = [torch.empty(P, self.d, device=x.device, dtype=torch.float32) for _ in range(3)]
@@ -372,11 +384,12 @@ class AE(nn.Module):
             nbytes = _lib.load().pccx_ae_encode_h2_workspace_bytes(P, K)
             ws = workspace("patch_knn16", (nbytes + 3) // 4, x.device)
             # the two launches of pccx_ae_encode_h2_ws as two calls, so that a stage timer sees each kernel on its own
+            uq, nu = (groups.uniq.data_ptr(), groups.n_uniq.data_ptr()) if groups is not None else (None, None)
             with stage("patch_knn16"):
-                _lib.call("pccx_patch_knn16", x.data_ptr(), P, K, ws.data_ptr(), _stream())
+                _lib.call("pccx_patch_knn16_list", x.data_ptr(), P, K, ws.data_ptr(), uq, nu, _stream())
             with stage("sa_pn_forward"):
-                _lib.call("pccx_ae_encode_h2_tables", x.data_ptr(), P, K, enc.data_ptr(), self._enc_h2_blob(x.device).data_ptr(), self.d, self.L,
-                          outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), ws.data_ptr(), _stream())
+                _lib.call("pccx_ae_encode_h2_tables_list", x.data_ptr(), P, K, enc.data_ptr(), self._enc_h2_blob(x.device).data_ptr(), self.d, self.L,
+                          outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), ws.data_ptr(), uq, nu, _stream())
             return tuple(outs)
         if sa_matmul == "f16x2" or pn_matmul == "f16x2":      # K beyond the fused kernel, or fused=False: the bf16x3 kernels
             sa_matmul = "bf16x3" if sa_matmul == "f16x2" else sa_matmul
@@ -435,11 +448,13 @@ class AE(nn.Module):
             _lib.call("pccx_pack_ae_decoder_b3", dec.data_ptr(), self.k, self._dec_b3.data_ptr(), _stream())
         return self._dec_b3
 
-    def decode(self, latent_q, centres=None, center=None, longest=None, S=None, scale=None, margin=0.01, matmul=None):
+    def decode(self, latent_q, centres=None, center=None, longest=None, S=None, scale=None, margin=0.01, matmul=None, group=False):
         """latent_q (BS,d) -> decoded patches (BS,k,3) (AE.py:48-53).  With centres/center/longest/S/scale
         it returns instead the reassembled, denormalised cloud (B,S*k,3) of decompress.py:104-116.
         matmul="bf16x3" / "f16x2" evaluate the matrix products as fp32 products of three bf16 / two exactly scaled fp16 pieces
-        per operand on the matrix cores (fp32-level error, not bit-identical to "f32"); None = pccx.DEFAULT_MATMUL."""
+        per operand on the matrix cores (fp32-level error, not bit-identical to "f32"); None = pccx.DEFAULT_MATMUL.
+        group=True (reassembling form, "f16x2"): patches of a cloud with the same (centre row, latent_q row) decode to the same 3 k floats, so
+        the decoder runs once per distinct pair (ops.patch_groups) and the copies are filled from it; the other modes decode every patch."""
         matmul = matmul or _pccx_default_matmul()
         q = _f32c(latent_q, "AE.decode")
         P = q.shape[0]
@@ -475,6 +490,14 @@ class AE(nn.Module):
         center = _f32c(center.reshape(B, 3), "AE.decode.center")
         longest = _f32c(longest.reshape(B), "AE.decode.longest")
         pc = torch.empty(B, S * self.k, 3, device=q.device, dtype=torch.float32)
+        if group and matmul == "f16x2":
+            from .ops import patch_groups, replicate_rows
+            groups = patch_groups(centres.view(B, S, 3), q.view(B, S, self.d))
+            _lib.call("pccx_ae_decode_h2_list", q.data_ptr(), P, self.d, self.k, dec.data_ptr(), *extra, ws.data_ptr(), None, float(scale),
+                      centres.data_ptr(), center.data_ptr(), longest.data_ptr(), int(S), float(margin), pc.data_ptr(),
+                      groups.uniq.data_ptr(), groups.n_uniq.data_ptr(), _stream())
+            replicate_rows(groups, pc)
+            return pc
         _lib.call(fn, q.data_ptr(), P, self.d, self.k, dec.data_ptr(), *extra, ws.data_ptr(), None, float(scale),
                   centres.data_ptr(), center.data_ptr(), longest.data_ptr(), int(S), float(margin), pc.data_ptr(), _stream())
         return pc

@@ -10,6 +10,9 @@ import torch
 from . import _lib
 
 KNN = collections.namedtuple("KNN", ["dists", "idx", "knn"])      # pytorch3d's _KNN result shape
+# duplicate patches of a batch (patch_groups): rep (B*S) i32 = first patch of the same cloud with an equal key row, uniq (B*S) i32 = the
+# patches with rep[p] == p, n_uniq (1) i32 = how many -- all on the device, never read back
+Groups = collections.namedtuple("Groups", ["rep", "uniq", "n_uniq"])
 OCTREE_BPP_DICT = {1024: 0.07, 512: 0.125, 256: 0.25, 128: 0.5, 64: 1.0}   # pn_kit.py:17-23
 
 
@@ -135,10 +138,38 @@ def knn_gather(x, idx):
     return index_points(x, idx)
 
 
-def knn_points(p1, p2, K, return_nn=True, patch_scale=0.0, return_dists=True, return_idx=True):
+def patch_groups(keys_a, keys_b=None):
+    """Which patches of a batch repeat an earlier patch of their own cloud (csrc/patch_groups.hip).  keys_a (B,S,fa) f32 and optionally
+    keys_b (B,S,fb) f32: the key row of patch (b, i) is the fa + fb words of the two rows, compared bit for bit.  In octree_mode
+    "reference" the decoded centres take at most 8 distinct values per cloud (octree_np.py:47-112 consumes one byte of the stream), so
+    the transforms run on about an eighth of the patches and the results are copied (replicate_rows).  Returns Groups, all on the device."""
+    a = _f32c(keys_a, "patch_groups.keys_a")
+    B, S, fa = a.shape
+    b = _f32c(keys_b.reshape(B, S, -1), "patch_groups.keys_b") if keys_b is not None else None
+    buf = torch.empty(2 * B * S + 1 + _lib.load().pccx_patch_groups_workspace_ints(B), device=a.device, dtype=torch.int32)
+    g = Groups(buf[:B * S], buf[B * S:2 * B * S], buf[2 * B * S:2 * B * S + 1])
+    with stage("patch_groups"):
+        _lib.call("pccx_patch_groups", a.data_ptr(), fa, b.data_ptr() if b is not None else None, b.shape[2] if b is not None else 0, B, S,
+                  g.rep.data_ptr(), g.uniq.data_ptr(), g.n_uniq.data_ptr(), buf[2 * B * S + 1:].data_ptr(), _stream())
+    return g
+
+
+def replicate_rows(groups, *arrays):
+    """Rows of the duplicates := rows of their representatives, in place, in up to three dense f32 arrays of P rows each (same row width)."""
+    P = groups.rep.numel()
+    if not arrays or len(arrays) > 3 or any(t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != arrays[0].numel() or t.numel() % max(P, 1)
+                                            for t in arrays):
+        raise _lib.PccxError("replicate_rows: one to three dense float32 arrays of P rows each, all of one row width, are expected")
+    ptrs = [t.data_ptr() for t in arrays] + [None] * (3 - len(arrays))
+    with stage("replicate"):
+        _lib.call("pccx_replicate_rows", groups.rep.data_ptr(), P, arrays[0].numel() // max(P, 1), *ptrs, _stream())
+
+
+def knn_points(p1, p2, K, return_nn=True, patch_scale=0.0, return_dists=True, return_idx=True, rep=None):
     """pytorch3d.ops.knn_points (compress.py:71, pn_kit.py:190).  With patch_scale != 0 the third
     field holds (nn - p1) * patch_scale, i.e. compress.py:72 and :108 fused.  return_dists / return_idx = False leave that field None
-    and its bytes unwritten (KNN_Patching, compress.py:70-74, keeps the gathered points only)."""
+    and its bytes unwritten (KNN_Patching, compress.py:70-74, keeps the gathered points only).
+    rep: Groups.rep over the (B, M) queries -- only the representatives are searched, the rows of the other queries stay unwritten."""
     p1, p2 = _f32c(p1, "knn_points.p1"), _f32c(p2, "knn_points.p2")
     B, M, _ = p1.shape
     N = p2.shape[1]
@@ -146,7 +177,9 @@ def knn_points(p1, p2, K, return_nn=True, patch_scale=0.0, return_dists=True, re
     idx = torch.empty(B, M, K, device=p1.device, dtype=torch.int64) if return_idx else None
     nn = torch.empty(B, M, K, 3, device=p1.device, dtype=torch.float32) if return_nn else None
     ptr = lambda t: t.data_ptr() if t is not None else None
-    _lib.call("pccx_knn", p1.data_ptr(), B, M, p2.data_ptr(), N, int(K), ptr(dists), ptr(idx), ptr(nn), float(patch_scale), _stream())
+    if rep is not None and (rep.dtype != torch.int32 or rep.numel() != B * M or not rep.is_cuda or not rep.is_contiguous()):
+        raise _lib.PccxError("knn_points: rep must be the dense int32 (B*M) table of patch_groups over the queries")
+    _lib.call("pccx_knn_list", p1.data_ptr(), B, M, p2.data_ptr(), N, int(K), ptr(dists), ptr(idx), ptr(nn), float(patch_scale), ptr(rep), _stream())
     return KNN(dists, idx, nn)
 
 
