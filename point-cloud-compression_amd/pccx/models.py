@@ -8,8 +8,13 @@ is no torch / CPU compute path (inference only, as compress.py / decompress.py u
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, MATMUL_MODES
 from .ops import _stream, _f32c, stage
+
+
+def check_matmul(name, value):
+    if value not in MATMUL_MODES:
+        raise ValueError(f"{name}={value!r}: expected 'f32', 'bf16x3' or 'f16x2'")
 
 
 def _conv_stack(chans, relu):
@@ -32,6 +37,21 @@ def _folded(conv, relu, device):
     return FoldedLinear(conv.weight, conv.bias, relu, None, device)
 
 
+def _folded_sequence(mods, device):
+    """The Linear / 1x1 Conv2d modules of a Sequential's list as generic layers, each with the ReLU that follows it fused."""
+    return [_folded(m, i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU), device)
+            for i, m in enumerate(mods) if isinstance(m, (nn.Linear, nn.Conv2d))]
+
+
+def _lazy_layers(module, device, build):
+    """module._layers = (device, build(device)): the generic path's packed layers, built on first use on a device.  The owner's
+    load_state_dict drops them by setting _layers to None."""
+    device = torch.device(device)
+    if module._layers is None or module._layers[0] != device:
+        object.__setattr__(module, "_layers", (device, build(device)))      # not a sub-module / buffer: plain attribute
+    return module._layers[1]
+
+
 class _Params(nn.Module):
     """Sub-modules of the reference's models.  They hold the parameters under the reference's state_dict keys AND are
     callable like the reference's (compress.py:113-121 calls ae.sa(x) / ae.pn(x), decompress.py:97-101 ae.inv_pool /
@@ -52,9 +72,7 @@ class _Params(nn.Module):
 
 class _ConvStack(_Params):
     def _stack(self, device):
-        if self._layers is None or self._layers[0] != torch.device(device):
-            object.__setattr__(self, "_layers", (torch.device(device), [_folded(m[0], len(m) > 1, device) for m in self.mlp_Modules]))
-        return self._layers[1]
+        return _lazy_layers(self, device, lambda dev: [_folded(m[0], len(m) > 1, dev) for m in self.mlp_Modules])
 
     def _rows(self, points):
         x = _f32c(points, type(self).__name__)
@@ -90,10 +108,8 @@ class SetAbstraction(_Params):      # pn_kit.SetAbstraction (pn_kit.py:146-161),
         new_xyz = pts if S == N else ops.index_points(pts, ops.farthest_point_sample_batch(pts, S, start_idx))   # :180-183
         nn_ = ops.knn_points(new_xyz, pts, self.K, patch_scale=1.0)                        # :190-191 (nn - centre)
         rows = nn_.knn.reshape(B * S * self.K, Cc).contiguous()
-        if self._layers is None or self._layers[0] != x.device:
-            object.__setattr__(self, "_layers", (x.device, [_folded(self.conv0, True, x.device), _folded(self.conv1, True, x.device),
-                                                            _folded(self.conv2, self.finalRelu, x.device)]))
-        for layer in self._layers[1]:
+        for layer in _lazy_layers(self, x.device, lambda dev: [_folded(self.conv0, True, dev), _folded(self.conv1, True, dev),
+                                                               _folded(self.conv2, self.finalRelu, dev)]):
             rows = layer(rows)                                                             # :198-205
         feat = group_max(rows.view(B * S, self.K, -1)).view(B, S, -1)                      # :207
         return new_xyz.permute(0, 2, 1), feat.permute(0, 2, 1)                             # :209-211
@@ -143,15 +159,9 @@ class LinearStack(nn.Sequential):
 
     def forward(self, x):
         x = _f32c(x, "inv_pool")
-        if self._layers is None or self._layers[0] != x.device:
-            mods, layers = list(self), []
-            for i, m in enumerate(mods):
-                if isinstance(m, nn.Linear):
-                    layers.append(_folded(m, i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU), x.device))
-            object.__setattr__(self, "_layers", (x.device, layers))
         lead = x.shape[:-1]
         rows = x.reshape(-1, x.shape[-1]).contiguous()
-        for layer in self._layers[1]:
+        for layer in _lazy_layers(self, x.device, lambda dev: _folded_sequence(list(self), dev)):
             rows = layer(rows)
         return rows.view(*lead, -1)
 
@@ -181,6 +191,38 @@ def _pack(fn_name, size, tensors, ints):
     return blob
 
 
+def _pack_on_device(fn_name, size, src, ints=()):
+    """A blob of bf16x3 planes built by a kernel from the packed fp32 blob ``src`` (csrc/pack.hip)."""
+    blob = torch.empty(size, device=src.device, dtype=torch.float32)
+    _lib.call(fn_name, src.data_ptr(), *ints, blob.data_ptr(), _stream())
+    return blob
+
+
+# The blobs derived from the packed pair (enc, dec) of an AE: name -> builder(ae, lib, enc, dec).  The bf16x3 planes come from the fp32
+# blobs on the device, the f16x2 ones are packed on the host from the weights (csrc/pack_h2.hip) and uploaded.
+_DERIVED_BLOBS = {
+    "sa_b3": lambda ae, lib, enc, dec: _pack_on_device("pccx_pack_sa_b3", lib.pccx_sa_b3_blob_floats(), enc),
+    "pn_b3": lambda ae, lib, enc, dec: _pack_on_device("pccx_pack_pn_b3", lib.pccx_pn_b3_blob_floats(), enc),
+    "dec_b3": lambda ae, lib, enc, dec: _pack_on_device("pccx_pack_ae_decoder_b3", lib.pccx_dec_b3_blob_floats(ae.k), dec, (ae.k,)),
+    "enc_h2": lambda ae, lib, enc, dec: _pack("pccx_pack_ae_encoder_h2", lib.pccx_ae_encoder_h2_blob_floats(), ae._enc_tensors(),
+                                              [ae.d]).to(enc.device),
+    "dec_h2": lambda ae, lib, enc, dec: _pack("pccx_pack_ae_decoder_h2", lib.pccx_ae_decoder_h2_blob_floats(ae.k), ae._dec_tensors(),
+                                              [ae.k, ae.d]).to(enc.device),
+}
+# The fused encoders: mode -> (entry point taking the in-patch neighbour tables, its workspace size function, derived blobs after enc_blob,
+# whether it takes the list of distinct patches)
+_FUSED_ENCODERS = {
+    "f16x2": ("pccx_ae_encode_h2_tables_list", "pccx_ae_encode_h2_workspace_bytes", ("enc_h2",), True),
+    "bf16x3": ("pccx_ae_encode_b3_tables", "pccx_ae_encode_b3_workspace_bytes", ("sa_b3", "pn_b3"), False),
+}
+# The decoders: mode -> (entry point, workspace size function, tag of the persistent workspace, derived blob after dec_blob)
+_DECODERS = {
+    "f32": ("pccx_ae_decode", "pccx_ae_decode_workspace_floats", "dec_h2", None),
+    "bf16x3": ("pccx_ae_decode_b3", "pccx_ae_decode_b3_workspace_floats", "dec_h2_b3", "dec_b3"),
+    "f16x2": ("pccx_ae_decode_h2_list", "pccx_ae_decode_h2_workspace_floats", "dec_h2_h2", "dec_h2"),
+}
+
+
 class AE(nn.Module):
     """AE.AE (AE.py:12-55): SetAbstraction + PointNet encoder, Linear + MLP decoder."""
 
@@ -201,6 +243,7 @@ class AE(nn.Module):
         self.inv_mlp = MLP(d + 128, [128, 64, 32, 3], [True, True, True, False])
         self.K, self.k, self.d, self.L = K, k, d, L
         self._enc_blob = self._dec_blob = None
+        self._derived_blobs = {}
         self.sa._own(self._sa_call)
         self.pn._own(self._pn_call)
 
@@ -234,42 +277,21 @@ class AE(nn.Module):
     def load_state_dict(self, *a, **k):
         r = super().load_state_dict(*a, **k)
         self._enc_blob = self._dec_blob = None
+        self._derived_blobs.clear()
         return r
 
     def pack(self, device="cuda"):
         """Build the MFMA fragment blobs (C ABI pccx_pack_*) and upload them."""
-        sd = self.state_dict()
-        w = lambda key: sd[key].reshape(sd[key].shape[0], -1)
         lib = _lib.load()
+        tensors, d = self._enc_tensors(), self.d
         if not self.fused_d:
             # only the SetAbstraction part of the encoder blob is used (ae.sa does not depend on --d): pack it with a 16-wide stand-in
             # for PointNet's last layer; PointNet and the decoder run through the generic layers (their own lazily packed weights)
-            pad_w, pad_b = torch.zeros(16, 512), torch.zeros(16)
-            enc = _pack("pccx_pack_ae_encoder", lib.pccx_ae_encoder_blob_floats(),
-                        [w("sa.conv0.weight"), sd["sa.conv0.bias"], w("sa.conv1.weight"), sd["sa.conv1.bias"],
-                         w("sa.conv2.weight"), sd["sa.conv2.bias"],
-                         w("pn.mlp_Modules.0.0.weight"), sd["pn.mlp_Modules.0.0.bias"],
-                         w("pn.mlp_Modules.1.0.weight"), sd["pn.mlp_Modules.1.0.bias"],
-                         w("pn.mlp_Modules.2.0.weight"), sd["pn.mlp_Modules.2.0.bias"], pad_w, pad_b], [16])
-            self._enc_blob, self._dec_blob = enc.to(device), None
-            self._dec_b3 = self._sa_b3 = self._pn_b3 = self._enc_h2 = self._dec_h2 = None
-            return self
-        enc = _pack("pccx_pack_ae_encoder", lib.pccx_ae_encoder_blob_floats(),
-                    [w("sa.conv0.weight"), sd["sa.conv0.bias"], w("sa.conv1.weight"), sd["sa.conv1.bias"],
-                     w("sa.conv2.weight"), sd["sa.conv2.bias"],
-                     w("pn.mlp_Modules.0.0.weight"), sd["pn.mlp_Modules.0.0.bias"],
-                     w("pn.mlp_Modules.1.0.weight"), sd["pn.mlp_Modules.1.0.bias"],
-                     w("pn.mlp_Modules.2.0.weight"), sd["pn.mlp_Modules.2.0.bias"],
-                     w("pn.mlp_Modules.3.0.weight"), sd["pn.mlp_Modules.3.0.bias"]], [self.d])
-        dec = _pack("pccx_pack_ae_decoder", lib.pccx_ae_decoder_blob_floats(self.k),
-                    [sd["inv_pool.0.weight"], sd["inv_pool.0.bias"], sd["inv_pool.2.weight"], sd["inv_pool.2.bias"],
-                     sd["inv_pool.4.weight"], sd["inv_pool.4.bias"],
-                     w("inv_mlp.mlp_Modules.0.0.weight"), sd["inv_mlp.mlp_Modules.0.0.bias"],
-                     w("inv_mlp.mlp_Modules.1.0.weight"), sd["inv_mlp.mlp_Modules.1.0.bias"],
-                     w("inv_mlp.mlp_Modules.2.0.weight"), sd["inv_mlp.mlp_Modules.2.0.bias"],
-                     w("inv_mlp.mlp_Modules.3.0.weight"), sd["inv_mlp.mlp_Modules.3.0.bias"]], [self.k, self.d])
-        self._enc_blob, self._dec_blob = enc.to(device), dec.to(device)
-        self._dec_b3 = self._sa_b3 = self._pn_b3 = self._enc_h2 = self._dec_h2 = None
+            tensors, d = tensors[:12] + [torch.zeros(16, 512), torch.zeros(16)], 16
+        self._enc_blob = _pack("pccx_pack_ae_encoder", lib.pccx_ae_encoder_blob_floats(), tensors, [d]).to(device)
+        self._dec_blob = _pack("pccx_pack_ae_decoder", lib.pccx_ae_decoder_blob_floats(self.k), self._dec_tensors(),
+                               [self.k, self.d]).to(device) if self.fused_d else None
+        self._derived_blobs.clear()
         return self
 
     def _enc_tensors(self):
@@ -292,64 +314,58 @@ class AE(nn.Module):
                 w("inv_mlp.mlp_Modules.2.0.weight"), sd["inv_mlp.mlp_Modules.2.0.bias"],
                 w("inv_mlp.mlp_Modules.3.0.weight"), sd["inv_mlp.mlp_Modules.3.0.bias"]]
 
-    def _enc_h2_blob(self, device):
-        """f16x2 operand planes, scaled biases and layer scales of the encoder (csrc/pack_h2.hip), packed on the host."""
-        enc, _ = self._blobs(device)
-        if getattr(self, "_enc_h2", None) is None or self._enc_h2.device != enc.device:
-            self._enc_h2 = _pack("pccx_pack_ae_encoder_h2", _lib.load().pccx_ae_encoder_h2_blob_floats(), self._enc_tensors(),
-                                 [self.d]).to(enc.device)
-        return self._enc_h2
-
-    def _dec_h2_blob(self, device):
-        _, dec = self._blobs(device)
-        if getattr(self, "_dec_h2", None) is None or self._dec_h2.device != dec.device:
-            self._dec_h2 = _pack("pccx_pack_ae_decoder_h2", _lib.load().pccx_ae_decoder_h2_blob_floats(self.k), self._dec_tensors(),
-                                 [self.k, self.d]).to(dec.device)
-        return self._dec_h2
-
     def _blobs(self, device):
         if self._enc_blob is None or self._enc_blob.device != torch.device(device):
             self.pack(device)
         return self._enc_blob, self._dec_blob
 
+    def _derived(self, name, device):
+        """One of the five blobs made from the packed weights, built on first use on a device; pack() and load_state_dict() drop them."""
+        enc, dec = self._blobs(device)                    # first: packing for another device empties the cache
+        blob = self._derived_blobs.get(name)
+        if blob is None or blob.device != enc.device:
+            blob = self._derived_blobs[name] = _DERIVED_BLOBS[name](self, _lib.load(), enc, dec)
+        return blob
+
     def _sa_b3_blob(self, device):
-        """bf16x3 planes of the SetAbstraction conv1 / conv2 weights, built on the device."""
-        enc, _ = self._blobs(device)
-        if getattr(self, "_sa_b3", None) is None or self._sa_b3.device != enc.device:
-            self._sa_b3 = torch.empty(_lib.load().pccx_sa_b3_blob_floats(), device=enc.device, dtype=torch.float32)
-            _lib.call("pccx_pack_sa_b3", enc.data_ptr(), self._sa_b3.data_ptr(), _stream())
-        return self._sa_b3
+        """bf16x3 planes of the SetAbstraction conv1 / conv2 weights."""
+        return self._derived("sa_b3", device)
 
     def _pn_b3_blob(self, device):
-        """bf16x3 planes of the PointNet weight stream, built on the device."""
-        enc, _ = self._blobs(device)
-        if getattr(self, "_pn_b3", None) is None or self._pn_b3.device != enc.device:
-            self._pn_b3 = torch.empty(_lib.load().pccx_pn_b3_blob_floats(), device=enc.device, dtype=torch.float32)
-            _lib.call("pccx_pack_pn_b3", enc.data_ptr(), self._pn_b3.data_ptr(), _stream())
-        return self._pn_b3
+        """bf16x3 planes of the PointNet weight stream."""
+        return self._derived("pn_b3", device)
+
+    def _dec_b3_blob(self, device):
+        """bf16x3 planes of the decoder's big Linear."""
+        return self._derived("dec_b3", device)
+
+    def _enc_h2_blob(self, device):
+        """f16x2 operand planes, scaled biases and layer scales of the encoder."""
+        return self._derived("enc_h2", device)
+
+    def _dec_h2_blob(self, device):
+        return self._derived("dec_h2", device)
 
     def _launch_sa(self, x, feat, matmul):
         P, K, _ = x.shape
         enc, _ = self._blobs(x.device)
-        if matmul in ("bf16x3", "f16x2"):                 # f16x2 exists for the fused transforms only: the module alone runs bf16x3
+        check_matmul("sa_matmul", matmul)
+        if matmul == "f32":
+            _lib.call("pccx_sa_forward", x.data_ptr(), P, K, enc.data_ptr(), feat.data_ptr(), _stream())
+        else:                                             # f16x2 exists for the fused transforms only: the module alone runs bf16x3
             _lib.call("pccx_sa_forward_b3", x.data_ptr(), P, K, enc.data_ptr(), self._sa_b3_blob(x.device).data_ptr(),
                       feat.data_ptr(), _stream())
-        elif matmul == "f32":
-            _lib.call("pccx_sa_forward", x.data_ptr(), P, K, enc.data_ptr(), feat.data_ptr(), _stream())
-        else:
-            raise ValueError(f"sa_matmul={matmul!r}: expected 'f32', 'bf16x3' or 'f16x2'")
 
     def _launch_pn(self, x, feat, outs, matmul):
         P, K, _ = x.shape
         enc, _ = self._blobs(x.device)
-        if matmul in ("bf16x3", "f16x2"):
-            _lib.call("pccx_pn_forward_b3", x.data_ptr(), feat.data_ptr(), P, K, enc.data_ptr(), self._pn_b3_blob(x.device).data_ptr(),
-                      self.d, self.L, outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), _stream())
-        elif matmul == "f32":
+        check_matmul("pn_matmul", matmul)
+        if matmul == "f32":
             _lib.call("pccx_pn_forward", x.data_ptr(), feat.data_ptr(), P, K, enc.data_ptr(), self.d, self.L,
                       outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), _stream())
         else:
-            raise ValueError(f"pn_matmul={matmul!r}: expected 'f32', 'bf16x3' or 'f16x2'")
+            _lib.call("pccx_pn_forward_b3", x.data_ptr(), feat.data_ptr(), P, K, enc.data_ptr(), self._pn_b3_blob(x.device).data_ptr(),
+                      self.d, self.L, outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), _stream())
 
     def encode(self, patches, sa_matmul=None, pn_matmul=None, fused=True, groups=None):
         """patches (BS,K,3), centred and scaled -> (latent_raw, latent, latent_quantized), each (BS,d).
@@ -378,36 +394,29 @@ class AE(nn.Module):
             return self.encode_generic(x)
         outs = [torch.empty(P, self.d, device=x.device, dtype=torch.float32) for _ in range(3)]
         sa_matmul, pn_matmul = sa_matmul or _pccx_default_matmul(), pn_matmul or _pccx_default_matmul()
-        if fused and sa_matmul == pn_matmul == "f16x2" and _lib.load().pccx_ae_encode_h2_fused_ok(K):
-            # the fused kernel on f16x2 operands (csrc/encoder_fused_h2.hip): two fp16 pieces per operand, three MFMA passes
+        lib = _lib.load()
+        # one kernel, the (P,128,K) feature map never leaves the CU: on f16x2 operands (csrc/encoder_fused_h2.hip) when both modules ask
+        # for them; every other f16x2 request runs bf16x3, fused (csrc/encoder_fused.hip) when both modules then agree on it
+        if fused and sa_matmul == pn_matmul == "f16x2" and lib.pccx_ae_encode_h2_fused_ok(K):
+            mode = "f16x2"
+        else:
+            sa_matmul, pn_matmul = ("bf16x3" if m == "f16x2" else m for m in (sa_matmul, pn_matmul))
+            mode = "bf16x3" if fused and sa_matmul == pn_matmul == "bf16x3" and lib.pccx_ae_encode_b3_fused_ok(K) else None
+        if mode is not None:
+            tables_fn, ws_bytes, blobs, takes_lists = _FUSED_ENCODERS[mode]
             enc, _ = self._blobs(x.device)
-            nbytes = _lib.load().pccx_ae_encode_h2_workspace_bytes(P, K)
-            ws = workspace("patch_knn16", (nbytes + 3) // 4, x.device)
-            # the two launches of pccx_ae_encode_h2_ws as two calls, so that a stage timer sees each kernel on its own
-            uq, nu = (groups.uniq.data_ptr(), groups.n_uniq.data_ptr()) if groups is not None else (None, None)
+            # the in-patch 16-NN tables come from a kernel of their own (csrc/patch_knn.hip) through a persistent workspace, 4 KB per
+            # 256-point patch: two calls, so that a stage timer sees each kernel on its own
+            ws = workspace("patch_knn16", (getattr(lib, ws_bytes)(P, K) + 3) // 4, x.device)
+            lists = (groups.uniq.data_ptr(), groups.n_uniq.data_ptr()) if takes_lists and groups is not None else (None, None)
             with stage("patch_knn16"):
-                _lib.call("pccx_patch_knn16_list", x.data_ptr(), P, K, ws.data_ptr(), uq, nu, _stream())
+                _lib.call("pccx_patch_knn16_list", x.data_ptr(), P, K, ws.data_ptr(), *lists, _stream())
             with stage("sa_pn_forward"):
-                _lib.call("pccx_ae_encode_h2_tables_list", x.data_ptr(), P, K, enc.data_ptr(), self._enc_h2_blob(x.device).data_ptr(), self.d, self.L,
-                          outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), ws.data_ptr(), uq, nu, _stream())
+                _lib.call(tables_fn, x.data_ptr(), P, K, enc.data_ptr(), *[self._derived(b, x.device).data_ptr() for b in blobs],
+                          self.d, self.L, outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), ws.data_ptr(),
+                          *(lists if takes_lists else ()), _stream())
             return tuple(outs)
-        if sa_matmul == "f16x2" or pn_matmul == "f16x2":      # K beyond the fused kernel, or fused=False: the bf16x3 kernels
-            sa_matmul = "bf16x3" if sa_matmul == "f16x2" else sa_matmul
-            pn_matmul = "bf16x3" if pn_matmul == "f16x2" else pn_matmul
-        if fused and sa_matmul == pn_matmul == "bf16x3" and _lib.load().pccx_ae_encode_b3_fused_ok(K):
-            # one kernel, the (P,128,K) feature map never leaves the CU (csrc/encoder_fused.hip)
-            # (csrc/encoder_fused.hip); the in-patch 16-NN tables come from a kernel of their own (csrc/patch_knn.hip) through
-            # a persistent workspace: 4 KB per 256-point patch
-            enc, _ = self._blobs(x.device)
-            nbytes = _lib.load().pccx_ae_encode_b3_workspace_bytes(P, K)
-            ws = workspace("patch_knn16", (nbytes + 3) // 4, x.device)
-            with stage("patch_knn16"):
-                _lib.call("pccx_patch_knn16", x.data_ptr(), P, K, ws.data_ptr(), _stream())
-            with stage("sa_pn_forward"):
-                _lib.call("pccx_ae_encode_b3_tables", x.data_ptr(), P, K, enc.data_ptr(), self._sa_b3_blob(x.device).data_ptr(),
-                          self._pn_b3_blob(x.device).data_ptr(), self.d, self.L, outs[0].data_ptr(), outs[1].data_ptr(),
-                          outs[2].data_ptr(), ws.data_ptr(), _stream())
-            return tuple(outs)
+        # the two-kernel path, the feature map through HBM
         ws = workspace("sa_feat", P * K * 128, x.device)
         with stage("sa_forward"):
             self._launch_sa(x, ws, sa_matmul)
@@ -440,14 +449,6 @@ class AE(nn.Module):
             outs.append(self.inv_mlp(mlp_in).transpose(2, 1).contiguous())                         # :101-102
         return torch.cat(outs) if outs else torch.empty(0, self.k, 3, device=q.device)
 
-    def _b3_blob(self, device):
-        """bf16x3 planes of the decoder's big Linear, built on the device from the packed fp32 blob."""
-        _, dec = self._blobs(device)
-        if getattr(self, "_dec_b3", None) is None or self._dec_b3.device != dec.device:
-            self._dec_b3 = torch.empty(_lib.load().pccx_dec_b3_blob_floats(self.k), device=dec.device, dtype=torch.float32)
-            _lib.call("pccx_pack_ae_decoder_b3", dec.data_ptr(), self.k, self._dec_b3.data_ptr(), _stream())
-        return self._dec_b3
-
     def decode(self, latent_q, centres=None, center=None, longest=None, S=None, scale=None, margin=0.01, matmul=None, group=False):
         """latent_q (BS,d) -> decoded patches (BS,k,3) (AE.py:48-53).  With centres/center/longest/S/scale
         it returns instead the reassembled, denormalised cloud (B,S*k,3) of decompress.py:104-116.
@@ -458,49 +459,40 @@ class AE(nn.Module):
         matmul = matmul or _pccx_default_matmul()
         q = _f32c(latent_q, "AE.decode")
         P = q.shape[0]
+        reassemble = centres is not None
+        if not (self.fused_d or reassemble):
+            return self.decode_generic(q)
+        if reassemble:
+            B = P // S
+            centres = _f32c(centres.reshape(P, 3), "AE.decode.centres")
+            center = _f32c(center.reshape(B, 3), "AE.decode.center")
+            longest = _f32c(longest.reshape(B), "AE.decode.longest")
+            form = (float(scale), centres.data_ptr(), center.data_ptr(), longest.data_ptr(), int(S), float(margin))
+            result = torch.empty(B, S * self.k, 3, device=q.device, dtype=torch.float32)
+        else:
+            form = (0.0, None, None, None, 1, float(margin))
+            result = torch.empty(P, self.k, 3, device=q.device, dtype=torch.float32)
         if not self.fused_d:
             raw = self.decode_generic(q)
-            if centres is None:
-                return raw
-            B = P // S
-            pc = torch.empty(B, S * self.k, 3, device=q.device, dtype=torch.float32)
-            _lib.call("pccx_reassemble", raw.data_ptr(), P, self.k, float(scale), _f32c(centres.reshape(P, 3), "AE.decode.centres").data_ptr(),
-                      _f32c(center.reshape(B, 3), "AE.decode.center").data_ptr(), _f32c(longest.reshape(B), "AE.decode.longest").data_ptr(),
-                      int(S), float(margin), pc.data_ptr(), _stream())
-            return pc
+            _lib.call("pccx_reassemble", raw.data_ptr(), P, self.k, *form, result.data_ptr(), _stream())
+            return result
+        check_matmul("matmul", matmul)
+        fn, ws_floats, ws_tag, blob = _DECODERS[matmul]
         _, dec = self._blobs(q.device)
-        if matmul == "bf16x3":
-            fn, extra = "pccx_ae_decode_b3", (self._b3_blob(q.device).data_ptr(),)
-            ws = workspace("dec_h2_b3", _lib.load().pccx_ae_decode_b3_workspace_floats(P), q.device)
-        elif matmul == "f16x2":
-            fn, extra = "pccx_ae_decode_h2", (self._dec_h2_blob(q.device).data_ptr(),)
-            ws = workspace("dec_h2_h2", _lib.load().pccx_ae_decode_h2_workspace_floats(P), q.device)
-        elif matmul == "f32":
-            fn, extra = "pccx_ae_decode", ()
-            ws = workspace("dec_h2", _lib.load().pccx_ae_decode_workspace_floats(P), q.device)
-        else:
-            raise ValueError(f"matmul={matmul!r}: expected 'f32', 'bf16x3' or 'f16x2'")
-        if centres is None:
-            out = torch.empty(P, self.k, 3, device=q.device, dtype=torch.float32)
-            _lib.call(fn, q.data_ptr(), P, self.d, self.k, dec.data_ptr(), *extra, ws.data_ptr(), out.data_ptr(),
-                      0.0, None, None, None, 1, float(margin), None, _stream())
-            return out
-        B = P // S
-        centres = _f32c(centres.reshape(P, 3), "AE.decode.centres")
-        center = _f32c(center.reshape(B, 3), "AE.decode.center")
-        longest = _f32c(longest.reshape(B), "AE.decode.longest")
-        pc = torch.empty(B, S * self.k, 3, device=q.device, dtype=torch.float32)
-        if group and matmul == "f16x2":
-            from .ops import patch_groups, replicate_rows
-            groups = patch_groups(centres.view(B, S, 3), q.view(B, S, self.d))
-            _lib.call("pccx_ae_decode_h2_list", q.data_ptr(), P, self.d, self.k, dec.data_ptr(), *extra, ws.data_ptr(), None, float(scale),
-                      centres.data_ptr(), center.data_ptr(), longest.data_ptr(), int(S), float(margin), pc.data_ptr(),
-                      groups.uniq.data_ptr(), groups.n_uniq.data_ptr(), _stream())
-            replicate_rows(groups, pc)
-            return pc
-        _lib.call(fn, q.data_ptr(), P, self.d, self.k, dec.data_ptr(), *extra, ws.data_ptr(), None, float(scale),
-                  centres.data_ptr(), center.data_ptr(), longest.data_ptr(), int(S), float(margin), pc.data_ptr(), _stream())
-        return pc
+        extra = (self._derived(blob, q.device).data_ptr(),) if blob else ()
+        ws = workspace(ws_tag, getattr(_lib.load(), ws_floats)(P), q.device)
+        groups, lists = None, ()
+        if matmul == "f16x2":
+            if group and reassemble:
+                from .ops import patch_groups, replicate_rows
+                groups = patch_groups(centres.view(B, S, 3), q.view(B, S, self.d))
+            lists = (groups.uniq.data_ptr(), groups.n_uniq.data_ptr()) if groups is not None else (None, None)
+        # patches_out, then the reassembling arguments, then pc_out: one of the two destinations is null
+        dest = (None, *form, result.data_ptr()) if reassemble else (result.data_ptr(), *form, None)
+        _lib.call(fn, q.data_ptr(), P, self.d, self.k, dec.data_ptr(), *extra, ws.data_ptr(), *dest, *lists, _stream())
+        if groups is not None:
+            replicate_rows(groups, result)
+        return result
 
     def forward(self, xyz):
         """AE.AE.forward (AE.py:34-55), inference: xyz (BS,K,3) -> (new_xyz (BS,k,3), latent, latent_quantized)."""
@@ -510,6 +502,8 @@ class AE(nn.Module):
 
 class ConditionalProbabilityModel(nn.Module):
     """AE.ConditionalProbabilityModel (AE.py:87-123)."""
+
+    _layers = None                # generic path: model_mlp's packed layers (_lazy_layers)
 
     def __init__(self, L, d):
         super().__init__()
@@ -521,7 +515,7 @@ class ConditionalProbabilityModel(nn.Module):
 
     def load_state_dict(self, *a, **k):
         r = super().load_state_dict(*a, **k)
-        self._blob = None
+        self._blob = self._layers = self.model_pn._layers = None      # model_pn's weights came in through this call too
         return r
 
     def fused_ok(self, S=16):
@@ -530,8 +524,7 @@ class ConditionalProbabilityModel(nn.Module):
 
     def pack(self, device="cuda"):
         if not self.fused_ok():
-            self._blob = None
-            self._generic = None
+            self._blob = self._layers = None
             return self
         sd = self.state_dict()
         w = lambda key: sd[key].reshape(sd[key].shape[0], -1)
@@ -552,45 +545,30 @@ class ConditionalProbabilityModel(nn.Module):
             return self._run_generic(x, want)
         if self._blob is None or self._blob.device != x.device:
             self.pack(x.device)
-        r = {}
-        if "pmf" in want:
-            r["pmf"] = torch.empty(B, S, self.d, self.L, device=x.device, dtype=torch.float32)
-        if "cdf" in want:
-            r["cdf"] = torch.empty(B, S, self.d, self.L + 1, device=x.device, dtype=torch.float32)
-        if "cdf_int" in want:
-            r["cdf_int"] = torch.empty(B, S, self.d, self.L + 1, device=x.device, dtype=torch.int32)
-        p = lambda k: r[k].data_ptr() if k in r else None
-        _lib.call("pccx_prob_forward", x.data_ptr(), B, S, self.d, self.L, self._blob.data_ptr(), p("pmf"), p("cdf"),
-                  p("cdf_int"), _stream())
+        r, ptrs = self._outputs(want, B, S, x.device)
+        _lib.call("pccx_prob_forward", x.data_ptr(), B, S, self.d, self.L, self._blob.data_ptr(), *ptrs, _stream())
         return r
+
+    def _outputs(self, want, B, S, device):
+        """The wanted ones of pmf / cdf / cdf_int, and the three pointers the kernels take (null for an output not wanted)."""
+        kinds = {"pmf": (self.L, torch.float32), "cdf": (self.L + 1, torch.float32), "cdf_int": (self.L + 1, torch.int32)}
+        r = {name: torch.empty(B, S, self.d, n, device=device, dtype=dt) for name, (n, dt) in kinds.items() if name in want}
+        return r, [r[name].data_ptr() if name in r else None for name in kinds]
 
     def _run_generic(self, x, want):
         """AE.ConditionalProbabilityModel.forward (AE.py:107-123) + pmf_to_cdf + torchac's integer CDF through the generic layers,
         for --d / --L / S outside the fused kernel's shapes: model_pn (generic PointNet), the three 1x1 convolutions as generic
         layers on the (B*S, 259) rows, then pccx_softmax_cdf."""
-        from .families import FoldedLinear
         B, S, _ = x.shape
-        if getattr(self, "_generic", None) is None or self._generic[0] != x.device:
-            mods = list(self.model_mlp)
-            layers = [FoldedLinear(m.weight, m.bias, i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU), None, x.device)
-                      for i, m in enumerate(mods) if isinstance(m, nn.Conv2d)]
-            object.__setattr__(self, "_generic", (x.device, layers))
         feature = self.model_pn(x.transpose(1, 2).contiguous())                                    # AE.py:111-112  (B, 256)
         rows = torch.cat((x, feature[:, None, :].expand(B, S, feature.shape[1])), dim=2).reshape(B * S, -1)   # :113-115
         buf = torch.zeros(B * S, (rows.shape[1] + 3) // 4 * 4, device=x.device, dtype=torch.float32)           # 16-byte rows
         buf[:, :rows.shape[1]] = rows
         rows = buf[:, :rows.shape[1]]
-        for layer in self._generic[1]:
+        for layer in _lazy_layers(self, x.device, lambda dev: _folded_sequence(list(self.model_mlp), dev)):
             rows = layer(rows)                                                                     # :117  (B*S, d*L)
-        r = {}
-        if "pmf" in want:
-            r["pmf"] = torch.empty(B, S, self.d, self.L, device=x.device, dtype=torch.float32)
-        if "cdf" in want:
-            r["cdf"] = torch.empty(B, S, self.d, self.L + 1, device=x.device, dtype=torch.float32)
-        if "cdf_int" in want:
-            r["cdf_int"] = torch.empty(B, S, self.d, self.L + 1, device=x.device, dtype=torch.int32)
-        p = lambda k_: r[k_].data_ptr() if k_ in r else None
-        _lib.call("pccx_softmax_cdf", rows.contiguous().data_ptr(), B * S * self.d, self.L, p("pmf"), p("cdf"), p("cdf_int"), _stream())   # :119-123
+        r, ptrs = self._outputs(want, B, S, x.device)
+        _lib.call("pccx_softmax_cdf", rows.contiguous().data_ptr(), B * S * self.d, self.L, *ptrs, _stream())   # :119-123
         return r
 
     def forward(self, sampled_xyz):

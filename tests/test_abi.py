@@ -33,6 +33,25 @@ def test_python_binding_covers_header():
     assert sorted(_lib.declared_symbols()) == _declared()
 
 
+def test_derived_signatures():
+    """The ctypes table is parsed from include/pccx.h: hand-written rows that between them hold every kind of type the header uses."""
+    C = ctypes
+    P, i, i64, f, dbl, s = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_char_p
+    sig = _lib.signatures()
+    assert sig["pccx_last_error"] == (s, [])
+    assert sig["pccx_sort_keys_workspace_bytes"] == (C.c_size_t, [i64])
+    assert sig["pccx_normalize"] == (i, [P, i, i, dbl, P, P, P, P])
+    assert sig["pccx_write_streams_host"] == (i, [P, i, i, i, s, s, P, i])
+    assert sig["pccx_replicate_rows"] == (i, [P, i64, i, P, P, P, P])
+    assert sig["pccx_ae_decode_h2_list"] == (i, [P, i, i, i, P, P, P, P, f, P, P, P, i, dbl, P, P, P, P])
+    assert _lib.parse_header("/* PCCX_API int pccx_a(int); */\nPCCX_API size_t pccx_b(void); // PCCX_API int pccx_c(int);\n") == {
+        "pccx_b": (C.c_size_t, [])}
+    for bad in ("PCCX_API int pccx_f(const float *x,\n                    uint8_t flag);", "PCCX_API long pccx_f(int n);",
+                "PCCX_API int pccx_f(unsigned int n);", "PCCX_API int pccx_f(int (*callback)(int));"):
+        with pytest.raises(_lib.PccxError, match="pccx_f"):
+            _lib.parse_header(bad)
+
+
 def test_ops_fail_loudly_without_gpu_tensor():
     import torch
     from pccx import ops

@@ -384,6 +384,50 @@ def _seeded_ae(Kx, kx, bias_gain=1.0):
     return ae.pack("cuda")
 
 
+def test_load_state_dict_leaves_no_stale_blob(matmul_mode):
+    """New weights loaded into a packed AE that has already run: every blob made from the old ones (the packed fp32 pair and the five
+    derived from it) is rebuilt, so the object computes bit for bit what a fresh AE with those weights does.  P = 5 is no multiple of
+    the decoder's 16-patch tile, K = 32 the smallest K with two PointNet tiles."""
+    Kx, kx, dx, P = 32, 16, 4, 5
+    x = torch.from_numpy(np.random.default_rng(3).standard_normal((P, Kx, 3)).astype(np.float32)).cuda()
+
+    def run(ae):
+        raw, lat, q = ae.encode(x, sa_matmul=matmul_mode, pn_matmul=matmul_mode)
+        return raw, lat, q, ae.decode(q, matmul=matmul_mode)
+
+    ae = models.AE(Kx, kx, dx, L)
+    ae.load_state_dict(ref_model.seeded_state_dict(ae, synth.AE_SEED, last_gain=synth.AE_LAST_GAIN))
+    first = run(ae)
+    sd2 = ref_model.seeded_state_dict(ae, synth.AE_SEED + 10, last_gain=synth.AE_LAST_GAIN)
+    ae.load_state_dict(sd2)
+    second = run(ae)
+    fresh = models.AE(Kx, kx, dx, L)
+    fresh.load_state_dict(sd2)
+    for got, want in zip(second, run(fresh)):
+        assert torch.equal(got, want)
+    raw1, lat1, _, rec1 = first                           # (the 20 symbols alone could agree by chance)
+    assert not torch.equal(second[0], raw1) and not torch.equal(second[1], lat1) and not torch.equal(second[3], rec1)
+
+
+def test_prob_model_reload_drops_the_generic_layers():
+    """The same guard for the probability model outside the fused kernel's shapes (d * L = 144 > 128): its generic layers, model_pn's
+    and model_mlp's, are packed lazily on first use, and load_state_dict drops them."""
+    Lx, dx = 9, 16
+    x = torch.from_numpy(np.random.default_rng(4).random((2, 16, 3)).astype(np.float32)).cuda()
+    prob = models.ConditionalProbabilityModel(Lx, dx)
+    assert not prob.fused_ok(16)
+    prob.load_state_dict(ref_model.seeded_state_dict(prob, synth.PROB_SEED, gain=synth.PROB_GAIN))
+    first = prob.run(x, ("pmf", "cdf_int"))
+    sd2 = ref_model.seeded_state_dict(prob, synth.PROB_SEED + 10, gain=synth.PROB_GAIN)
+    prob.load_state_dict(sd2)
+    second = prob.run(x, ("pmf", "cdf_int"))
+    fresh = models.ConditionalProbabilityModel(Lx, dx)
+    fresh.load_state_dict(sd2)
+    want = fresh.run(x, ("pmf", "cdf_int"))
+    assert torch.equal(second["pmf"], want["pmf"]) and torch.equal(second["cdf_int"], want["cdf_int"])
+    assert not torch.equal(second["pmf"], first["pmf"])
+
+
 @pytest.mark.parametrize("Kx,kx,P", [(256, 128, 37), (64, 32, 5), (512, 256, 3), (16, 8, 2), (48, 24, 3)])
 def test_f16x2_matches_fp32_path(Kx, kx, P):
     """The f16x2 kernels (csrc/encoder_fused_h2.hip, decoder_h2.hip: two scaled fp16 pieces per operand, three MFMA passes per

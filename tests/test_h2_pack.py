@@ -167,6 +167,23 @@ def test_pack_rejects_non_finite_weights():
         models._pack("pccx_pack_ae_encoder_h2", _lib.load().pccx_ae_encoder_h2_blob_floats(), ae._enc_tensors(), [d])
 
 
+def test_derived_blobs_are_cached_and_dropped_by_load_state_dict():
+    """The f16x2 blobs are built once per packing and never outlive the weights they were packed from."""
+    ae = models.AE(32, 16, 4, 7)
+    sd = ref_model.seeded_state_dict(ae, synth.AE_SEED, last_gain=synth.AE_LAST_GAIN)
+    ae.load_state_dict(sd)
+    ae.pack("cpu")
+    for blob, key in ((ae._enc_h2_blob, "pn.mlp_Modules.1.0.weight"), (ae._dec_h2_blob, "inv_mlp.mlp_Modules.1.0.weight")):
+        first = blob("cpu")
+        assert blob("cpu") is first
+        sd = {n: v.clone() for n, v in sd.items()}
+        sd[key][3, 5] += 0.25
+        ae.load_state_dict(sd)
+        assert ae._derived_blobs == {}
+        second = blob("cpu")
+        assert second is not first and second.shape == first.shape and not torch.equal(second, first)
+
+
 def test_two_piece_split_arithmetic_property():
     """The arithmetic behind the mode, in numpy (IEEE binary16, round to nearest even -- what v_cvt_pk_f16_f32 does): for operands
     scaled into fp16's normal range, hi = rn16(x), lo = rn16(x - hi) reproduce x to 2^-22 |x|, the residual x - hi is exact in fp32,
