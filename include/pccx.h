@@ -663,6 +663,52 @@ PCCX_API int pccx_adam_step_dev(float *param, const float *grad, float *exp_avg,
                                 const double *gnorm_sq, float max_norm, const float *hyper, float beta1, float beta2,
                                 float eps, void *stream);
 
+/* ---- 11b. The deterministic mode of the training step (pccx.train.step_scope(deterministic=True)): every accumulation of a
+ *      step in a FIXED order, so that a step is a pure function of its inputs and bit-identical from run to run.  Each entry WRITES its
+ *      result (no cleared buffer is needed, what the output held is ignored) and takes its scratch from the caller; every launch geometry
+ *      is a function of the shapes alone.  Workspaces are plain uninitialised memory of the size the *_workspace_* / *_doubles call names. */
+/* (a) stands in for pccx_linear_dw (also with the roles swapped, pccx/train.py _is_wide): every row slice stores its partial dW tile in
+ * workspace [slices][N][K], a second kernel adds the slices in ascending index.  The workspace is at most max(8 N K, 2 Mi) floats; a
+ * shape that splits into one slice needs none (the size is then 0 and workspace may be NULL). */
+PCCX_API size_t pccx_linear_dw_det_workspace_floats(int64_t M, int N, int K);
+PCCX_API int pccx_linear_dw_det(const float *dZ, const float *X, int64_t M, int N, int K, int ldz, int ldx, float *dW, int flags,
+                                float *workspace, void *stream);
+/* (a) stands in for pccx_linear_skinny_dx: the n-chunks store their partial rows in workspace [chunks][M][K] (16-byte aligned, at most
+ * a quarter of the weight), added in ascending chunk index. */
+PCCX_API size_t pccx_linear_skinny_dx_det_workspace_floats(int M, int N, int K);
+PCCX_API int pccx_linear_skinny_dx_det(const float *dZ, int M, int N, int ldz, const float *W, int K, int flags, float *dX, int ldd,
+                                       float *workspace, void *stream);
+/* (b) stands in for the column reductions inside pccx_bn_relu_train_forward (mode 0: sum z, sum z^2 of A), pccx_bn_relu_train_backward
+ * (mode 1: sum dy (y>0) xhat, sum dy (y>0) with dY = A) and pccx_col_sum_w (mode 2: sum of A), and for the epilogues of
+ * pccx_linear_moments / pccx_linear_bnback, for any C: workgroup w stores its double partials in slot w of `partials`
+ * (pccx_col_reduce_det_doubles(M, C) doubles), one kernel adds the slots in ascending index from +0.  sums (modes 0, 1;
+ * pccx_train_sums_doubles(C) doubles, all written: totals in replica 0, +0 in the others) is what the two BatchNorm entries take with
+ * flags 4 | 8; in mode 2 `sums` is C doubles.  f32_out: the first sum as C floats (the bias gradient).  Either may be NULL, not both. */
+PCCX_API size_t pccx_col_reduce_det_doubles(int64_t M, int C);
+PCCX_API int pccx_col_reduce_det(int mode, const float *A, const float *Y, const float *Z, const float *mean, const float *rstd,
+                                 int64_t M, int C, double *partials, double *sums, float *f32_out, void *stream);
+/* (b) stand in for pccx_smooth_l1 and pccx_sumsq_multi: value[0] / acc[0] WRITTEN as the sum of the workgroups' partials in ascending
+ * workgroup index.  (pccx_rate_from_logits is one thread's loop: it has no order to fix.) */
+PCCX_API size_t pccx_smooth_l1_det_doubles(int64_t n);
+PCCX_API int pccx_smooth_l1_det(const float *a, const float *b, int64_t n, float grad_scale, double *partials, double *value,
+                                float *grad, void *stream);
+PCCX_API size_t pccx_sumsq_multi_det_doubles(int64_t total_blocks);
+PCCX_API int pccx_sumsq_multi_det(const int64_t *table_dev, int ntensors, int64_t total_blocks, double *partials, double *acc,
+                                  void *stream);
+/* (c) stands in for pccx_gather_backward_acc: out (B,N,C) WRITTEN, out[b][n] = the fp32 sum from +0 of vals[b][m] (row stride ldv >= C)
+ * over the m with idx[b][m] == n in ascending m; untouched rows are +0 (np.add.at on float32, bit for bit).  idx (B,Mrows): int64
+ * (idx_is_i32 = 0) or int32 (1), clamped to [0, N-1].  The inverse lists are built on the device, no host read-back; a segment may be
+ * as long as Mrows.  workspace: pccx_scatter_add_ordered_workspace_ints(B, Mrows, N) int32. */
+PCCX_API size_t pccx_scatter_add_ordered_workspace_ints(int B, int Mrows, int N);
+PCCX_API int pccx_scatter_add_ordered(const float *vals, int ldv, const void *idx, int idx_is_i32, int B, int Mrows, int N, int C,
+                                      float *out, int32_t *workspace, void *stream);
+/* (c) stands in for pccx_chamfer_grad_dev_acc: gX / gY WRITTEN; the nearest-neighbour scatter goes through pccx_scatter_add_ordered
+ * (gX[i] = own term - ordered sum over the y that chose x_i). */
+PCCX_API size_t pccx_chamfer_grad_det_workspace_floats(int B, int P, int Q);
+PCCX_API size_t pccx_chamfer_grad_det_workspace_ints(int B, int P, int Q);
+PCCX_API int pccx_chamfer_grad_det(const float *X, int B, int P, const float *Y, int Q, const int32_t *nn_xy, const int32_t *nn_yx,
+                                   const float *grad_out_dev, float *gX, float *gY, float *ws_floats, int32_t *ws_ints, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@ parser.add_argument('--device', default='cuda', help='AE Model Device (cuda)')
 parser.add_argument('--reset', action='store_true', help='Reset training and start from scratch (ignore saved model).')
 parser.add_argument('--autocast', action='store_true', help='bf16 operands on the matrix cores (the reference wraps its CUDA step in autocast, train.py:175).')
 parser.add_argument('--eager', action='store_true', help='launch every kernel of every step from Python instead of replaying the captured step.')
+parser.add_argument('--deterministic', action='store_true', help='every reduction of a step in a fixed order: the same inputs give the same bits, run after run (one GPU).')
 
 
 def latest(folder, prefix):
@@ -85,6 +86,7 @@ def main():
     args.S, args.k = N * args.ALPHA // K, K // args.ALPHA                              # train.py:253
     print(f"Training {args.model} on {args.device}")
     print(f"N={N}, K={K}, S={args.S}, d={args.d}, L={args.L}")
+    print(f"deterministic={args.deterministic}, autocast={args.autocast}, eager={args.eager}")
     os.makedirs(args.model_save_folder, exist_ok=True)
     files = sorted(glob(args.train_glob, recursive=True))
     points = np.stack([plyio.read_point_cloud(f) for f in files]).astype(np.float32)   # pn_kit.read_point_clouds (pn_kit.py:36-42)
@@ -94,7 +96,7 @@ def main():
     prob = models.ConditionalProbabilityModel(args.L, args.d).to(args.device)
     tr = train_ipdae.IpdaeTrainer(ae, prob, N=N, N0=args.N0, ALPHA=args.ALPHA, K=K, lr=args.lr, lamda=args.lamda,
                                   rate_loss_enable_step=args.rate_loss_enable_step, lr_decay=args.lr_decay,
-                                  lr_decay_steps=args.lr_decay_steps, autocast=args.autocast)
+                                  lr_decay_steps=args.lr_decay_steps, autocast=args.autocast, deterministic=args.deterministic)
     if not args.reset:
         tr.global_step = load_checkpoints(tr, args.model_save_folder)                  # :137-144
         print(f"Resuming from step {tr.global_step}")

@@ -1019,3 +1019,70 @@ static int chamfer_grad_launch(const float *X, int B, int P, const float *Y, int
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// The same gradient in the deterministic mode (pccx_chamfer_grad_det stands in for pccx_chamfer_grad_dev_acc): the own-point term of
+// every point is one value, so it has no order; the nearest-neighbour scatter goes through the ordered segmented scatter-add of
+// train.hip (pccx_scatter_add_ordered: ascending source index, from +0).  gX[i] = own_x[i] - S_x[i] with own_x[i] = 2 wx (x_i - y_nn(i))
+// and S_x[i] = the ordered sum of own_y[j] over the j with nn'(j) = i; likewise for gY.  Both are WRITTEN.
+// workspace floats: own_x (B,P,3) | own_y (B,Q,3) | S_x (B,P,3) | S_y (B,Q,3); workspace ints: the scatter's, for the larger direction.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void chamfer_own_kernel(const float *__restrict__ X, int P, const float *__restrict__ Y, int Q,
+                                                         const int32_t *__restrict__ nn_xy, const int32_t *__restrict__ nn_yx, float wx, float wy,
+                                                         const float *__restrict__ g_dev, float *__restrict__ ownX, float *__restrict__ ownY)
+{
+    if (g_dev) { wx *= *g_dev; wy *= *g_dev; }
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const float *x = X + (size_t)b * P * 3, *y = Y + (size_t)b * Q * 3;
+    if (t < P) {
+        int j = nn_xy[(size_t)b * P + t];
+        j = j < 0 ? 0 : (j >= Q ? Q - 1 : j);
+        for (int a = 0; a < 3; ++a) ownX[((size_t)b * P + t) * 3 + a] = 2.f * wx * (x[3 * t + a] - y[3 * j + a]);
+    }
+    if (t < Q) {
+        int i = nn_yx[(size_t)b * Q + t];
+        i = i < 0 ? 0 : (i >= P ? P - 1 : i);
+        for (int a = 0; a < 3; ++a) ownY[((size_t)b * Q + t) * 3 + a] = 2.f * wy * (y[3 * t + a] - x[3 * i + a]);
+    }
+}
+
+__global__ __launch_bounds__(256) void chamfer_combine_kernel(const float *__restrict__ own, const float *__restrict__ sc, size_t n, float *__restrict__ g)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) g[i] = own[i] - sc[i];
+}
+
+extern "C" size_t pccx_chamfer_grad_det_workspace_floats(int B, int P, int Q)
+{
+    if (B < 1 || P < 1 || Q < 1) return 0;
+    return (size_t)6 * B * ((size_t)P + Q);
+}
+
+extern "C" size_t pccx_chamfer_grad_det_workspace_ints(int B, int P, int Q)
+{
+    const size_t a = pccx_scatter_add_ordered_workspace_ints(B, Q, P), b = pccx_scatter_add_ordered_workspace_ints(B, P, Q);
+    return a > b ? a : b;
+}
+
+extern "C" int pccx_chamfer_grad_det(const float *X, int B, int P, const float *Y, int Q, const int32_t *nn_xy, const int32_t *nn_yx,
+                                     const float *grad_out_dev, float *gX, float *gY, float *ws_floats, int32_t *ws_ints, void *stream)
+{
+    PCCX_CHECK_ARG(X && Y && nn_xy && nn_yx && grad_out_dev && gX && gY && ws_floats && ws_ints, "pccx_chamfer_grad_det: null pointer");
+    PCCX_CHECK_ARG(B >= 1 && P >= 1 && Q >= 1 && B <= 65535, "pccx_chamfer_grad_det: bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t np = (size_t)B * P * 3, nq = (size_t)B * Q * 3;
+    float *ownX = ws_floats, *ownY = ownX + np, *sX = ownY + nq, *sY = sX + np;
+    const int n = P > Q ? P : Q;
+    hipLaunchKernelGGL(chamfer_own_kernel, dim3((n + 255) / 256, B), dim3(256), 0, st, X, P, Y, Q, nn_xy, nn_yx, 1.0f / ((float)B * P),
+                       1.0f / ((float)B * Q), grad_out_dev, ownX, ownY);
+    PCCX_CHECK_LAUNCH();
+    int rc = pccx_scatter_add_ordered(ownY, 3, nn_yx, 1, B, Q, P, 3, sX, ws_ints, stream);       // the y that chose x_i, in ascending j
+    if (rc) return rc;
+    rc = pccx_scatter_add_ordered(ownX, 3, nn_xy, 1, B, P, Q, 3, sY, ws_ints, stream);           // the x that chose y_j, in ascending i
+    if (rc) return rc;
+    size_t bp = (np + 255) / 256, bq = (nq + 255) / 256;
+    hipLaunchKernelGGL(chamfer_combine_kernel, dim3((unsigned)(bp > 2048 ? 2048 : bp)), dim3(256), 0, st, ownX, sX, np, gX);
+    hipLaunchKernelGGL(chamfer_combine_kernel, dim3((unsigned)(bq > 2048 ? 2048 : bq)), dim3(256), 0, st, ownY, sY, nq, gY);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}

@@ -53,7 +53,9 @@ __device__ __forceinline__ float round_bf16(float v) { return (float)(__bf16)v; 
 // (16 TN) x (16 TK) tile of dW and a slice of the rows: per step of four rows it loads TN + TK operand registers and issues
 // TN * TK MFMAs (the first version loaded two registers per MFMA and was bound by its loads: 2.6 ms of the 13.7 ms step).
 // BF16 = the autocast backward: dZ and X rounded to bf16 (their products are then exact in fp32), fp32 accumulate.
-template <bool BF16, int TN, int TK>
+// DET (the deterministic mode, pccx_linear_dw_det): `dW` is then the workspace [slices][N][K] and the slice STORES its tile at
+// [blockIdx.z][n][k] instead of adding it atomically; fold_slices_kernel adds the slices in ascending index.
+template <bool BF16, int TN, int TK, bool DET = false>
 __global__ __launch_bounds__(256) void linear_dw_kernel(const float *__restrict__ dZ, const float *__restrict__ X, long M, int N,
                                                         int K, int ldz, int ldx, int rows_per_slice, float *__restrict__ dW)
 {
@@ -145,13 +147,16 @@ __global__ __launch_bounds__(256) void linear_dw_kernel(const float *__restrict_
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int nn = (nt0 + a) * 16 + 4 * g + r;
-            if (nn < N && k < K) atomicAdd(&dW[(size_t)nn * K + k], v[r]);
+            if (nn < N && k < K) {
+                if (DET) dW[((size_t)blockIdx.z * N + nn) * K + k] = v[r];
+                else atomicAdd(&dW[(size_t)nn * K + k], v[r]);
+            }
         }
     }
 }
 
-template <int TN, int TK>
-static int launch_dw(const float *dZ, const float *X, int64_t M, int N, int K, int ldz, int ldx, float *dW, int flags, hipStream_t st)
+// the row split of linear_dw_kernel, a function of (M, N, K) and the tile shape alone -> slices, *rps = rows per slice
+static int dw_slices(int64_t M, int N, int K, int TN, int TK, int cap, int *rps_out)
 {
     const int nt = (N + 15) / 16, kt = (K + 15) / 16;
     // tiles x slices ~ 512 workgroups (two per CU), each slice at least 256 rows (64 per wave): the atomics are slices x N x K
@@ -159,11 +164,20 @@ static int launch_dw(const float *dZ, const float *X, int64_t M, int N, int K, i
     int slices = (512 + tiles - 1) / tiles;
     const int max_slices = (int)((M + 255) / 256);
     if (slices > max_slices) slices = max_slices;
+    if (slices > cap) slices = cap;
     if (slices < 1) slices = 1;
-    if (slices > 1024) slices = 1024;
     int rps = (int)((M + slices - 1) / slices);
     rps = (rps + 15) / 16 * 16;
-    slices = (int)((M + rps - 1) / rps);
+    *rps_out = rps;
+    return (int)((M + rps - 1) / rps);
+}
+
+template <int TN, int TK>
+static int launch_dw(const float *dZ, const float *X, int64_t M, int N, int K, int ldz, int ldx, float *dW, int flags, hipStream_t st)
+{
+    const int nt = (N + 15) / 16, kt = (K + 15) / 16;
+    int rps;
+    const int slices = dw_slices(M, N, K, TN, TK, 1024, &rps);
     dim3 grid((nt + TN - 1) / TN, (kt + TK - 1) / TK, slices);
     PCCX_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535, "pccx_linear_dw: shape too large");
     const size_t lds = (size_t)4 * TN * TK * 256 * sizeof(float);
@@ -189,6 +203,94 @@ extern "C" int pccx_linear_dw(const float *dZ, const float *X, int64_t M, int N,
     if (nt >= 2 && kt >= 2) return launch_dw<2, 2>(dZ, X, M, N, K, ldz, ldx, dW, flags, (hipStream_t)stream);
     if (nt >= 2) return launch_dw<2, 1>(dZ, X, M, N, K, ldz, ldx, dW, flags, (hipStream_t)stream);
     return launch_dw<1, 1>(dZ, X, M, N, K, ldz, ldx, dW, flags, (hipStream_t)stream);
+}
+
+// ---- deterministic mode (a): partial tiles STORED per slice, then folded in ascending slice index ---------------------------------------
+// pccx_linear_dw_det stands in for pccx_linear_dw, pccx_linear_skinny_dx_det (below) for pccx_linear_skinny_dx.  The result is WRITTEN:
+// it needs no cleared buffer and ignores what dW held.  The slice count is dw_slices() of (M, N, K) with a cap that bounds the
+// workspace [slices][N][K] to max(8 x the weight, 2 Mi floats = 8 MiB): the decoder's 1024 x 16384 weight splits into ONE slice (its 4096
+// tiles fill the chip) and takes no workspace at all; a 64 x 64 layer over 131 072 rows keeps its 256 slices (4 MiB).
+#define DW_DET_WS_FLOATS ((size_t)2 << 20)
+static int dw_det_cap(int N, int K)
+{
+    const size_t w = (size_t)N * K;
+    const size_t cap = DW_DET_WS_FLOATS / w;
+    return cap < 8 ? 8 : (cap > 1024 ? 1024 : (int)cap);
+}
+
+// out[(i / cols) * ldo + i % cols] = part[0][i] + part[1][i] + ... (ascending slice index), i < n = rows * cols
+__global__ __launch_bounds__(256) void fold_slices_kernel(const float *__restrict__ part, int slices, size_t n, int cols, int ldo,
+                                                          float *__restrict__ out)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float t = part[i];
+        for (int s = 1; s < slices; ++s) t += part[(size_t)s * n + i];
+        out[(i / cols) * (size_t)ldo + i % cols] = t;
+    }
+}
+
+static int launch_fold_slices(const float *part, int slices, size_t n, int cols, int ldo, float *out, hipStream_t st)
+{
+    size_t blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(fold_slices_kernel, dim3((unsigned)blocks), dim3(256), 0, st, part, slices, n, cols, ldo, out);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+static void dw_tile_shape(int N, int K, int *TN, int *TK)
+{
+    const int nt = (N + 15) / 16, kt = (K + 15) / 16;
+    if (nt >= 4 && kt >= 4) { *TN = 4; *TK = 4; }
+    else if (nt >= 2 && kt >= 2) { *TN = 2; *TK = 2; }
+    else if (nt >= 2) { *TN = 2; *TK = 1; }
+    else { *TN = 1; *TK = 1; }
+}
+
+extern "C" size_t pccx_linear_dw_det_workspace_floats(int64_t M, int N, int K)
+{
+    if (M <= 0 || N < 1 || K < 1) return 0;
+    int TN, TK, rps;
+    dw_tile_shape(N, K, &TN, &TK);
+    const int slices = dw_slices(M, N, K, TN, TK, dw_det_cap(N, K), &rps);
+    return slices > 1 ? (size_t)slices * N * K : 0;
+}
+
+template <int TN, int TK>
+static int launch_dw_det(const float *dZ, const float *X, int64_t M, int N, int K, int ldz, int ldx, float *dW, int flags, float *ws,
+                         hipStream_t st)
+{
+    const int nt = (N + 15) / 16, kt = (K + 15) / 16;
+    int rps;
+    const int slices = dw_slices(M, N, K, TN, TK, dw_det_cap(N, K), &rps);
+    PCCX_CHECK_ARG(slices == 1 || ws, "pccx_linear_dw_det: %d slices need the workspace", slices);
+    dim3 grid((nt + TN - 1) / TN, (kt + TK - 1) / TK, slices);
+    PCCX_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535, "pccx_linear_dw_det: shape too large");
+    const size_t lds = (size_t)4 * TN * TK * 256 * sizeof(float);
+    if (lds > 48 * 1024) {
+        PCCX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_dw_kernel<true, TN, TK, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        PCCX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_dw_kernel<false, TN, TK, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    float *part = slices == 1 ? dW : ws;                  // one slice: its tile IS the result, stored straight into dW
+    if (flags & 2)
+        hipLaunchKernelGGL((linear_dw_kernel<true, TN, TK, true>), grid, dim3(256), lds, st, dZ, X, (long)M, N, K, ldz, ldx, rps, part);
+    else
+        hipLaunchKernelGGL((linear_dw_kernel<false, TN, TK, true>), grid, dim3(256), lds, st, dZ, X, (long)M, N, K, ldz, ldx, rps, part);
+    PCCX_CHECK_LAUNCH();
+    if (slices > 1) return launch_fold_slices(ws, slices, (size_t)N * K, K, K, dW, st);
+    return PCCX_OK;
+}
+
+extern "C" int pccx_linear_dw_det(const float *dZ, const float *X, int64_t M, int N, int K, int ldz, int ldx, float *dW, int flags,
+                                  float *workspace, void *stream)
+{
+    PCCX_CHECK_ARG(dZ && X && dW && M >= 1 && N >= 1 && K >= 1 && ldz >= N && ldx >= K, "pccx_linear_dw_det: bad arguments");
+    int TN, TK;
+    dw_tile_shape(N, K, &TN, &TK);
+    if (TN == 4) return launch_dw_det<4, 4>(dZ, X, M, N, K, ldz, ldx, dW, flags, workspace, (hipStream_t)stream);
+    if (TK == 2) return launch_dw_det<2, 2>(dZ, X, M, N, K, ldz, ldx, dW, flags, workspace, (hipStream_t)stream);
+    if (TN == 2) return launch_dw_det<2, 1>(dZ, X, M, N, K, ldz, ldx, dW, flags, workspace, (hipStream_t)stream);
+    return launch_dw_det<1, 1>(dZ, X, M, N, K, ldz, ldx, dW, flags, workspace, (hipStream_t)stream);
 }
 
 // ---- layers with a handful of rows (the pppe model's global / decoder / probability Linears: M = batch = 4) ---------------------
@@ -237,7 +339,8 @@ __global__ __launch_bounds__(256) void skinny_fwd_kernel(const float *__restrict
     }
 }
 
-template <bool BF16>
+// DET (pccx_linear_skinny_dx_det): `dx` is the workspace [chunks][M][K] and n-chunk blockIdx.y STORES its partial rows there.
+template <bool BF16, bool DET = false>
 __global__ __launch_bounds__(256) void skinny_dx_kernel(const float *__restrict__ dz, int M, int N, int ldz, const float *__restrict__ W, int K,
                                                        int rows_per_chunk, float *__restrict__ dx, int ldd)
 {
@@ -276,6 +379,10 @@ __global__ __launch_bounds__(256) void skinny_dx_kernel(const float *__restrict_
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
         if (m < M) {
+            if (DET) {
+                *(float4 *)(dx + ((size_t)blockIdx.y * M + m) * ldd + 4 * k4) = acc[m];
+                continue;
+            }
             float *o = dx + (size_t)m * ldd + 4 * k4;
             atomicAdd(o, acc[m].x); atomicAdd(o + 1, acc[m].y); atomicAdd(o + 2, acc[m].z); atomicAdd(o + 3, acc[m].w);
         }
@@ -298,6 +405,21 @@ extern "C" int pccx_linear_skinny(const float *x, int M, int K, int ldx, const f
     return PCCX_OK;
 }
 
+// the n-chunks of the split-K dX, a function of (N, K) alone -> chunks, *rpc = W rows per chunk: about one workgroup per CU in all, every
+// chunk ends in M x K atomics (the 100 MB expansion layer: 58 us at 256, 66 at 128, 80 at 512, 128 at the old 1024); the deterministic
+// form cuts the same chunks
+static int skinny_dx_chunks(int N, int K, int *rpc_out)
+{
+    const int kblocks = (K / 4 + 255) / 256;
+    int chunks = 256 / kblocks;
+    if (chunks < 1) chunks = 1;
+    int rpc = (N + chunks - 1) / chunks;
+    if (rpc < 32) rpc = 32;
+    rpc = (rpc + 7) / 8 * 8;
+    *rpc_out = rpc;
+    return (N + rpc - 1) / rpc;
+}
+
 // dX (M, K) += dZ (M, N) . W (N, K); dX must be zeroed by the caller (partial sums of the n-chunks are added atomically).
 extern "C" int pccx_linear_skinny_dx(const float *dZ, int M, int N, int ldz, const float *W, int K, int flags, float *dX, int ldd, void *stream)
 {
@@ -306,19 +428,42 @@ extern "C" int pccx_linear_skinny_dx(const float *dZ, int M, int N, int ldz, con
     PCCX_CHECK_ARG(M >= 1 && M <= 8 && K >= 4 && K % 4 == 0 && N >= 1 && ldz >= N && ldd >= K && ((uintptr_t)W & 15) == 0,
                    "pccx_linear_skinny_dx: needs 1 <= M <= 8 rows and K %% 4 == 0 (M=%d K=%d)", M, K);
     const int kblocks = (K / 4 + 255) / 256;
-    int chunks = 256 / kblocks;                                        // about one workgroup per CU in all: every chunk ends in M x K atomics
-                                                                       // (the 100 MB expansion layer: 58 us at 256, 66 at 128, 80 at 512, 128 at the old 1024)
-    if (chunks < 1) chunks = 1;
-    int rpc = (N + chunks - 1) / chunks;
-    if (rpc < 32) rpc = 32;
-    rpc = (rpc + 7) / 8 * 8;
-    chunks = (N + rpc - 1) / rpc;
+    int rpc;
+    const int chunks = skinny_dx_chunks(N, K, &rpc);
     if (flags & 2)
         hipLaunchKernelGGL(skinny_dx_kernel<true>, dim3(kblocks, chunks), dim3(256), 0, (hipStream_t)stream, dZ, M, N, ldz, W, K, rpc, dX, ldd);
     else
         hipLaunchKernelGGL(skinny_dx_kernel<false>, dim3(kblocks, chunks), dim3(256), 0, (hipStream_t)stream, dZ, M, N, ldz, W, K, rpc, dX, ldd);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
+}
+
+// workspace [chunks][M][K]: a chunk is at least 32 W rows and M <= 8, so it is at most a quarter of the weight
+extern "C" size_t pccx_linear_skinny_dx_det_workspace_floats(int M, int N, int K)
+{
+    if (M < 1 || N < 1 || K < 4) return 0;
+    int rpc;
+    return (size_t)skinny_dx_chunks(N, K, &rpc) * M * K;
+}
+
+// dX (M, K) = dZ (M, N) . W (N, K), WRITTEN: every n-chunk stores its partial rows, fold_slices_kernel adds the chunks in ascending index
+// (deterministic mode; stands in for pccx_linear_skinny_dx, whose chunks add atomically into a cleared dX)
+extern "C" int pccx_linear_skinny_dx_det(const float *dZ, int M, int N, int ldz, const float *W, int K, int flags, float *dX, int ldd,
+                                         float *workspace, void *stream)
+{
+    PCCX_CHECK_ARG(dZ && W && dX && workspace, "pccx_linear_skinny_dx_det: null pointer");
+    PCCX_CHECK_ARG(M >= 1 && M <= 8 && K >= 4 && K % 4 == 0 && N >= 1 && ldz >= N && ldd >= K && ((uintptr_t)W & 15) == 0 &&
+                       ((uintptr_t)workspace & 15) == 0,
+                   "pccx_linear_skinny_dx_det: needs 1 <= M <= 8 rows, K %% 4 == 0 and a 16-byte aligned workspace (M=%d K=%d)", M, K);
+    const int kblocks = (K / 4 + 255) / 256;
+    int rpc;
+    const int chunks = skinny_dx_chunks(N, K, &rpc);
+    if (flags & 2)
+        hipLaunchKernelGGL((skinny_dx_kernel<true, true>), dim3(kblocks, chunks), dim3(256), 0, (hipStream_t)stream, dZ, M, N, ldz, W, K, rpc, workspace, K);
+    else
+        hipLaunchKernelGGL((skinny_dx_kernel<false, true>), dim3(kblocks, chunks), dim3(256), 0, (hipStream_t)stream, dZ, M, N, ldz, W, K, rpc, workspace, K);
+    PCCX_CHECK_LAUNCH();
+    return launch_fold_slices(workspace, chunks, (size_t)M * K, K, ldd, dX, (hipStream_t)stream);
 }
 
 // ---- column reductions -----------------------------------------------------------------------------
@@ -1158,4 +1303,354 @@ extern "C" int pccx_rate_from_logits(const float *logits, const float *y_q, int 
     hipLaunchKernelGGL(rate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, logits, y_q, B, bins, ld_yq, out);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
+}
+
+// ====================================================================================================================================
+// Deterministic mode (b): ordered column and scalar sums.  Workgroup w STORES its double partial(s) in slot w of a workspace
+// [slots][ncol]; fold_slots_kernel adds the slots in ascending index, starting from +0, and writes what the consumers read today.  Every
+// grid below is a function of the shapes alone; inside a workgroup the rows of a thread, the row lanes of a column and the waves of a
+// scalar sum are added in a fixed order.  Nothing here needs a cleared buffer.
+// ====================================================================================================================================
+// out_d[j] = sum of the slots (and +0 into the other nrep - 1 replicas, rep_stride doubles apart: the layout of
+// pccx_train_sums_doubles, which the BatchNorm apply kernels add up); out_f[j] = that sum as float for j < nf.  Either may be null.
+__global__ __launch_bounds__(256) void fold_slots_kernel(const double *__restrict__ part, int slots, int ncol, double *__restrict__ out_d,
+                                                         int nrep, size_t rep_stride, float *__restrict__ out_f, int nf)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= ncol) return;
+    double t = 0;
+    for (int s = 0; s < slots; ++s) t += part[(size_t)s * ncol + j];
+    if (out_d) {
+        out_d[j] = t;
+        for (int r = 1; r < nrep; ++r) out_d[(size_t)r * rep_stride + j] = 0.0;
+    }
+    if (out_f && j < nf) out_f[j] = (float)t;
+}
+
+static int launch_fold_slots(const double *part, int slots, int ncol, double *out_d, int nrep, size_t rep_stride, float *out_f, int nf,
+                             hipStream_t st)
+{
+    hipLaunchKernelGGL(fold_slots_kernel, dim3((ncol + 255) / 256), dim3(256), 0, st, part, slots, ncol, out_d, nrep, rep_stride, out_f, nf);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+// The three reductions of col_reduce_kernel for ANY channel count: a workgroup is cw columns x (256 / cw) row lanes (cw = 64, or the next
+// power of two above a smaller C) over rows_per_block rows; a thread adds its rows in ascending order (four loads in flight), thread
+// (column, lane 0) adds the row lanes in ascending order through LDS and stores part[blockIdx.y][sum][c].
+template <int MODE>
+__global__ __launch_bounds__(256) void col_reduce_det_kernel(const float *__restrict__ A, const float *__restrict__ Y, const float *__restrict__ Z,
+                                                            const float *__restrict__ mean, const float *__restrict__ rstd, long M, int C, int cw,
+                                                            long rows_per_block, double *__restrict__ part)
+{
+    constexpr int NS = MODE == 2 ? 1 : 2;
+    __shared__ double red[2][256];
+    const int tid = threadIdx.x, cl = tid % cw, rl = tid / cw, nrl = 256 / cw;
+    const int c = blockIdx.x * cw + cl;
+    const bool okc = c < C;
+    const long m0 = (long)blockIdx.y * rows_per_block;
+    const long m1 = m0 + rows_per_block < M ? m0 + rows_per_block : M;
+    double s0 = 0, s1 = 0;
+    if (okc) {
+        const float mu = MODE == 1 ? mean[c] : 0.f, rs = MODE == 1 ? rstd[c] : 0.f;
+        auto add = [&](float a, float y, float z) {
+            if (MODE == 0) {
+                const double zz = a;
+                s0 += zz; s1 += zz * zz;
+            } else if (MODE == 1) {
+                const float d = y > 0.f ? a : 0.f;
+                s0 += (double)d * (double)((z - mu) * rs);
+                s1 += d;
+            } else {
+                s0 += a;
+            }
+        };
+        long m = m0 + rl;
+        for (; m + 3 * nrl < m1; m += 4 * nrl) {
+            float a[4], y[4], z[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const size_t e = (size_t)(m + (long)q * nrl) * C + c;
+                a[q] = A[e];
+                y[q] = MODE == 1 ? Y[e] : 0.f;
+                z[q] = MODE == 1 ? Z[e] : 0.f;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) add(a[q], y[q], z[q]);
+        }
+        for (; m < m1; m += nrl) {
+            const size_t e = (size_t)m * C + c;
+            add(A[e], MODE == 1 ? Y[e] : 0.f, MODE == 1 ? Z[e] : 0.f);
+        }
+    }
+    red[0][tid] = s0;
+    red[1][tid] = s1;
+    __syncthreads();
+    if (rl == 0 && okc) {
+        double t0 = 0, t1 = 0;
+        for (int l = 0; l < nrl; ++l) { t0 += red[0][l * cw + cl]; t1 += red[1][l * cw + cl]; }
+        part[((size_t)blockIdx.y * NS) * C + c] = t0;
+        if (NS == 2) part[((size_t)blockIdx.y * NS + 1) * C + c] = t1;
+    }
+}
+
+// rows per workgroup and the slot count of col_reduce_det_kernel: at most 256 slots, at least 256 rows each
+static int col_det_slots(int64_t M, int C, int *cw_out, long *rpb_out)
+{
+    int cw = 64;
+    if (C < 64) { cw = 1; while (cw < C) cw <<= 1; }
+    long rpb = (long)((M + 255) / 256);
+    if (rpb < 256) rpb = 256;
+    *cw_out = cw;
+    *rpb_out = rpb;
+    return (int)((M + rpb - 1) / rpb);
+}
+
+extern "C" size_t pccx_col_reduce_det_doubles(int64_t M, int C)
+{
+    if (M < 1 || C < 1) return 0;
+    int cw;
+    long rpb;
+    return (size_t)col_det_slots(M, C, &cw, &rpb) * 2 * C;
+}
+
+// mode 0 / 1 / 2 of col_reduce_kernel (BatchNorm moments of A; BatchNorm-ReLU backward sums of dY = A with Y, Z, mean, rstd; column sums
+// of A), ordered.  partials: pccx_col_reduce_det_doubles(M, C) doubles of scratch.  sums (may be null): pccx_train_sums_doubles(C)
+// doubles, ALL written -- the totals in replica 0 ([0, C) the first sum, [C, 2C) the second), +0 in the other replicas -- which
+// pccx_bn_relu_train_forward / _backward take with flags 4 | 8; in mode 2 `sums` is the C column sums alone.  f32_out (may be null): the
+// first sum as C floats (the bias gradient).  Stands in for the col_reduce*_kernel launches inside pccx_bn_relu_train_forward / _backward /
+// pccx_col_sum_w and for the moment / bnback epilogues of linear.hip.
+extern "C" int pccx_col_reduce_det(int mode, const float *A, const float *Y, const float *Z, const float *mean, const float *rstd, int64_t M,
+                                   int C, double *partials, double *sums, float *f32_out, void *stream)
+{
+    PCCX_CHECK_ARG(A && partials && (sums || f32_out) && M >= 1 && C >= 1 && mode >= 0 && mode <= 2, "pccx_col_reduce_det: bad arguments");
+    PCCX_CHECK_ARG(mode != 1 || (Y && Z && mean && rstd), "pccx_col_reduce_det: mode 1 needs Y, Z, mean and rstd");
+    hipStream_t st = (hipStream_t)stream;
+    int cw;
+    long rpb;
+    const int slots = col_det_slots(M, C, &cw, &rpb);
+    dim3 grid((C + cw - 1) / cw, slots);
+    if (mode == 0) hipLaunchKernelGGL(col_reduce_det_kernel<0>, grid, dim3(256), 0, st, A, Y, Z, mean, rstd, (long)M, C, cw, rpb, partials);
+    else if (mode == 1) hipLaunchKernelGGL(col_reduce_det_kernel<1>, grid, dim3(256), 0, st, A, Y, Z, mean, rstd, (long)M, C, cw, rpb, partials);
+    else hipLaunchKernelGGL(col_reduce_det_kernel<2>, grid, dim3(256), 0, st, A, Y, Z, mean, rstd, (long)M, C, cw, rpb, partials);
+    PCCX_CHECK_LAUNCH();
+    if (mode == 2) return launch_fold_slots(partials, slots, C, sums, 1, 0, f32_out, C, st);
+    return launch_fold_slots(partials, slots, 2 * C, sums, PCCX_SUM_REPLICAS, (size_t)2 * C, f32_out, C, st);
+}
+
+// smooth_l1_kernel / sumsq_multi_kernel with the workgroup's sum STORED in slot blockIdx.x: the lanes of a wave are added by the xor
+// butterfly (a fixed tree), the four waves in wave order
+__device__ __forceinline__ void store_block_sum(double s, double *__restrict__ slot)
+{
+    for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
+    __shared__ double wsum[4];
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) *slot = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+__global__ __launch_bounds__(256) void smooth_l1_det_kernel(const float *__restrict__ a, const float *__restrict__ b, long n, float gscale,
+                                                           double *__restrict__ part, float *__restrict__ grad)
+{
+    double s = 0;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const float d = a[i] - b[i], ad = fabsf(d);
+        s += ad < 1.f ? 0.5 * (double)d * d : (double)ad - 0.5;
+        if (grad) grad[i] = gscale * (ad < 1.f ? d : (d > 0.f ? 1.f : -1.f));
+    }
+    store_block_sum(s, part + blockIdx.x);
+}
+
+static long smooth_l1_blocks(int64_t n)
+{
+    long blocks = (long)((n + 255) / 256);
+    return blocks > 1024 ? 1024 : blocks;
+}
+
+extern "C" size_t pccx_smooth_l1_det_doubles(int64_t n) { return n >= 1 ? (size_t)smooth_l1_blocks(n) : 0; }
+
+// pccx_smooth_l1 with value[0] WRITTEN as the ordered sum of the workgroups' partials (partials: pccx_smooth_l1_det_doubles(n) doubles)
+extern "C" int pccx_smooth_l1_det(const float *a, const float *b, int64_t n, float grad_scale, double *partials, double *value, float *grad,
+                                  void *stream)
+{
+    PCCX_CHECK_ARG(a && b && partials && value && n >= 1, "pccx_smooth_l1_det: bad arguments");
+    const long blocks = smooth_l1_blocks(n);
+    hipLaunchKernelGGL(smooth_l1_det_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, (long)n, grad_scale, partials, grad);
+    PCCX_CHECK_LAUNCH();
+    return launch_fold_slots(partials, (int)blocks, 1, value, 1, 0, nullptr, 0, (hipStream_t)stream);
+}
+
+__global__ __launch_bounds__(256) void sumsq_multi_det_kernel(const MtRow *__restrict__ tab, int T, long total_blocks, double *__restrict__ part)
+{
+    double s = 0;
+    for (long blk = (long)blockIdx.x * MT_SUMSQ_SPAN; blk < min((long)(blockIdx.x + 1) * MT_SUMSQ_SPAN, total_blocks); ++blk) {
+        const MtRow row = tab[mt_find_row(tab, T, blk)];
+        const long base = (blk - row.first) * MT_ELEMS;
+        for (int u = 0; u < MT_ELEMS / 256; ++u) {
+            const long i = base + u * 256 + threadIdx.x;
+            if (i < row.n) { const double gi = row.g[i]; s += gi * gi; }
+        }
+    }
+    store_block_sum(s, part + blockIdx.x);
+}
+
+extern "C" size_t pccx_sumsq_multi_det_doubles(int64_t total_blocks)
+{
+    return total_blocks >= 1 ? (size_t)((total_blocks + MT_SUMSQ_SPAN - 1) / MT_SUMSQ_SPAN) : 0;
+}
+
+// pccx_sumsq_multi with acc[0] WRITTEN as the ordered sum of the workgroups' partials (partials: pccx_sumsq_multi_det_doubles doubles)
+extern "C" int pccx_sumsq_multi_det(const int64_t *table_dev, int ntensors, int64_t total_blocks, double *partials, double *acc, void *stream)
+{
+    PCCX_CHECK_ARG(table_dev && partials && acc && ntensors >= 1 && total_blocks >= 1 && total_blocks <= 0x7fffffffLL,
+                   "pccx_sumsq_multi_det: bad arguments");
+    const long blocks = (long)((total_blocks + MT_SUMSQ_SPAN - 1) / MT_SUMSQ_SPAN);
+    hipLaunchKernelGGL(sumsq_multi_det_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const MtRow *)table_dev, ntensors,
+                       (long)total_blocks, partials);
+    PCCX_CHECK_LAUNCH();
+    return launch_fold_slots(partials, (int)blocks, 1, acc, 1, 0, nullptr, 0, (hipStream_t)stream);
+}
+
+// ====================================================================================================================================
+// Deterministic mode (c): ordered segmented scatter-add.  out[b][n][:] = the fp32 sum, starting from +0, of vals[b][m][:] over the
+// sources m with idx[b][m] == n in ASCENDING m; rows nobody targets are +0.  A pure function of its inputs (np.add.at on float32 gives
+// the same bits).  The inverse lists are built on the device, per cloud: count per destination (integer atomics: order-free), exclusive
+// scan, fill (the position inside a segment is whatever the atomic cursor hands out), then every entry finds its RANK among the entries
+// of its segment -- a count of the smaller m over the segment in global memory, so a segment may be as long as M -- and the sorted list
+// is summed row by row.  workspace ints: cursor [B][N] | offsets [B][N + 1] | filled [B][M] | sorted [B][M].
+// Cost of the ranking: the sum over the segments of L^2 four-byte reads (L = segment length), spread over one thread per source --
+// 2 M per cloud at the training shapes (L ~ S K / N ~ 2), 17 M reads for 4096 sources on one row (tests), 67 M for the 8192 points of an
+// untrained decoder's blob on one neighbour; quadratic beyond that (4 G for 65 536 sources on one row), where a stable radix sort of
+// (destination, m) as in sort.hip would be the form to take.  The sum itself is serial per row by definition (ascending m).
+// Indices are clamped to [0, N - 1] (pccx_gather_backward clamps a negative index, the -1 padding of ball_query, to row 0 as well).
+// ====================================================================================================================================
+template <typename I>
+__device__ __forceinline__ int seg_dest(const I *__restrict__ idx, size_t e, int N)
+{
+    const long long i = (long long)idx[e];
+    return i < 0 ? 0 : (i >= N ? N - 1 : (int)i);
+}
+
+template <typename I>
+__global__ __launch_bounds__(256) void seg_count_kernel(const I *__restrict__ idx, long total, int Mrows, int N, int *__restrict__ cnt)
+{
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x)
+        atomicAdd(&cnt[(e / Mrows) * N + seg_dest(idx, (size_t)e, N)], 1);
+}
+
+// one workgroup per cloud: off[b][0 .. N] = exclusive scan of cnt[b][:], and cnt[b][n] := off[b][n] (the fill's cursor)
+__global__ __launch_bounds__(256) void seg_scan_kernel(int *__restrict__ cnt, int N, int Mrows, int *__restrict__ off)
+{
+    __shared__ int sh[256];
+    const int b = blockIdx.x, t = threadIdx.x;
+    int *c = cnt + (size_t)b * N, *o = off + (size_t)b * (N + 1);
+    const int per = (N + 255) / 256;
+    const int i0 = min(t * per, N), i1 = min(i0 + per, N);
+    int s = 0;
+    for (int i = i0; i < i1; ++i) s += c[i];
+    sh[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        int run = 0;
+        for (int k = 0; k < 256; ++k) { const int v = sh[k]; sh[k] = run; run += v; }
+        o[N] = Mrows;
+    }
+    __syncthreads();
+    int run = sh[t];
+    for (int i = i0; i < i1; ++i) {
+        const int v = c[i];
+        o[i] = run;
+        c[i] = run;
+        run += v;
+    }
+}
+
+template <typename I>
+__global__ __launch_bounds__(256) void seg_fill_kernel(const I *__restrict__ idx, long total, int Mrows, int N, int *__restrict__ cursor,
+                                                      int *__restrict__ filled)
+{
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const long b = e / Mrows;
+        const int p = atomicAdd(&cursor[b * N + seg_dest(idx, (size_t)e, N)], 1);
+        if (p >= 0 && p < Mrows) filled[b * Mrows + p] = (int)(e - b * Mrows);
+    }
+}
+
+// entry p of cloud b's filled list holds source m; its place in the sorted list is the segment's start + the number of smaller m there
+template <typename I>
+__global__ __launch_bounds__(256) void seg_rank_kernel(const I *__restrict__ idx, long total, int Mrows, int N, const int *__restrict__ off,
+                                                      const int *__restrict__ filled, int *__restrict__ sorted)
+{
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const long b = e / Mrows;
+        const int *f = filled + b * Mrows;
+        const int m = f[e - b * Mrows];
+        const int n = seg_dest(idx, (size_t)(b * Mrows + m), N);
+        const int s0 = off[b * (N + 1) + n], s1 = off[b * (N + 1) + n + 1];
+        int r = 0, q = s0;
+        for (; q + 3 < s1; q += 4) r += (f[q] < m) + (f[q + 1] < m) + (f[q + 2] < m) + (f[q + 3] < m);
+        for (; q < s1; ++q) r += f[q] < m;
+        sorted[b * Mrows + s0 + r] = m;
+    }
+}
+
+// thread (n, c) of cloud blockIdx.y walks row n's sorted sources: four indices, then their four values, in flight per trip; the adds in order
+__global__ __launch_bounds__(256) void seg_sum_kernel(const float *__restrict__ vals, int ldv, int Mrows, int N, int C, const int *__restrict__ off,
+                                                     const int *__restrict__ sorted, float *__restrict__ out)
+{
+    const long b = blockIdx.y;
+    const long total = (long)N * C;
+    const int *srt = sorted + b * Mrows;
+    const float *v = vals + (size_t)b * Mrows * ldv;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+        const int n = (int)(e / C), c = (int)(e % C);
+        const int s0 = off[b * (N + 1) + n], s1 = off[b * (N + 1) + n + 1];
+        float acc = 0.f;
+        int q = s0;
+        for (; q + 3 < s1; q += 4) {
+            const int m0 = srt[q], m1 = srt[q + 1], m2 = srt[q + 2], m3 = srt[q + 3];
+            const float v0 = v[(size_t)m0 * ldv + c], v1 = v[(size_t)m1 * ldv + c], v2 = v[(size_t)m2 * ldv + c], v3 = v[(size_t)m3 * ldv + c];
+            acc += v0; acc += v1; acc += v2; acc += v3;
+        }
+        for (; q < s1; ++q) acc += v[(size_t)srt[q] * ldv + c];
+        out[((size_t)b * N + n) * C + c] = acc;
+    }
+}
+
+extern "C" size_t pccx_scatter_add_ordered_workspace_ints(int B, int Mrows, int N)
+{
+    if (B < 1 || Mrows < 1 || N < 1) return 0;
+    return (size_t)B * N + (size_t)B * (N + 1) + 2 * (size_t)B * Mrows;
+}
+
+template <typename I>
+static int scatter_ordered_launch(const float *vals, int ldv, const I *idx, int B, int Mrows, int N, int C, float *out, int *ws, hipStream_t st)
+{
+    int *cnt = ws, *off = cnt + (size_t)B * N, *filled = off + (size_t)B * (N + 1), *sorted = filled + (size_t)B * Mrows;
+    const long total = (long)B * Mrows;
+    PCCX_CHECK_HIP(pccx_zero_async(cnt, sizeof(int) * (size_t)B * N, st));
+    long blocks = (total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(seg_count_kernel<I>, dim3((unsigned)blocks), dim3(256), 0, st, idx, total, Mrows, N, cnt);
+    hipLaunchKernelGGL(seg_scan_kernel, dim3(B), dim3(256), 0, st, cnt, N, Mrows, off);
+    hipLaunchKernelGGL(seg_fill_kernel<I>, dim3((unsigned)blocks), dim3(256), 0, st, idx, total, Mrows, N, cnt, filled);
+    hipLaunchKernelGGL(seg_rank_kernel<I>, dim3((unsigned)blocks), dim3(256), 0, st, idx, total, Mrows, N, off, filled, sorted);
+    long sblocks = ((long)N * C + 255) / 256;
+    if (sblocks > 4096) sblocks = 4096;
+    hipLaunchKernelGGL(seg_sum_kernel, dim3((unsigned)sblocks, B), dim3(256), 0, st, vals, ldv, Mrows, N, C, off, sorted, out);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+// vals (B, Mrows, row stride ldv >= C), idx (B, Mrows) int64 (idx_is_i32 = 0) or int32 (1) into N rows, out (B, N, C) WRITTEN.
+// workspace: pccx_scatter_add_ordered_workspace_ints(B, Mrows, N) ints.  Stands in for scatter_add_rows_kernel (pccx_gather_backward_acc)
+// and for the nearest-neighbour scatter of chamfer_grad_kernel (through pccx_chamfer_grad_det).
+extern "C" int pccx_scatter_add_ordered(const float *vals, int ldv, const void *idx, int idx_is_i32, int B, int Mrows, int N, int C,
+                                        float *out, int32_t *workspace, void *stream)
+{
+    PCCX_CHECK_ARG(vals && idx && out && workspace, "pccx_scatter_add_ordered: null pointer");
+    PCCX_CHECK_ARG(B >= 1 && B <= 65535 && Mrows >= 1 && N >= 1 && C >= 1 && ldv >= C && (long)B * Mrows <= 0x7fffffffL && (long)B * (N + 1) <= 0x7fffffffL,
+                   "pccx_scatter_add_ordered: bad shape (B=%d M=%d N=%d C=%d ldv=%d)", B, Mrows, N, C, ldv);
+    if (idx_is_i32) return scatter_ordered_launch(vals, ldv, (const int32_t *)idx, B, Mrows, N, C, out, (int *)workspace, (hipStream_t)stream);
+    return scatter_ordered_launch(vals, ldv, (const int64_t *)idx, B, Mrows, N, C, out, (int *)workspace, (hipStream_t)stream);
 }

@@ -247,6 +247,20 @@ def point_plane_err(x, y, normals_y):
 
 
 zeros_hook = None       # pccx.train installs its arena's allocator here: (shape, dtype, device) -> (zero tensor, from-arena?)
+deterministic_hook = None    # pccx.train: () -> True while a deterministic step runs (train.step_scope(deterministic=True))
+
+
+def chamfer_grad_det(x, y, nxy, nyx, gd):
+    """The Chamfer gradient with its nearest-neighbour scatter in ascending source order (pccx_chamfer_grad_det): gx, gy WRITTEN into
+    plain memory; gd = the upstream gradient, one float32 on the device."""
+    lib = _lib.load()
+    B, P, Q = x.shape[0], x.shape[1], y.shape[1]
+    gx, gy = torch.empty_like(x), torch.empty_like(y)
+    wf = torch.empty(max(int(lib.pccx_chamfer_grad_det_workspace_floats(B, P, Q)), 1), device=x.device, dtype=torch.float32)
+    wi = torch.empty(max(int(lib.pccx_chamfer_grad_det_workspace_ints(B, P, Q)), 1), device=x.device, dtype=torch.int32)
+    _lib.call("pccx_chamfer_grad_det", x.data_ptr(), B, P, y.data_ptr(), Q, nxy.data_ptr(), nyx.data_ptr(), gd.data_ptr(), gx.data_ptr(),
+              gy.data_ptr(), wf.data_ptr(), wi.data_ptr(), _stream())
+    return gx, gy
 
 
 class _ChamferFn(torch.autograd.Function):
@@ -258,6 +272,7 @@ class _ChamferFn(torch.autograd.Function):
         dxy, nxy = nn_dist(x, y, return_idx=True)
         dyx, nyx = nn_dist(y, x, return_idx=True)
         ctx.save_for_backward(x, y, nxy, nyx)
+        ctx.det = bool(deterministic_hook()) if deterministic_hook is not None else False
         out = torch.empty((), device=x.device, dtype=torch.float32)
         _lib.call("pccx_chamfer_mean", dxy.data_ptr(), dyx.data_ptr(), x.shape[0], x.shape[1], y.shape[1], out.data_ptr(), _stream())
         return out
@@ -266,6 +281,8 @@ class _ChamferFn(torch.autograd.Function):
     def backward(ctx, g):
         x, y, nxy, nyx = ctx.saved_tensors
         gd = g.detach().to(torch.float32).reshape(1).contiguous()        # stays on the device: no sync inside backward
+        if ctx.det:
+            return chamfer_grad_det(x, y, nxy, nyx, gd)
         if zeros_hook is not None:          # inside a training step: the two gradients come cleared from the step's arena (train.StepArena)
             gx, gy = zeros_hook(tuple(x.shape), torch.float32, x.device)[0], zeros_hook(tuple(y.shape), torch.float32, y.device)[0]
             _lib.call("pccx_chamfer_grad_dev_acc", x.data_ptr(), x.shape[0], x.shape[1], y.data_ptr(), y.shape[1], nxy.data_ptr(),

@@ -147,10 +147,14 @@ def _chamfer_setup(ctx, inputs, output):
     x, y = inputs
     _, nxy, nyx = output
     ctx.save_for_backward(x, y, nxy, nyx)
+    ctx.det = bool(_ops.deterministic_hook()) if _ops.deterministic_hook is not None else False
 
 
 def _chamfer_backward(ctx, g, _g1, _g2):
     x, y, nxy, nyx = ctx.saved_tensors
+    if ctx.det:                                      # inside train.step_scope(deterministic=True): the ordered scatter, g read on the device
+        return _ops.chamfer_grad_det(_ops._f32c(x, "chamfer_grad.x"), _ops._f32c(y, "chamfer_grad.y"), nxy.contiguous(), nyx.contiguous(),
+                                     g.detach().to(torch.float32).reshape(1).contiguous())
     gx, gy = torch.ops.pccx.chamfer_grad(x, y, nxy, nyx, float(g))
     return gx, gy
 

@@ -24,6 +24,7 @@ from .ops import _stream
 
 _SCRATCH = {}
 _AUTOCAST = False          # True while the forward of an autocast step runs (step_scope): the Linear layers take their bf16 form
+_DETERMINISTIC = False     # True through a deterministic step (step_scope): every accumulation takes its fixed-order form
 
 
 class StepArena:
@@ -38,14 +39,15 @@ class StepArena:
     def __init__(self):
         self.buf, self.off, self.need, self.active = None, 0, 0, False
 
-    def begin(self, device):
+    def begin(self, device, clear=True):
+        """clear=False (a deterministic step: nothing is taken from the arena) leaves the buffer of earlier steps as it is"""
         self.off, self.need, self.active = 0, 0, True
         dv = torch.device(device)
         if dv.type == "cuda" and dv.index is None:
             dv = torch.device("cuda", torch.cuda.current_device())
         if self.buf is not None and self.buf.device != dv:
             self.buf = None
-        if self.buf is not None:
+        if self.buf is not None and clear:
             _lib.call("pccx_zero_bytes", self.buf.data_ptr(), self.buf.numel(), _stream())
 
     def zeros(self, shape, dtype, device):
@@ -73,17 +75,20 @@ _ARENA = None              # the arena of the step in progress (step_scope insta
 
 
 @contextlib.contextmanager
-def step_scope(device, arena=None, autocast=False, params=(), begin=True, end=True):
+def step_scope(device, arena=None, autocast=False, params=(), begin=True, end=True, deterministic=False):
     """The process-wide state of one training iteration, set on entry and restored on EVERY way out of the block; the only code that
-    assigns _AUTOCAST or _ARENA.  Entry: every .grad of `params` is dropped (optimizer.zero_grad()), the arena is installed and begun --
+    assigns _AUTOCAST, _DETERMINISTIC or _ARENA.  Entry: every .grad of `params` is dropped (optimizer.zero_grad()), the arena is installed and begun --
     ONE clear for everything the step accumulates into -- and _AUTOCAST is set.  arena=None is an eager step: _EAGER_ARENA on a CUDA
     device (looked up now: a caller may have swapped in a fresh one), no arena on the CPU.  The block receives forward_done(), to call
     in front of loss.backward(): autocast off (the backward layers carry their arithmetic in ctx.flags).  The arena stays installed
     through backward AND the optimiser step: Adam's norm accumulator comes from it.  Exit: _AUTOCAST False, _ARENA None, arena ended.
     A step cut in two (GraphedTrainStep(data_parallel=True): forward + backward | gradient all-reduce | clip + Adam) enters twice:
     end=False leaves the arena open after the first half -- unless the block raises, which always ends it -- and begin=False installs
-    it again for the second without dropping the gradients or clearing what the first half accumulated."""
-    global _AUTOCAST, _ARENA
+    it again for the second without dropping the gradients or clearing what the first half accumulated.
+    deterministic=True: _DETERMINISTIC stays set through forward, backward AND the optimiser step (the Functions read it in forward and
+    carry it to backward in ctx; Adam reads it for its norm); every accumulation then WRITES its result in a fixed order into plain
+    torch.empty memory, so nothing is taken from the arena and the arena's clear is not launched."""
+    global _AUTOCAST, _ARENA, _DETERMINISTIC
     device = torch.device(device)
     if arena is None and device.type == "cuda":
         arena = _EAGER_ARENA
@@ -98,25 +103,28 @@ def step_scope(device, arena=None, autocast=False, params=(), begin=True, end=Tr
             for p in params:
                 p.grad = None
             if arena is not None:
-                arena.begin(device)
+                arena.begin(device, clear=not deterministic)
         _AUTOCAST = bool(autocast)
+        _DETERMINISTIC = bool(deterministic)
         yield forward_done
     except BaseException:
         end = True
         raise
     finally:
         _AUTOCAST = False
+        _DETERMINISTIC = False
         _ARENA = None
         if arena is not None and end:
             arena.end(device)
 
 
-def capture_step(device, opt, warmup, warm, body, opt_body=None, debug_dot=None):
+def capture_step(device, opt, warmup, warm, body, opt_body=None, debug_dot=None, keep_graph=False):
     """Capture one training iteration as a hipGraph: `warmup` calls of warm() -- real optimisation steps, which also size the arena and
     the scratch buffers -- on a side stream that waited for the current one, then body() under capture.  opt_body: the iteration is cut
     in two at the data-parallel gradient exchange and opt_body() (clip + Adam) becomes a second graph in the first one's pool.
     -> (graph, what body() returned, the captured gradients, the second graph or None, the gradients present between the two halves
-    or None).  The captured gradients are graph-pool tensors at the addresses the optimiser's table holds; the table is uploaded here."""
+    or None).  keep_graph: the hipGraph stays behind its executable (CUDAGraph.raw_cuda_graph()), for a caller that walks its nodes.
+    The captured gradients are graph-pool tensors at the addresses the optimiser's table holds; the table is uploaded here."""
     if warmup > 0:
         side = torch.cuda.Stream(device=device)
         side.wait_stream(torch.cuda.current_stream())
@@ -125,7 +133,7 @@ def capture_step(device, opt, warmup, warm, body, opt_body=None, debug_dot=None)
                 warm()
         torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
-    graph, graph_opt, between = torch.cuda.CUDAGraph(), None, None
+    graph, graph_opt, between = (torch.cuda.CUDAGraph(keep_graph=True) if keep_graph else torch.cuda.CUDAGraph()), None, None
     if debug_dot:                           # hipGraphDebugDotPrint of the captured step (nodes and edges), for diagnostics
         graph.enable_debug_mode()
     # thread_local, below: only THIS thread's calls are checked against the capture.  In the default (global) mode a
@@ -161,6 +169,47 @@ def _zeros(shape, dtype, device):
 
 
 ops.zeros_hook = _zeros       # the Chamfer backward's two gradient buffers come from the step's arena too
+ops.deterministic_hook = lambda: _DETERMINISTIC      # ... and its scatter takes the ordered form in a deterministic step
+
+
+def _empty(n, dtype, device):
+    """n elements of uninitialised scratch (at least one, so that the pointer is never null)"""
+    return torch.empty(max(int(n), 1), dtype=dtype, device=device)
+
+
+def _dw(dz, x, M, N, K, ldz, ldx, flags, det):
+    """dW (N, K) = dZ^T (M rows of N, stride ldz) . X (M rows of K, stride ldx).  det: pccx_linear_dw_det -- partial tiles per row slice,
+    folded in ascending slice index, WRITTEN into plain memory; otherwise atomics over the slices into a cleared arena slice."""
+    if det:
+        dW = torch.empty(N, K, device=dz.device, dtype=torch.float32)
+        ws = _empty(_lib.load().pccx_linear_dw_det_workspace_floats(M, N, K), torch.float32, dz.device)
+        _lib.call("pccx_linear_dw_det", dz.data_ptr(), x.data_ptr(), M, N, K, ldz, ldx, dW.data_ptr(), flags, ws.data_ptr(), _stream())
+        return dW
+    dW, _ = _zeros((N, K), torch.float32, dz.device)
+    _lib.call("pccx_linear_dw", dz.data_ptr(), x.data_ptr(), M, N, K, ldz, ldx, dW.data_ptr(), flags, _stream())
+    return dW
+
+
+def _col_det(mode, a, M, C, y=None, z=None, mean=None, rstd=None, f32_out=None):
+    """pccx_col_reduce_det over the rows of a -> the sums (modes 0, 1: what the BatchNorm entries take with flags 4 | 8) or None when
+    only f32_out (the bias gradient) is asked for"""
+    lib = _lib.load()
+    part = _empty(lib.pccx_col_reduce_det_doubles(M, C), torch.float64, a.device)
+    sums = _empty(lib.pccx_train_sums_doubles(C), torch.float64, a.device) if f32_out is None else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    _lib.call("pccx_col_reduce_det", mode, a.data_ptr(), ptr(y), ptr(z), ptr(mean), ptr(rstd), M, C, part.data_ptr(), ptr(sums),
+              ptr(f32_out), _stream())
+    return sums
+
+
+def _bias_grad(dz, M, N, det):
+    db = torch.empty(N, device=dz.device, dtype=torch.float32)                                             # written, not accumulated
+    if det:
+        _col_det(2, dz, M, N, f32_out=db)
+        return db
+    sums, pre = _sums(N, dz.device)
+    _lib.call("pccx_col_sum_w", dz.data_ptr(), M, N, sums.data_ptr(), db.data_ptr(), pre, _stream())
+    return db
 
 
 def _sums(C, device, private=False):
@@ -257,7 +306,8 @@ class LinearFn(torch.autograd.Function):
         ctx.save_for_backward(x, W2)
         ctx.has_bias, ctx.wshape = b is not None, W.shape
         ctx.flags = 2 if _AUTOCAST else 0
-        bn_in = _BN_OF.get(x.data_ptr()) if _FOLD_MOMENTS else None
+        ctx.det = det = _DETERMINISTIC
+        bn_in = _BN_OF.get(x.data_ptr()) if (_FOLD_MOMENTS and not det) else None
         ctx.bn_in = bn_in if (bn_in is not None and bn_in[0] == tuple(x.shape)) else None
         N, K = W2.shape
         # a few rows: a weight stream, not matrix work (csrc/train.hip); anything the skinny kernels cannot load takes the generic layer
@@ -280,7 +330,7 @@ class LinearFn(torch.autograd.Function):
                 if ctx.flags & 2:
                     out = out.bfloat16().float()
             return out
-        if want_moments and b is None and _FOLD_MOMENTS and x.is_cuda:
+        if want_moments and b is None and _FOLD_MOMENTS and x.is_cuda and not det:    # det: the BatchNorm reduces its input itself
             sums, pre = _sums(N, x.device, private=True)
             out = torch.empty(x.shape[0], N, device=x.device, dtype=torch.float32)
             _lib.call("pccx_linear_moments", x.data_ptr(), x.shape[0], K, x.stride(0), _packed(W2, False).data_ptr(), N, ctx.flags | pre,
@@ -296,7 +346,12 @@ class LinearFn(torch.autograd.Function):
         N, K = W2.shape
         M = x.shape[0]
         dx = None
-        if ctx.needs_input_grad[0] and ctx.skinny:
+        if ctx.needs_input_grad[0] and ctx.skinny and ctx.det:
+            dx = torch.empty(M, K, device=dz.device, dtype=torch.float32)                  # the n-chunks' partial rows, folded in order
+            ws = _empty(_lib.load().pccx_linear_skinny_dx_det_workspace_floats(M, N, K), torch.float32, dz.device)
+            _lib.call("pccx_linear_skinny_dx_det", dz.data_ptr(), M, N, dz.stride(0), W2.data_ptr(), K, ctx.flags, dx.data_ptr(), K,
+                      ws.data_ptr(), _stream())
+        elif ctx.needs_input_grad[0] and ctx.skinny:
             # split-K with fp32 atomics: under autocast the operands are rounded to bf16 as in the generic dX, the SUM is left in fp32 (the
             # generic path rounds its result to bf16 as well; the per-layer pin of tests/test_train_step.py holds either to one bf16 ulp)
             dx, _ = _zeros((M, K), torch.float32, dz.device)
@@ -304,9 +359,7 @@ class LinearFn(torch.autograd.Function):
         elif ctx.needs_input_grad[0] and ctx.wide:
             # dX^T (K, M) = W^T dZ^T: the weight-gradient kernel with W as its "dZ" (N rows of K) and dZ^T as its "x" (N rows of M)
             dzT = dz.t().contiguous()
-            dxT, _ = _zeros((K, M), torch.float32, dz.device)
-            _lib.call("pccx_linear_dw", W2.data_ptr(), dzT.data_ptr(), N, K, M, K, M, dxT.data_ptr(), ctx.flags, _stream())
-            dx = dxT.t().contiguous()
+            dx = _dw(W2, dzT, N, K, M, K, M, ctx.flags, ctx.det).t().contiguous()
         elif ctx.needs_input_grad[0] and ctx.bn_in is not None and K % 4 == 0:
             # x is the output of a train-mode BatchNorm-ReLU: dX is that layer's dY, and the GEMM's epilogue accumulates the two column
             # sums its backward needs from the rows it has just produced (13 col_reduce4<1> launches per step otherwise)
@@ -318,13 +371,8 @@ class LinearFn(torch.autograd.Function):
             _BWD_SUMS[dx.data_ptr()] = (tuple(dx.shape), sums, dx, dx._version)
         elif ctx.needs_input_grad[0]:
             dx = _linear_raw(dz, _packed(W2, True), None, K, N, ctx.flags)                                       # dX = dZ . W
-        dW, _ = _zeros(tuple(W2.shape), torch.float32, dz.device)
-        _lib.call("pccx_linear_dw", dz.data_ptr(), x.data_ptr(), M, N, K, N, x.stride(0), dW.data_ptr(), ctx.flags, _stream())
-        db = None
-        if ctx.has_bias:
-            db = torch.empty(N, device=dz.device, dtype=torch.float32)                                             # written, not accumulated
-            sums, pre = _sums(N, dz.device)
-            _lib.call("pccx_col_sum_w", dz.data_ptr(), M, N, sums.data_ptr(), db.data_ptr(), pre, _stream())
+        dW = _dw(dz, x, M, N, K, N, x.stride(0), ctx.flags, ctx.det)
+        db = _bias_grad(dz, M, N, ctx.det) if ctx.has_bias else None
         return dx, dW.view(ctx.wshape), db, None
 
 
@@ -338,8 +386,11 @@ class BnReluFn(torch.autograd.Function):
         mean = torch.empty(Cc, device=z.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
         y = torch.empty_like(z)
+        ctx.det = _DETERMINISTIC
         mom = _parked(_MOMENTS, z)
-        if mom is not None:
+        if ctx.det:
+            sums, pre = _col_det(0, z, M, Cc), 4 | 8          # ordered moments of z; the folded epilogue is never used in this mode
+        elif mom is not None:
             sums, pre = mom, 4 | 8                   # the producing GEMM's epilogue accumulated the moments: no reduction pass here
         else:
             sums, pre = _sums(Cc, z.device)
@@ -350,7 +401,7 @@ class BnReluFn(torch.autograd.Function):
         if _BN_COUNTED is None:
             bn.num_batches_tracked += 1             # outside forward_train (which advances every counter of the model in one launch)
         ctx.save_for_backward(z, y, mean, rstd, gamma)
-        if _FOLD_MOMENTS:
+        if _FOLD_MOMENTS and not ctx.det:
             _BN_OF[y.data_ptr()] = (tuple(y.shape), y, z, mean, rstd)
         return y
 
@@ -362,7 +413,9 @@ class BnReluFn(torch.autograd.Function):
         dz = torch.empty_like(z)
         gg, gb = torch.empty_like(gamma), torch.empty_like(gamma)                    # written by the apply kernel's first workgroup
         bs = _parked(_BWD_SUMS, dy)
-        if bs is not None:
+        if ctx.det:
+            sums, pre = _col_det(1, dy, M, Cc, y, z, mean, rstd), 4 | 8
+        elif bs is not None:
             sums, pre = bs, 4 | 8                    # the GEMM that produced dY accumulated the two sums in its epilogue
         else:
             sums, pre = _sums(Cc, z.device)
@@ -418,6 +471,7 @@ class GatherFn(torch.autograd.Function):
     def forward(ctx, feats, idx):
         ctx.save_for_backward(idx)
         ctx.shape = feats.shape
+        ctx.det = _DETERMINISTIC
         return ops.index_points(feats, idx)
 
     @staticmethod
@@ -426,6 +480,12 @@ class GatherFn(torch.autograd.Function):
         B, N, Cc = ctx.shape
         dg = dg.contiguous()
         M = idx[0].numel()
+        if ctx.det:                                          # every feature row = its contributions in ascending source position, written
+            df = torch.empty(B, N, Cc, device=dg.device, dtype=torch.float32)
+            ws = _empty(_lib.load().pccx_scatter_add_ordered_workspace_ints(B, M, N), torch.int32, dg.device)
+            _lib.call("pccx_scatter_add_ordered", dg.data_ptr(), Cc, idx.contiguous().data_ptr(), 0, B, M, N, Cc, df.data_ptr(), ws.data_ptr(),
+                      _stream())
+            return df, None
         df, _ = _zeros((B, N, Cc), torch.float32, dg.device)
         _lib.call("pccx_gather_backward_acc", dg.data_ptr(), Cc, idx.contiguous().data_ptr(), B, M, N, Cc, df.data_ptr(), 4, _stream())
         return df, None
@@ -461,7 +521,12 @@ class SmoothL1Fn(torch.autograd.Function):
     def forward(ctx, a, b):
         a, b = a.contiguous(), b.contiguous()
         val = torch.empty(1, device=a.device, dtype=torch.float64)
-        _lib.call("pccx_smooth_l1", a.data_ptr(), b.data_ptr(), a.numel(), 0.0, val.data_ptr(), None, _stream())
+        ctx.det = _DETERMINISTIC
+        if ctx.det:
+            part = _empty(_lib.load().pccx_smooth_l1_det_doubles(a.numel()), torch.float64, a.device)
+            _lib.call("pccx_smooth_l1_det", a.data_ptr(), b.data_ptr(), a.numel(), 0.0, part.data_ptr(), val.data_ptr(), None, _stream())
+        else:
+            _lib.call("pccx_smooth_l1", a.data_ptr(), b.data_ptr(), a.numel(), 0.0, val.data_ptr(), None, _stream())
         ctx.save_for_backward(a, b)
         return (val / a.numel()).float().reshape(())
 
@@ -470,6 +535,11 @@ class SmoothL1Fn(torch.autograd.Function):
         a, b = ctx.saved_tensors
         val = torch.empty(1, device=a.device, dtype=torch.float64)
         grad = torch.empty_like(a)
+        if ctx.det:
+            part = _empty(_lib.load().pccx_smooth_l1_det_doubles(a.numel()), torch.float64, a.device)
+            _lib.call("pccx_smooth_l1_det", a.data_ptr(), b.data_ptr(), a.numel(), float(g) / a.numel(), part.data_ptr(), val.data_ptr(),
+                      grad.data_ptr(), _stream())
+            return grad, None
         _lib.call("pccx_smooth_l1", a.data_ptr(), b.data_ptr(), a.numel(), float(g) / a.numel(), val.data_ptr(), grad.data_ptr(),
                   _stream())
         return grad, None
@@ -681,7 +751,11 @@ class Adam:
             table = self._table
             table[:len(live)].copy_(torch.from_numpy(rows))          # pageable source: the copy has completed when this returns
         acc = None
-        if max_norm is not None:
+        if max_norm is not None and _DETERMINISTIC:
+            acc = torch.empty(1, device=dev, dtype=torch.float64)     # the workgroups' sums of squares, added in workgroup order
+            part = _empty(_lib.load().pccx_sumsq_multi_det_doubles(first), torch.float64, dev)
+            _lib.call("pccx_sumsq_multi_det", table.data_ptr(), len(live), first, part.data_ptr(), acc.data_ptr(), _stream())
+        elif max_norm is not None:
             acc, _ = _zeros(1, torch.float64, dev)
             _lib.call("pccx_sumsq_multi", table.data_ptr(), len(live), first, acc.data_ptr(), _stream())
         _lib.call("pccx_adam_multi", table.data_ptr(), len(live), first, acc.data_ptr() if acc is not None else None,
@@ -774,13 +848,14 @@ class GraphedTrainStep:
     step); results are the same either way (tests/test_train_step.py)."""
 
     def __init__(self, model, opt, batch_x, starts, lam=1.0, grad_clip=1.0, loss_type="chamfer", autocast=False, warmup=2,
-                 data_parallel=False, debug_dot=None, prefetch=False):
+                 data_parallel=False, debug_dot=None, prefetch=False, deterministic=False, keep_graph=False):
+        _check_det_dp(deterministic, data_parallel, "GraphedTrainStep")
         if loss_type != "chamfer":
             raise _lib.PccxError("GraphedTrainStep: loss_type='chamfer' (what train_pppe_pcd_ae.py:48 builds) is the captured loss; "
                                  "the smooth-L1 backward still reads its upstream gradient on the host")
         dev = batch_x.device
         self.model, self.opt, self.grad_clip, self.loss_type, self.autocast = model, opt, grad_clip, loss_type, autocast
-        self.data_parallel = bool(data_parallel)
+        self.data_parallel, self.deterministic = bool(data_parallel), bool(deterministic)
         self.arena = StepArena()            # this step's accumulation buffers: sized by the warm-up iterations, cleared by the graph's first node
         opt.make_capturable(dev)
         as_dev = lambda s_: torch.as_tensor(s_).to(device=dev, dtype=torch.int32).contiguous().clone()
@@ -806,10 +881,10 @@ class GraphedTrainStep:
             self._sel_done, self._copied = torch.cuda.Event(), torch.cuda.Event()
             self._copied.record(torch.cuda.current_stream())
         halves = (self._fwd_bwd, self._opt_step) if self.data_parallel else (self._body, None)
-        self.graph, self.out, self._grads, self.graph_opt, self._dp_grads = capture_step(dev, opt, warmup, self._body, *halves, debug_dot)
+        self.graph, self.out, self._grads, self.graph_opt, self._dp_grads = capture_step(dev, opt, warmup, self._body, *halves, debug_dot, keep_graph)
 
     def _fwd_bwd(self):
-        with step_scope(self.x.device, self.arena, self.autocast, self.opt.params, end=False) as forward_done:
+        with step_scope(self.x.device, self.arena, self.autocast, self.opt.params, end=False, deterministic=self.deterministic) as forward_done:
             coarse, fine, cond, y_q = forward_train(self.model, self.x, self.starts, tables=self.tables)
             fbpp = estimate_bits_per_point(self.model, y_q, cond.detach())
             loss, dist, rate = rd_loss(fine, self.x, fbpp, self.lam, self.loss_type)
@@ -818,7 +893,7 @@ class GraphedTrainStep:
         return loss.detach(), dist, rate
 
     def _opt_step(self):
-        with step_scope(self.x.device, self.arena, begin=False):
+        with step_scope(self.x.device, self.arena, begin=False, deterministic=self.deterministic):
             self.opt.step(max_norm=self.grad_clip)
 
     def _body(self):
@@ -909,12 +984,25 @@ class GraphedTrainStep:
         return tuple(float(t) for t in self.out) if sync else self.out
 
 
-def train_step(model, opt, batch_x, starts, lam=1.0, grad_clip=1.0, data_parallel=False, loss_type="chamfer", autocast=False):
+def _check_det_dp(deterministic, data_parallel, who):
+    if deterministic and data_parallel:
+        raise _lib.PccxError(f"{who}: deterministic=True with data_parallel=True is not built -- the order in which the gradient all-reduce "
+                             "adds the ranks' gradients is RCCL's, not this library's (DESIGN 4.4c); the deterministic mode is one GPU")
+
+
+def train_step(model, opt, batch_x, starts, lam=1.0, grad_clip=1.0, data_parallel=False, loss_type="chamfer", autocast=False,
+               deterministic=False):
     """One iteration of train_one_epoch (train_pppe_pcd_ae.py:184-226).  ``opt`` covers ae + prob
     parameters as the reference's optimizer does; returns (loss, dist, rate) as python floats.
     data_parallel=True averages the gradients over the ranks of the default process group (bucketed
-    all-reduce, dist.allreduce_mean_) between backward and the clipped Adam step."""
-    with step_scope(batch_x.device, None, autocast, opt.params) as forward_done:
+    all-reduce, dist.allreduce_mean_) between backward and the clipped Adam step.  deterministic=True: every reduction of the step in
+    a fixed order, one GPU only."""
+    _check_det_dp(deterministic, data_parallel, "train_step")
+    if deterministic:
+        # Adam's bias corrections from the DEVICE state, as the captured step has them (and as IpdaeTrainer does under the switch): one
+        # arithmetic for the eager and the replayed deterministic step
+        opt.make_capturable(batch_x.device)
+    with step_scope(batch_x.device, None, autocast, opt.params, deterministic=deterministic) as forward_done:
         coarse, fine, cond, y_q = forward_train(model, batch_x, starts)
         fbpp = estimate_bits_per_point(model, y_q, cond.detach())
         loss, dist, rate = rd_loss(fine.float(), batch_x.float(), fbpp, lam, loss_type)      # :205 casts back to fp32 for the loss

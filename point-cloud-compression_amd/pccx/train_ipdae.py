@@ -37,6 +37,7 @@ class LinearReluFn(torch.autograd.Function):
         W2 = W.reshape(W.shape[0], -1).contiguous()
         N, K = W2.shape
         ctx.flags = 2 if train._AUTOCAST else 0
+        ctx.det = train._DETERMINISTIC
         y = train._linear_raw(x, train._packed(W2, False), b, N, K, ctx.flags | 1)
         ctx.save_for_backward(x, W2, y)
         ctx.has_bias, ctx.wshape = b is not None, W.shape
@@ -50,13 +51,8 @@ class LinearReluFn(torch.autograd.Function):
         dz = torch.empty_like(y)
         _lib.call("pccx_relu_backward", dy.contiguous().data_ptr(), y.data_ptr(), y.numel(), dz.data_ptr(), train._stream())
         dx = train._linear_raw(dz, train._packed(W2, True), None, K, N, ctx.flags) if ctx.needs_input_grad[0] else None
-        dW, _ = train._zeros(tuple(W2.shape), torch.float32, dz.device)
-        _lib.call("pccx_linear_dw", dz.data_ptr(), x.data_ptr(), M, N, K, N, x.stride(0), dW.data_ptr(), ctx.flags, train._stream())
-        db = None
-        if ctx.has_bias:
-            db = torch.empty(N, device=dz.device, dtype=torch.float32)
-            sums, pre = train._sums(N, dz.device)
-            _lib.call("pccx_col_sum_w", dz.data_ptr(), M, N, sums.data_ptr(), db.data_ptr(), pre, train._stream())
+        dW = train._dw(dz, x, M, N, K, N, x.stride(0), ctx.flags, ctx.det)
+        db = train._bias_grad(dz, M, N, ctx.det) if ctx.has_bias else None
         return dx, dW.view(ctx.wshape), db
 
 
@@ -183,12 +179,12 @@ class IpdaeTrainer:
     rate term switched on at rate_loss_enable_step (:218-221) and the learning-rate decay (:250-254)."""
 
     def __init__(self, ae, prob, N=8192, N0=1024, ALPHA=2, K=256, lr=0.0005, lamda=1e-6, rate_loss_enable_step=40000, lr_decay=0.1,
-                 lr_decay_steps=60000, autocast=False):
+                 lr_decay_steps=60000, autocast=False, deterministic=False):
         self.ae, self.prob = ae, prob
         self.N, self.N0, self.K, self.S = int(N), int(N0), int(K), int(N) * int(ALPHA) // int(K)
         self.lamda, self.rate_loss_enable_step = float(lamda), int(rate_loss_enable_step)
         self.lr, self.lr_decay, self.lr_decay_steps = float(lr), float(lr_decay), int(lr_decay_steps)
-        self.autocast = bool(autocast)
+        self.autocast, self.deterministic = bool(autocast), bool(deterministic)
         self.opt = train.Adam(list(ae.parameters()) + list(prob.parameters()), lr=self.lr)
         self.global_step = 0
 
@@ -198,7 +194,11 @@ class IpdaeTrainer:
         if batch_x.dim() != 3 or batch_x.shape[1] != self.N or batch_x.shape[2] != 3:
             raise _lib.PccxError(f"train_ipdae: batch must be (B, {self.N}, 3), got {tuple(batch_x.shape)}")
         lam = 0.0 if self.global_step < self.rate_loss_enable_step else self.lamda    # :218-221
-        with train.step_scope(batch_x.device, None, self.autocast, self.opt.params) as forward_done:     # :173 optimizer.zero_grad()
+        if self.deterministic:
+            # Adam's bias corrections from the DEVICE state, as the captured step has them (make_capturable): the host's powf and the
+            # device's running double product differ in the last bit, and the eager and the replayed step are to give the same bits
+            self.opt.make_capturable(batch_x.device)
+        with train.step_scope(batch_x.device, None, self.autocast, self.opt.params, deterministic=self.deterministic) as forward_done:     # :173 optimizer.zero_grad()
             loss, fbpp, bpp = forward_loss(self.ae, self.prob, batch_x, starts, lam, self.S, self.K, self.N, self.N0)
             forward_done()
             loss.backward()                                                           # :229
@@ -209,9 +209,9 @@ class IpdaeTrainer:
             self.opt.set_lr(self.lr)
         return dict(loss=float(loss.detach()), fbpp=float(fbpp.detach()), bpp=float(bpp.detach()))
 
-    def graphed(self, batch_x, starts, warmup=2):
+    def graphed(self, batch_x, starts, warmup=2, keep_graph=False):
         """-> GraphedIpdaeStep over this trainer's models and optimizer (the warm-up iterations are real steps on batch_x)"""
-        return GraphedIpdaeStep(self, batch_x, starts, warmup)
+        return GraphedIpdaeStep(self, batch_x, starts, warmup, keep_graph)
 
 
 class GraphedIpdaeStep:
@@ -221,7 +221,7 @@ class GraphedIpdaeStep:
     step lives in buffers the graph reads: the batch, the start indices, lambda (0 until rate_loss_enable_step) and Adam's lr / bias
     corrections (Adam.make_capturable).  Shapes are fixed at construction."""
 
-    def __init__(self, trainer, batch_x, starts, warmup=2):
+    def __init__(self, trainer, batch_x, starts, warmup=2, keep_graph=False):
         tr = self.tr = trainer
         dev = batch_x.device
         self.arena = train.StepArena()
@@ -235,7 +235,7 @@ class GraphedIpdaeStep:
             self._set_lam()
             self.warm_out = self._body()                             # (loss, fbpp, bpp) of the last warm-up iteration, device scalars
             self._advance()
-        self.graph, self.out, self._grads, _, _ = train.capture_step(dev, tr.opt, warmup, warm, self._body)
+        self.graph, self.out, self._grads, _, _ = train.capture_step(dev, tr.opt, warmup, warm, self._body, keep_graph=keep_graph)
 
     def _set_lam(self):
         self.lam.fill_(0.0 if self.tr.global_step < self.tr.rate_loss_enable_step else self.tr.lamda)
@@ -249,7 +249,7 @@ class GraphedIpdaeStep:
 
     def _body(self):
         tr = self.tr
-        with train.step_scope(self.x.device, self.arena, tr.autocast, tr.opt.params) as forward_done:
+        with train.step_scope(self.x.device, self.arena, tr.autocast, tr.opt.params, deterministic=tr.deterministic) as forward_done:
             loss, fbpp, bpp = forward_loss(tr.ae, tr.prob, self.x, self.starts, self.lam, tr.S, tr.K, tr.N, tr.N0)
             forward_done()
             loss.backward()
