@@ -8,11 +8,16 @@
 
 Same constructor arguments and state_dict keys as the reference (torch modules are parameter
 containers only).  Every layer is a HIP kernel behind the C ABI: selection ops from ops.py, the
-Conv/Linear stacks through pccx_linear with eval-mode BatchNorm folded into weight and bias at pack
-time, neighbour max through pccx_group_max.  Activations are kept channels-last ((rows, C)), so the
-reference's permutes disappear; torch only concatenates and reshapes buffers.
-These families are correctness-first (layer by layer through HBM); the fused, tuned path is the
-IPDAE codec in models.py / codec.py.
+Conv/Linear stacks with eval-mode BatchNorm folded into weight and bias at pack time.  Activations
+are kept channels-last ((rows, C)), so the reference's permutes disappear; torch only concatenates
+and reshapes buffers.
+
+PPPF_AE is a tuned path: its Conv/Linear stacks run on operand planes (csrc/planes.hip) in
+one of three arithmetics -- f16x2 or bf16x3 planes, or exact-fp32 rows -- each stack on its SOURCE rows
+only, in one chain kernel where one fits.  The file states that machinery once: _PLANES (the entry points
+of the two planes arithmetics), Stack (the packed layers and every operand derived from them) and
+run_planes (the one stack runner).  The pppe PointCloudAE forward is layer by layer on fp32 rows
+(pccx_linear / pccx_linear_b3).
 """
 import math
 
@@ -22,6 +27,43 @@ import torch.nn as nn
 
 from . import _lib, ops
 from .ops import _stream, stage
+
+
+def _arith(matmul=None):
+    """The arithmetic asked for: a layer's own, else pccx.DEFAULT_MATMUL read at call time (tests and bench.py switch it between calls)."""
+    from . import DEFAULT_MATMUL
+    return matmul or DEFAULT_MATMUL
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+# The two planes arithmetics (the host mirror of PgArith<P> in csrc/planes.hip): the size function and the entry points by role.  An
+# f16x2 entry point takes its bf16x3 sibling's arguments plus scale arguments in front of `out`: _pcall() puts them there.
+_PLANES = {
+    "bf16x3": dict(floats="pccx_planes_floats", operand="pccx_group_planes", gemm="pccx_planes_gemm", gemm_gather="pccx_planes_gemm_gather",
+                   chain4="pccx_planes_chain4", chain4_gather="pccx_planes_chain4_gather", rows_affine="pccx_rows_affine_planes"),
+    "f16x2": dict(floats="pccx_planes_floats_h2", operand="pccx_group_planes_h2", gemm="pccx_planes_gemm_h2", gemm_gather="pccx_planes_gemm_gather_h2",
+                  chain4="pccx_planes_chain4_h2", chain4_gather="pccx_planes_chain4_gather_h2", rows_affine="pccx_rows_affine_planes_h2",
+                  member_max="pccx_planes_gemm_h2_member_max"),
+}
+
+
+def _pcall(ar, role, args, scales, out):
+    """The entry point of `role` in the arithmetic `ar`: (*args, *scales [f16x2 only], *out, stream)."""
+    name = _PLANES[ar].get(role)
+    if name is None:
+        raise _lib.PccxError(f"families: no {role} entry point in the {ar} arithmetic")
+    _lib.call(name, *args, *(scales if ar == "f16x2" else ()), *out, _stream())
+
+
+def _planes_out(ar, M, N, epilogue, group, device):
+    """What a planes kernel writes for M input rows: epilogue 0 -> the planes of the (M, N) output in `ar`, 1 -> fp32 rows (M, N),
+    2 -> (M // group, N) maxima over `group` consecutive rows."""
+    if epilogue == 0:
+        return torch.empty(getattr(_lib.load(), _PLANES[ar]["floats"])(M, N), device=device, dtype=torch.float32)
+    return torch.empty(M if epilogue == 1 else M // group, N, device=device, dtype=torch.float32)
 
 
 # ---- f16x2 scales (csrc/planes.hip, "the same layers in the f16x2 arithmetic"; the rules of csrc/pack_h2.hip) -------------------------
@@ -56,7 +98,8 @@ def ibp_layer(W, b, lo, hi, relu):
 def h2_prepare_stack(stack, lo, hi):
     """Give every layer of a Conv/Linear stack its f16x2 operands for inputs within [lo, hi] per channel (the stack's NORMALISED input:
     magnitudes <= 1): sigma_l from the interval bound of the layer's input, tau_l from its weights, the two fp16 planes of tau W as
-    the GEMM's weight stream, the bias as sigma tau b.  Returns the bounds of the stack's output."""
+    the GEMM's weight stream, the bias as sigma tau b.  Returns the bounds of the stack's output (a Stack keeps them: they say it is
+    prepared)."""
     lib = _lib.load()
     lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
     for l in stack:
@@ -68,6 +111,9 @@ def h2_prepare_stack(stack, lo, hi):
         _lib.call("pccx_pack_planes_gemm_h2", wp2.data_ptr(), l.N, l.K, ws2.data_ptr(), _stream())
         l.h2 = dict(sig=sig, tau=tau, ws=ws2, b=(l.b * float(sig * tau)).contiguous())
         lo, hi = ibp_layer(l.W_host, l.b_host, lo, hi, l.relu)
+    if isinstance(stack, Stack):
+        stack.derived.pop(("chain4", "f16x2"), None)
+        stack.derived["h2"] = (lo, hi)
     return lo, hi
 
 
@@ -92,34 +138,12 @@ class FoldedLinear:
         self.matmul, self.wp3, self.ws3 = matmul, None, None
 
     def mode(self):
-        from . import DEFAULT_MATMUL
-        m = self.matmul or DEFAULT_MATMUL
+        m = _arith(self.matmul)
         return "bf16x3" if m == "f16x2" else m              # a layer called by itself on fp32 rows has no f16x2 form: bf16x3
 
     def planes_mode(self):
         """the arithmetic of the layer as part of a planes stack: "f16x2" when asked for (the stacks of PPPF_AE.forward), else mode()"""
-        from . import DEFAULT_MATMUL
-        return self.matmul or DEFAULT_MATMUL
-
-    def planes_h2(self, pin, M, epilogue=0, group=0, sig_next=None, dyn=None, amax=None, member=None):
-        """planes() in the f16x2 arithmetic (h2_prepare_stack first): pin = f16x2 planes of sigma * input.  epilogue 0 -> f16x2 planes of
-        sig_next * output; 1 / 2 -> fp32 rows / group maxima, un-scaled (and times dyn[1]); amax: 8 floats the row epilogue folds the
-        largest |value| into.  member (M bytes, with epilogue 2): the maxima run over the rows marked 1 only."""
-        h = self.h2
-        scale = (float(sig_next) if epilogue == 0 else 1.0) / (h["sig"] * h["tau"])
-        if member is not None:
-            out = torch.empty(M // group, self.N, device=pin.device, dtype=torch.float32)
-            _lib.call("pccx_planes_gemm_h2_member_max", pin.data_ptr(), M, self.K, h["ws"].data_ptr(), h["b"].data_ptr(), self.N, self.relu, group,
-                      member.data_ptr(), scale, dyn.data_ptr() if dyn is not None else None, out.data_ptr(), self.N, _stream())
-            return out
-        if epilogue == 0:
-            out = torch.empty(_lib.load().pccx_planes_floats_h2(M, self.N), device=pin.device, dtype=torch.float32)
-        else:
-            out = torch.empty(M if epilogue == 1 else M // group, self.N, device=pin.device, dtype=torch.float32)
-        _lib.call("pccx_planes_gemm_h2", pin.data_ptr(), M, self.K, h["ws"].data_ptr(), h["b"].data_ptr(), self.N, self.relu, epilogue, group,
-                  scale, dyn.data_ptr() if dyn is not None else None, amax.data_ptr() if amax is not None else None, out.data_ptr(), self.N,
-                  _stream())
-        return out
+        return _arith(self.matmul)
 
     def _planes3(self):
         if self.wp3 is None:
@@ -133,43 +157,90 @@ class FoldedLinear:
             _lib.call("pccx_pack_planes_gemm", self._planes3().data_ptr(), self.N, self.K, self.ws3.data_ptr(), _stream())
         return self.ws3
 
-    def planes_gather(self, src, C, idx, epilogue=0, group=0):
-        """planes() on rows gathered inside the kernel: src (B, N, ldp) from padded_rows(), idx (B, M, ns) int64 (-1 -> row 0)."""
-        B, Mq, ns = idx.shape
-        rows = B * Mq * ns
-        self._stream3()
-        if epilogue == 0:
-            out = torch.empty(_lib.load().pccx_planes_floats(rows, self.N), device=src.device, dtype=torch.float32)
+    def planes(self, x, M, epilogue=0, group=0, idx=None, member=None, ar="bf16x3", sig_next=None, dyn=None, amax=None):
+        """The layer on an activation kept in planes (csrc/planes.hip): x = the planes of the (M, K) input in the arithmetic `ar`, or,
+        with idx (B, Mq, ns) int64 (-1 -> row 0), the source rows (B, N, ldp) of padded_rows() that the kernel gathers itself.
+        epilogue 0 -> planes of the (M, N) output, 1 -> fp32 rows (M, N), 2 -> (M // group, N) max over `group` consecutive rows; member
+        (M bytes, epilogue 2, f16x2): the maxima run over the rows marked 1 only.
+        f16x2 (h2_prepare_stack first): x holds sigma * input; epilogue 0 writes sig_next * output, 1 / 2 write un-scaled values (times
+        dyn[1]); amax: 8 floats the row epilogue folds the largest |value| into."""
+        if ar == "f16x2":
+            h = self.h2
+            ws, b, sig_in = h["ws"], h["b"], [float(h["sig"])]
+            scales = [(float(sig_next) if epilogue == 0 else 1.0) / (h["sig"] * h["tau"]), _ptr(dyn), _ptr(amax)]
         else:
-            out = torch.empty(rows if epilogue == 1 else rows // group, self.N, device=src.device, dtype=torch.float32)
-        _lib.call("pccx_planes_gemm_gather", src.data_ptr(), src.shape[2], idx.data_ptr(), Mq * ns, src.shape[1], rows, C,
-                  self.ws3.data_ptr(), self.b.data_ptr(), self.N, self.relu, epilogue, group, out.data_ptr(), self.N, _stream())
-        return out
-
-    def planes(self, pin, M, epilogue=0, group=0):
-        """The layer on an activation kept in planes (csrc/planes.hip; bf16x3 only): pin = planes of the (M, K) input.
-        epilogue 0 -> planes of the (M, N) output, 1 -> fp32 rows (M, N), 2 -> (M // group, N) max over `group` consecutive rows."""
-        self._stream3()
-        if epilogue == 0:
-            out = torch.empty(_lib.load().pccx_planes_floats(M, self.N), device=pin.device, dtype=torch.float32)
+            ws, b, sig_in, scales = self._stream3(), self.b, [], []
+        out = _planes_out(ar, M, self.N, epilogue, group, x.device)
+        layer, to = [ws.data_ptr(), b.data_ptr(), self.N, self.relu], [out.data_ptr(), self.N]
+        if member is not None:
+            _pcall(ar, "member_max", [x.data_ptr(), M, self.K] + layer + [group, member.data_ptr()], scales[:2], to)
+        elif idx is not None:
+            _pcall(ar, "gemm_gather", [x.data_ptr(), x.shape[2], idx.data_ptr(), idx.shape[1] * idx.shape[2], x.shape[1], M, self.K] + layer +
+                   [epilogue, group], sig_in + scales, to)
         else:
-            out = torch.empty(M if epilogue == 1 else M // group, self.N, device=pin.device, dtype=torch.float32)
-        _lib.call("pccx_planes_gemm", pin.data_ptr(), M, self.K, self.ws3.data_ptr(), self.b.data_ptr(), self.N, self.relu, epilogue,
-                  group, out.data_ptr(), self.N, _stream())
+            _pcall(ar, "gemm", [x.data_ptr(), M, self.K] + layer + [epilogue, group], scales, to)
         return out
 
     def __call__(self, x):
         """x (M,K) f32 contiguous on the GPU -> (M,N)."""
-        from . import DEFAULT_MATMUL
         M = x.shape[0]
         out = torch.empty(M, self.N, device=x.device, dtype=torch.float32)
-        if self.mode() == "bf16x3":
-            _lib.call("pccx_linear_b3", x.data_ptr(), M, self.K, x.stride(0), self._planes3().data_ptr(), self.b.data_ptr(), self.N,
-                      self.relu, out.data_ptr(), self.N, _stream())
-            return out
-        _lib.call("pccx_linear", x.data_ptr(), M, self.K, x.stride(0), self.wp.data_ptr(), self.b.data_ptr(), self.N,
-                  self.relu, out.data_ptr(), self.N, _stream())
+        b3 = self.mode() == "bf16x3"
+        _lib.call("pccx_linear_b3" if b3 else "pccx_linear", x.data_ptr(), M, self.K, x.stride(0), (self._planes3() if b3 else self.wp).data_ptr(),
+                  self.b.data_ptr(), self.N, self.relu, out.data_ptr(), self.N, _stream())
         return out
+
+
+class Stack:
+    """The packed layers of one Conv/Linear stack and, in one dict, every operand derived from them, built the first time it is needed:
+    the chain4 weight stream per arithmetic (with the f16x2 chain's five scales), the wide-chain stream, and the output bounds
+    h2_prepare_stack leaves.  Indexing, len and iteration are the layer list's; a slice is a Stack of its own.  The owner drops the
+    Stack (PPPF_AE._packed = None) and everything derived goes with it."""
+
+    def __init__(self, layers):
+        self.layers, self.derived = list(layers), {}
+
+    def __len__(self):
+        return len(self.layers)
+
+    def __iter__(self):
+        return iter(self.layers)
+
+    def __getitem__(self, i):
+        return Stack(self.layers[i]) if isinstance(i, slice) else self.layers[i]
+
+    def rows(self, x):
+        """layer by layer on fp32 rows x (M, K) (pccx_linear / pccx_linear_b3) -> (M, N_last)"""
+        for layer in self.layers:
+            x = layer(x)
+        return x
+
+    def chain4(self, ar):
+        """the chain4 kernels' weight stream in `ar`, the f16x2 chain's five scales (None for bf16x3) and the (bias, width) arguments"""
+        h2 = ar == "f16x2"
+        if ("chain4", ar) not in self.derived:
+            if h2:
+                h = [l.h2 for l in self.layers]
+                sc = np.array([h[0]["sig"]] + [h[i]["sig"] / (h[i - 1]["sig"] * h[i - 1]["tau"]) for i in (1, 2, 3)] +
+                              [1.0 / (h[3]["sig"] * h[3]["tau"])], dtype=np.float32)
+                self.derived["chain4", ar] = torch.cat([x["ws"] for x in h]), sc
+            else:
+                self.derived["chain4", ar] = torch.cat([l._stream3() for l in self.layers]), None
+        ws, sc = self.derived["chain4", ar]
+        a = []
+        for l in self.layers:
+            a += [(l.h2["b"] if h2 else l.b).data_ptr(), l.N]
+        return ws, sc, a
+
+    def wide3(self):
+        """the weight stream of pccx_planes_chain_wide (the first three layers)"""
+        if "wide3" not in self.derived:
+            l0, l1, l2 = self.layers[:3]
+            ws = torch.empty(_lib.load().pccx_planes_chain_wide_weight_floats(l0.K), device=l0.wp.device, dtype=torch.float32)
+            _lib.call("pccx_pack_planes_chain_wide", l0._planes3().data_ptr(), l1._planes3().data_ptr(), l2._planes3().data_ptr(),
+                      l0.K, l0.N, l1.N, l2.N, ws.data_ptr(), _stream())
+            self.derived["wide3"] = ws
+        return self.derived["wide3"]
 
 
 def cat_rows(parts):
@@ -189,29 +260,31 @@ def cat_rows(parts):
     return buf[:, :C]
 
 
-def group_planes(feats, xyz, idx):
-    """index_points(feats, idx) ++ index_points(xyz, idx) (pointnet_sa_module.py:73-83; -1 -> row 0) as the planes of the first
-    layer's operand.  feats (B,N,C) channels-last or None, xyz (B,N,3) or None, idx (B,M,ns) int64.  Returns (planes, rows)."""
-    B, Mq, ns = idx.shape
-    rows = B * Mq * ns
-    f0 = feats.contiguous() if feats is not None else None
-    f1 = xyz.contiguous() if xyz is not None else None
-    C0 = int(f0.shape[-1]) if f0 is not None else 0
-    C1 = int(f1.shape[-1]) if f1 is not None else 0
-    n_src = int((f0 if f0 is not None else f1).shape[1])
-    idx = idx.contiguous()
-    out = torch.empty(_lib.load().pccx_planes_floats(rows, C0 + C1), device=idx.device, dtype=torch.float32)
-    _lib.call("pccx_group_planes", f0.data_ptr() if f0 is not None else None, C0, C0, f1.data_ptr() if f1 is not None else None, C1, C1,
-              idx.data_ptr(), rows, Mq * ns, n_src, out.data_ptr(), _stream())
+def _rows2d(p):
+    """(.., C) -> (2-D rows, C, row stride); rows that are 2-D already keep their row stride (cat_rows() pads it)"""
+    if p is None:
+        return None, 0, 0
+    if p.dim() != 2:
+        p = p.reshape(-1, p.shape[-1]).contiguous()
+    return p, int(p.shape[1]), int(p.stride(0))
+
+
+def group_planes(feats, xyz=None, idx=None, ar="bf16x3", sig=None, dyn=None):
+    """[feats | xyz] rows as the operand planes of a stack's first layer, in the arithmetic `ar` (f16x2: times sig * dyn[0]).  Either
+    part may be None.  With idx (B, M, ns) int64: index_points(feats, idx) ++ index_points(xyz, idx) (pointnet_sa_module.py:73-83; -1 ->
+    row 0) of feats (B, N, C) channels-last and xyz (B, N, 3).  Without: every row as it stands, fp32 rows (M, K) (row stride >= K)
+    or (B, N, C) tables (:83 features first, xyz last -- the concatenated rows never exist).  Returns (planes, rows)."""
+    n_src = int((feats if feats is not None else xyz).shape[1]) if idx is not None else 1
+    (f0, C0, ld0), (f1, C1, ld1) = _rows2d(feats), _rows2d(xyz)
+    if idx is not None:
+        idx = idx.contiguous()
+        rows, per_batch = idx.numel(), idx.shape[1] * idx.shape[2]
+    else:
+        rows, per_batch = int((f0 if f0 is not None else f1).shape[0]), 1
+    out = _planes_out(ar, rows, C0 + C1, 0, 0, (f0 if f0 is not None else f1).device)
+    _pcall(ar, "operand", [_ptr(f0), C0, ld0, _ptr(f1), C1, ld1, _ptr(idx), rows, per_batch, n_src],
+           [float(sig) if sig is not None else None, _ptr(dyn)], [out.data_ptr()])
     return out, rows
-
-
-def rows_planes(x):
-    """fp32 rows (M, K) (row stride >= K) -> planes."""
-    M, K = x.shape
-    out = torch.empty(_lib.load().pccx_planes_floats(M, K), device=x.device, dtype=torch.float32)
-    _lib.call("pccx_group_planes", x.data_ptr(), K, x.stride(0), None, 0, 0, None, M, 1, 1, out.data_ptr(), _stream())
-    return out
 
 
 def chain4_fits(stack):
@@ -221,15 +294,6 @@ def chain4_fits(stack):
     n = [l.N for l in stack]
     return (n[0] <= 32 and 32 < n[1] <= 64 and 32 < n[2] <= 64 and 64 < n[3] <= 128) or \
            (all(96 < v <= 128 for v in n[:3]) and 128 < n[3] <= 256)
-
-
-def _chain_args(stack, cache):
-    if "ws" not in cache:
-        cache["ws"] = torch.cat([l._stream3() for l in stack])
-    a = []
-    for l in stack:
-        a += [l.b.data_ptr(), l.N]
-    return cache["ws"], a
 
 
 def padded_rows(feats, xyz):
@@ -254,62 +318,65 @@ def wide3_fits(stack):
     return 240 < stack[0].N <= 256 and 240 < stack[1].N <= 256 and 496 < stack[2].N <= 512 and (stack[0].K + 31) // 32 in (8, 9)
 
 
-def wide3_planes(stack, src, C, idx, cache):
-    """relu(L2(relu(L1(relu(L0(gathered rows)))))) as planes, one kernel (pccx_planes_chain_wide).  src (B, N, ldp) from padded_rows();
-    idx (B, M, ns) int64 or None (then src is (rows, ldp) and every row is its own input)."""
-    if "wide" not in cache:
-        ws = torch.empty(_lib.load().pccx_planes_chain_wide_weight_floats(stack[0].K), device=src.device, dtype=torch.float32)
-        _lib.call("pccx_pack_planes_chain_wide", stack[0]._planes3().data_ptr(), stack[1]._planes3().data_ptr(), stack[2]._planes3().data_ptr(),
-                  stack[0].K, stack[0].N, stack[1].N, stack[2].N, ws.data_ptr(), _stream())
-        cache["wide"] = ws
-    if idx is not None:
-        B, Mq, ns = idx.shape
-        rows, rpb, n_src, ip = B * Mq * ns, Mq * ns, src.shape[1], idx.data_ptr()
-    else:
-        rows, rpb, n_src, ip = src.shape[0], 1, 1, None
-    out = torch.empty(_lib.load().pccx_planes_floats(rows, stack[2].N), device=src.device, dtype=torch.float32)
-    _lib.call("pccx_planes_chain_wide", src.data_ptr(), src.shape[-1], ip, rpb, n_src, rows, C, cache["wide"].data_ptr(),
-              stack[0].b.data_ptr(), stack[0].N, stack[1].b.data_ptr(), stack[1].N, stack[2].b.data_ptr(), stack[2].N, out.data_ptr(), _stream())
+def wide3_planes(stack, src, idx, rows):
+    """relu(L2(relu(L1(relu(L0(gathered rows)))))) as bf16x3 planes, one kernel (pccx_planes_chain_wide).  src (B, N, ldp) from
+    padded_rows(), idx (B, M, ns) int64."""
+    l0, l1, l2 = stack[0], stack[1], stack[2]
+    ws = stack.wide3()
+    out = _planes_out("bf16x3", rows, l2.N, 0, 0, src.device)
+    _lib.call("pccx_planes_chain_wide", src.data_ptr(), src.shape[-1], idx.data_ptr(), idx.shape[1] * idx.shape[2], src.shape[1], rows, l0.K,
+              ws.data_ptr(), l0.b.data_ptr(), l0.N, l1.b.data_ptr(), l1.N, l2.b.data_ptr(), l2.N, out.data_ptr(), _stream())
     return out
 
 
-def stack_max_gather(stack, feats, xyz, idx, cache):
-    """index_points(feats, idx) ++ index_points(xyz, idx) -> Conv-BN-ReLU x 4 -> max over nsample (pointnet_sa_module.py:73-91) in one
-    kernel for the stacks chain4_fits() accepts: the gather happens inside the kernel from the (B, N, C+3) rows zero padded to a
-    multiple of 32 channels, so the grouped tensor never exists.  idx (B, M, ns) int64, -1 -> row 0.  Returns (B * M, N3)."""
-    B, Mq, ns = idx.shape
-    src, C = padded_rows(feats, xyz)
-    idx = idx.contiguous()
-    rows = B * Mq * ns
-    if chain4_fits(stack):
-        ws, a = _chain_args(stack, cache)
-        out = torch.empty(B * Mq, stack[3].N, device=idx.device, dtype=torch.float32)
-        _lib.call("pccx_planes_chain4_gather", src.data_ptr(), src.shape[2], idx.data_ptr(), Mq * ns, src.shape[1], rows, C, ws.data_ptr(),
-                  *a, ns, out.data_ptr(), stack[3].N, _stream())
-        return out
-    if len(stack) == 4 and wide3_fits(stack):
-        # three wide layers in one kernel (gather inside), then the last layer with the max in its epilogue
-        return stack[3].planes(wide3_planes(stack, src, C, idx, cache), rows, 2, ns)
-    # layer by layer: the first layer gathers, the last reduces
-    pl = stack[0].planes_gather(src, C, idx) if len(stack) > 1 else None
-    for layer in stack[1:-1]:
-        pl = layer.planes(pl, rows, 0)
-    if len(stack) > 1:
-        return stack[-1].planes(pl, rows, 2, ns)
-    return stack[0].planes_gather(src, C, idx, 2, ns)
+_EPILOGUE = {"planes": 0, "rows": 1, "max": 2, "member": 2}
 
 
-def stack_max_planes(stack, pl, rows, group, cache):
-    """Conv-BN-ReLU stack + max over `group` consecutive rows on planes: one kernel when the stack fits pccx_planes_chain4, else
-    layer by layer with the max in the last layer's epilogue.  cache: a dict owned by the caller (holds the concatenated stream)."""
-    if chain4_fits(stack):
-        ws, a = _chain_args(stack, cache)
-        out = torch.empty(rows // group, stack[3].N, device=pl.device, dtype=torch.float32)
-        _lib.call("pccx_planes_chain4", pl.data_ptr(), rows, stack[0].K, ws.data_ptr(), *a, group, out.data_ptr(), stack[3].N, _stream())
+def run_planes(stack, x, M, want="rows", group=0, idx=None, member=None, ar="bf16x3", dyn=None, amax=None):
+    """A Conv/Linear Stack on M input rows through the planes kernels -- the one place that walks a stack's layers.
+    x: the operand planes of the (M, K) input in the arithmetic `ar`; or a PaddedRows, which the first kernel gathers row by row (an
+    identity index); or, with idx (B, Mq, ns) int64 (-1 -> row 0), the source rows (B, N, ldp) of padded_rows() -- the grouped tensor of
+    pointnet_sa_module.py:73-83 never exists.
+    want: "rows" -> fp32 rows (M, N_last); "max" -> (M // group, N_last), the maximum over `group` consecutive rows (:91); "member" ->
+    the same maximum over the rows marked 1 in `member` (M bytes; f16x2); "planes" -> the output as planes (bf16x3).
+    ONE kernel where the stack fits pccx_planes_chain4 (rows / max); three wide layers in one kernel and the last by itself for a gathered
+    bf16x3 input that fits pccx_planes_chain_wide; else layer by layer, the first layer gathering and the last one reducing.
+    f16x2: dyn = the stack's dynamic input normalisation {s, 1 / s} on the device, amax = 8 floats that receive the largest |value| of
+    the fp32 rows written (h2_prepare_stack first)."""
+    h2 = ar == "f16x2"
+    if h2 and "h2" not in stack.derived:
+        raise _lib.PccxError("run_planes: h2_prepare_stack() has not run on this stack")
+    if isinstance(x, PaddedRows):
+        Bn, n_src = x.src.shape[0], x.src.shape[1]
+        x, idx = x.src, identity_index(Bn, n_src, x.src.device).view(Bn, n_src, 1)
+    if want in ("rows", "max") and chain4_fits(stack):
+        g = group if want == "max" else 1
+        ws, sc, a = stack.chain4(ar)
+        out = _planes_out(ar, M, stack[3].N, 2, g, x.device)
+        scales, to = [sc.ctypes.data, _ptr(dyn), _ptr(amax)] if h2 else [], [out.data_ptr(), stack[3].N]
+        if idx is not None:
+            _pcall(ar, "chain4_gather", [x.data_ptr(), x.shape[2], idx.data_ptr(), idx.shape[1] * idx.shape[2], x.shape[1], M, stack[0].K,
+                                         ws.data_ptr(), *a, g], scales, to)
+        else:
+            _pcall(ar, "chain4", [x.data_ptr(), M, stack[0].K, ws.data_ptr(), *a, g], scales, to)
         return out
-    for layer in stack[:-1]:
-        pl = layer.planes(pl, rows, 0)
-    return stack[-1].planes(pl, rows, 2, group)
+    first = 0
+    if idx is not None and not h2 and len(stack) == 4 and wide3_fits(stack):
+        x, idx, first = wide3_planes(stack, x, idx, M), None, 3
+    for i, layer in enumerate(stack[first:-1], start=first):
+        x, idx = layer.planes(x, M, 0, idx=idx, ar=ar, sig_next=stack[i + 1].h2["sig"] if h2 else None, dyn=dyn), None
+    return stack[-1].planes(x, M, _EPILOGUE[want], group, idx=idx, member=member, ar=ar, dyn=dyn, amax=amax)
+
+
+def stack_max_gather(stack, feats, xyz, idx):
+    """index_points(feats, idx) ++ index_points(xyz, idx) -> Conv-BN-ReLU stack -> max over nsample (pointnet_sa_module.py:73-91), bf16x3:
+    the gather happens inside the first kernel from the (B, N, C+3) rows of padded_rows().  idx (B, M, ns) int64.  Returns (B * M, N_last)."""
+    return run_planes(stack, padded_rows(feats, xyz)[0], idx.numel(), "max", idx.shape[2], idx=idx.contiguous())
+
+
+def stack_max_planes(stack, pl, rows, group):
+    """Conv-BN-ReLU stack + max over `group` consecutive rows on bf16x3 planes."""
+    return run_planes(stack, pl, rows, "max", group)
 
 
 def fold_planes(a, mod0, b, div1, M):
@@ -317,62 +384,32 @@ def fold_planes(a, mod0, b, div1, M):
     (PPPF_AE.py:99-106).  a (.., C0), b (.., C1) fp32 rows."""
     a, b = a.contiguous(), b.contiguous()
     C0, C1 = int(a.shape[-1]), int(b.shape[-1])
-    out = torch.empty(_lib.load().pccx_planes_floats(M, C0 + C1), device=a.device, dtype=torch.float32)
+    out = _planes_out("bf16x3", M, C0 + C1, 0, 0, a.device)
     _lib.call("pccx_fold_planes", a.data_ptr(), C0, C0, mod0, b.data_ptr(), C1, C1, div1, M, out.data_ptr(), _stream())
     return out
 
 
-def run_stack_planes(stack, pl, M):
-    """A Conv/Linear stack on an input given as planes -> fp32 rows (M, N_last)."""
-    for layer in stack[:-1]:
-        pl = layer.planes(pl, M, 0)
-    return stack[-1].planes(pl, M, 1)
-
-
 def run_stack(stack, x):
-    """A Conv/Linear stack on fp32 rows x (M, K): layer by layer on rows (f32), or through planes (bf16x3)."""
-    if stack and stack[0].mode() == "bf16x3" and x.shape[0] > 0:
-        return run_stack_planes(stack, rows_planes(x), x.shape[0])
-    for layer in stack:
-        x = layer(x)
-    return x
+    """A Conv/Linear Stack on fp32 rows x (M, K): layer by layer on rows (f32), or through planes (bf16x3)."""
+    if len(stack) and stack[0].mode() == "bf16x3" and x.shape[0] > 0:
+        return run_planes(stack, group_planes(x)[0], x.shape[0])
+    return stack.rows(x)
 
 
-def rows_affine_small(base, div, x, mod, w_small, relu, M):
-    """act(base[r // div] + x[r % mod if mod else r] @ w_small.T) for r < M (pccx_rows_affine_small): base (B, C), x (.., Ks <= 4)."""
+def rows_affine_small(base, div, x, mod, w_small, relu, M, planes=None, rho=None, dyn=None):
+    """act(base[r // div] + x[r % mod if mod else r] @ w_small.T) for r < M: base (B, C), x (.., Ks <= 4).  planes=None -> fp32 rows (M, C)
+    (pccx_rows_affine_small); "bf16x3" / "f16x2" -> the same values written as the operand planes of the next layer, no fp32 rows in
+    between (f16x2: times rho * dyn[0])."""
     x = x.contiguous()
     Cc, Ks = int(base.shape[-1]), int(w_small.shape[1])
-    out = torch.empty(M, Cc, device=base.device, dtype=torch.float32)
-    _lib.call("pccx_rows_affine_small", base.contiguous().data_ptr(), Cc, int(div), x.data_ptr(), int(x.shape[-1]), Ks, int(mod),
-              w_small.data_ptr(), int(bool(relu)), int(M), out.data_ptr(), _stream())
+    args = [base.contiguous().data_ptr(), Cc, int(div), x.data_ptr(), int(x.shape[-1]), Ks, int(mod), w_small.data_ptr(), int(bool(relu)), int(M)]
+    if planes is None:
+        out = torch.empty(M, Cc, device=base.device, dtype=torch.float32)
+        _lib.call("pccx_rows_affine_small", *args, out.data_ptr(), _stream())
+    else:
+        out = _planes_out(planes, M, Cc, 0, 0, base.device)
+        _pcall(planes, "rows_affine", args, [float(rho) if rho is not None else None, _ptr(dyn)], [out.data_ptr()])
     return out
-
-
-def rows_affine_planes(base, div, x, mod, w_small, relu, M):
-    """rows_affine_small's values written as the operand planes of the next layer (pccx_rows_affine_planes): no fp32 rows in between."""
-    x = x.contiguous()
-    Cc, Ks = int(base.shape[-1]), int(w_small.shape[1])
-    out = torch.empty(_lib.load().pccx_planes_floats(M, Cc), device=base.device, dtype=torch.float32)
-    _lib.call("pccx_rows_affine_planes", base.contiguous().data_ptr(), Cc, int(div), x.data_ptr(), int(x.shape[-1]), Ks, int(mod),
-              w_small.data_ptr(), int(bool(relu)), int(M), out.data_ptr(), _stream())
-    return out
-
-
-def rows_affine_planes_h2(base, div, x, mod, w_small, relu, M, rho, dyn):
-    """rows_affine_planes in the f16x2 arithmetic: the planes of (rho * dyn[0]) * act(base[r // div] + x[..] @ w_small.T)"""
-    x = x.contiguous()
-    Cc, Ks = int(base.shape[-1]), int(w_small.shape[1])
-    out = torch.empty(_lib.load().pccx_planes_floats_h2(M, Cc), device=base.device, dtype=torch.float32)
-    _lib.call("pccx_rows_affine_planes_h2", base.contiguous().data_ptr(), Cc, int(div), x.data_ptr(), int(x.shape[-1]), Ks, int(mod),
-              w_small.data_ptr(), int(bool(relu)), int(M), float(rho), dyn.data_ptr(), out.data_ptr(), _stream())
-    return out
-
-
-def run_stack_planes_h2(stack, pl, M, dyn, amax=None):
-    """A Conv/Linear stack on f16x2 planes -> fp32 rows (M, N_last), un-scaled; amax: where the rows' largest |value| is recorded"""
-    for i, layer in enumerate(stack[:-1]):
-        pl = layer.planes_h2(pl, M, 0, sig_next=stack[i + 1].h2["sig"], dyn=dyn)
-    return stack[-1].planes_h2(pl, M, 1, dyn=dyn, amax=amax)
 
 
 def gather_max(y, idx):
@@ -438,7 +475,7 @@ def round_(x):
 
 
 def _fold_stack(seq, device):
-    """[Conv, (BN), (ReLU), ...] -> list of FoldedLinear."""
+    """[Conv, (BN), (ReLU), ...] -> Stack of FoldedLinear."""
     mods = list(seq)
     out, i = [], 0
     while i < len(mods):
@@ -452,7 +489,7 @@ def _fold_stack(seq, device):
         if relu:
             i += 1
         out.append(FoldedLinear(conv.weight, conv.bias, relu, bn, device))
-    return out
+    return Stack(out)
 
 
 class _Packable(nn.Module):
@@ -484,158 +521,63 @@ class PointnetSAModule(nn.Module):                      # pointnet_sa_module.py:
     dedup = True
     # A level whose output is only ever reduced over ALL its centroids (PPPF_AE's third: PPPF_AE.py:44) needs no per-centroid maxima: the
     # maximum over the centroids of the maxima over their samples is the maximum over the source rows that are a sample of any centroid.
-    # run_union_max() marks those rows (pccx_group_members) and takes that maximum in the last layer's epilogue -- neither the layer's
+    # run(union=True) marks those rows (pccx_group_members) and takes that maximum in the last layer's epilogue -- neither the layer's
     # fp32 rows (1 GB per 2048 patches) nor the per-centroid table exist.  union_max=False keeps gather_max + group_max (tests compare).
     union_max = True
     # Between the f16x2 levels the maxima are written as the next level's padded input rows (pccx_gather_max_rows) and that level's first
     # kernel gathers them itself (the gathering forms of the chain / GEMM with an identity index): the operand-plane pass of levels 2 and 3
-    # (pccx_group_planes_h2: 0.23 + 0.11 ms per 2048 patches) is not run.  Same planes, same results; False keeps the plane pass (tests compare).
+    # (0.23 + 0.11 ms per 2048 patches) is not run.  Same planes, same results; False keeps the plane pass (tests compare).
     padded_levels = True
 
-    def run_union_max(self, stack, xyz, feats, h2):
-        """max over the npoint centroids of the level's output (B, C'), f16x2 arithmetic; needs N in {32, 64, 128} source rows per element"""
+    def run(self, stack, xyz, feats, dyn=None, amax=None, pad_out=False, union=False):
+        """xyz (B,N,3); feats (B,N,C) channels-last or None -> (new_xyz (B,M,3), feats (B,M,C')).
+        dyn: evaluate the stack in the f16x2 arithmetic (h2_prepare_stack has run): the level's dynamic input normalisation {s, 1 / s} on
+        the device; amax = 8 floats that receive the largest value of the stack's output.  With dyn, feats may be a PaddedRows (the
+        previous level's pad_out) and pad_out=True returns one: the maxima written as the NEXT level's input rows [features | new_xyz | 0],
+        which its first kernel gathers itself -- no operand-plane pass between the levels.  union=True (f16x2, N in {32, 64, 128} source
+        rows per element, last layer with ReLU): feats is (B, C'), the maximum over the npoint centroids of the level's output."""
         B, N = xyz.shape[0], xyz.shape[1]
         with stage("fps"):
             new_xyz, _ = ops.sample_farthest_points(xyz, self.npoint)               # :66-68 (start index 0)
         with stage("ball_query"):
             idx = ops.ball_query(new_xyz, xyz, self.nsample, self.radius).idx       # :71 (-1 padded; gather clamps, :27)
-            member = torch.empty(B * N, device=xyz.device, dtype=torch.uint8)
-            _lib.call("pccx_group_members", idx.data_ptr(), idx.numel(), self.npoint * self.nsample, N, member.data_ptr(), _stream())
-        with stage("sa_stack_%d" % stack[-1].N):
-            dyn, _ = h2
-            if isinstance(feats, PaddedRows):
-                pl, first = self._h2_first_layer_gathered(stack, feats, dyn, stack[1].h2["sig"]), 1
-            else:
-                f2 = feats.reshape(-1, feats.shape[-1]).contiguous() if feats is not None else None
-                x2 = xyz.reshape(-1, 3).contiguous()
-                C0 = int(f2.shape[1]) if f2 is not None else 0
-                pl, first = torch.empty(_lib.load().pccx_planes_floats_h2(B * N, C0 + 3), device=x2.device, dtype=torch.float32), 0
-                _lib.call("pccx_group_planes_h2", f2.data_ptr() if f2 is not None else None, C0, C0, x2.data_ptr(), 3, 3, None, B * N, 1, 1,
-                          float(stack[0].h2["sig"]), dyn.data_ptr(), pl.data_ptr(), _stream())
-            for i, layer in enumerate(stack[first:-1], start=first):
-                pl = layer.planes_h2(pl, B * N, 0, sig_next=stack[i + 1].h2["sig"], dyn=dyn)
-            return stack[-1].planes_h2(pl, B * N, 2, group=N, dyn=dyn, member=member)
-
-    def run(self, stack, xyz, feats, h2=None, pad_out=False):
-        """xyz (B,N,3); feats (B,N,C) channels-last or None -> (new_xyz (B,M,3), feats (B,M,C')).
-        h2 = (dyn, amax_out): evaluate the stack in the f16x2 arithmetic (h2_prepare_stack has run): dyn = the level's dynamic input
-        normalisation {s, 1 / s} on the device, amax_out = 8 floats that receive the largest value of the stack's output.  With h2, feats
-        may be a PaddedRows (the previous level's pad_out) and pad_out=True returns one: the maxima written as the NEXT level's input rows
-        [features | new_xyz | 0], which its first kernel gathers itself -- no operand-plane pass between the levels."""
-        B = xyz.shape[0]
-        with stage("fps"):
-            new_xyz, _ = ops.sample_farthest_points(xyz, self.npoint)               # :66-68 (start index 0)
-        with stage("ball_query"):
-            idx = ops.ball_query(new_xyz, xyz, self.nsample, self.radius).idx       # :71 (-1 padded; gather clamps, :27)
+            member = torch.empty(B * N, device=xyz.device, dtype=torch.uint8) if union else None
+            if union:
+                _lib.call("pccx_group_members", idx.data_ptr(), idx.numel(), self.npoint * self.nsample, N, member.data_ptr(), _stream())
         if self.dedup and B > 0 and stack[-1].N % 4 == 0:
-            return new_xyz, self._run_dedup(stack, xyz, feats, idx, B, h2, new_xyz if pad_out else None)
-        if h2 is not None:
+            return new_xyz, self._run_dedup(stack, xyz, feats, idx, dyn, amax, new_xyz if pad_out else None, member)
+        if dyn is not None:
             raise _lib.PccxError("PointnetSAModule: the f16x2 stacks are built for the source-row evaluation (dedup=True)")
         return self._run_grouped(stack, xyz, feats, idx, new_xyz, B)
 
-    def _h2_first_layer_gathered(self, stack, padded, dyn, sig_next):
-        """the stack's first layer on PaddedRows through the gathering GEMM (identity index): -> planes of sig_next * output"""
-        l0, src = stack[0], padded.src
-        Bn, n_src, ldp = src.shape
-        M = Bn * n_src
-        out = torch.empty(_lib.load().pccx_planes_floats_h2(M, l0.N), device=src.device, dtype=torch.float32)
-        _lib.call("pccx_planes_gemm_gather_h2", src.data_ptr(), ldp, identity_index(Bn, n_src, src.device).data_ptr(), n_src, n_src, M, l0.K,
-                  l0.h2["ws"].data_ptr(), l0.h2["b"].data_ptr(), l0.N, l0.relu, 0, 0, float(l0.h2["sig"]),
-                  float(sig_next) / (l0.h2["sig"] * l0.h2["tau"]), dyn.data_ptr(), None, out.data_ptr(), l0.N, _stream())
-        return out
-
-    def _run_dedup_h2(self, stack, f2, x2, rows_n, C0, h2, padded=None):
-        """the stack on the source rows in the f16x2 arithmetic: rows -> planes of sigma_0 s [features, xyz], then ONE chain kernel (sa1 /
-        sa2) or the layers one by one (sa3), the last with the row epilogue that un-scales and records the output's maximum.  padded: the
-        rows as the previous level wrote them (PaddedRows): the first kernel gathers and splits them itself, no planes pass."""
-        dyn, amax_out = h2
-        lib = _lib.load()
-        ap = amax_out.data_ptr() if amax_out is not None else None
-        if padded is not None and chain4_fits(stack):
-            ws, sc, a = self._chain2_args(stack)
-            src = padded.src
-            y = torch.empty(rows_n, stack[3].N, device=src.device, dtype=torch.float32)
-            _lib.call("pccx_planes_chain4_gather_h2", src.data_ptr(), src.shape[2], identity_index(src.shape[0], src.shape[1], src.device).data_ptr(),
-                      src.shape[1], src.shape[1], rows_n, stack[0].K, ws.data_ptr(), *a, 1, sc.ctypes.data, dyn.data_ptr(), ap, y.data_ptr(),
-                      stack[3].N, _stream())
-            return y
-        if padded is not None:
-            pl = self._h2_first_layer_gathered(stack, padded, dyn, stack[1].h2["sig"])
-            for i, layer in enumerate(stack[1:-1], start=1):
-                pl = layer.planes_h2(pl, rows_n, 0, sig_next=stack[i + 1].h2["sig"], dyn=dyn)
-            return stack[-1].planes_h2(pl, rows_n, 1, dyn=dyn, amax=amax_out)
-        pl = torch.empty(lib.pccx_planes_floats_h2(rows_n, C0 + 3), device=x2.device, dtype=torch.float32)
-        _lib.call("pccx_group_planes_h2", f2.data_ptr() if f2 is not None else None, C0, C0, x2.data_ptr(), 3, 3, None, rows_n, 1, 1,
-                  float(stack[0].h2["sig"]), dyn.data_ptr(), pl.data_ptr(), _stream())
-        if chain4_fits(stack):
-            ws, sc, a = self._chain2_args(stack)
-            y = torch.empty(rows_n, stack[3].N, device=x2.device, dtype=torch.float32)
-            _lib.call("pccx_planes_chain4_h2", pl.data_ptr(), rows_n, stack[0].K, ws.data_ptr(), *a, 1, sc.ctypes.data, dyn.data_ptr(), ap,
-                      y.data_ptr(), stack[3].N, _stream())
-            return y
-        for i, layer in enumerate(stack[:-1]):
-            pl = layer.planes_h2(pl, rows_n, 0, sig_next=stack[i + 1].h2["sig"], dyn=dyn)
-        return stack[-1].planes_h2(pl, rows_n, 1, dyn=dyn, amax=amax_out)
-
-    def _chain2_args(self, stack):
-        """the f16x2 chain's weight stream, its five scales and its (bias, width) arguments, once per pack"""
-        if getattr(self, "_chain2_of", None) is not stack:
-            h = [l.h2 for l in stack]
-            sc = np.array([h[0]["sig"]] + [h[i]["sig"] / (h[i - 1]["sig"] * h[i - 1]["tau"]) for i in (1, 2, 3)] +
-                          [1.0 / (h[3]["sig"] * h[3]["tau"])], dtype=np.float32)
-            self._chain2_of, self._chain2 = stack, (torch.cat([x["ws"] for x in h]), sc)
-        ws, sc = self._chain2
-        a = []
-        for l in stack:
-            a += [l.h2["b"].data_ptr(), l.N]
-        return ws, sc, a
-
-    def _run_dedup(self, stack, xyz, feats, idx, B, h2=None, pad_xyz=None):
+    def _run_dedup(self, stack, xyz, feats, idx, dyn=None, amax=None, pad_xyz=None, member=None):
+        """the stack on the N SOURCE rows of every element, then each group's maximum over its members"""
+        B, N = xyz.shape[0], xyz.shape[1]
+        ar = "f16x2" if dyn is not None else stack[0].mode()
         with stage("sa_stack_%d" % stack[-1].N):
-            if h2 is not None and isinstance(feats, PaddedRows):
-                y = self._run_dedup_h2(stack, None, None, B * xyz.shape[1], feats.C, h2, padded=feats)
-            elif h2 is not None:
-                f2 = feats.reshape(-1, feats.shape[-1]).contiguous() if feats is not None else None
-                x2 = xyz.reshape(-1, 3).contiguous()
-                y = self._run_dedup_h2(stack, f2, x2, x2.shape[0], int(f2.shape[1]) if f2 is not None else 0, h2)
-            elif stack[0].mode() == "bf16x3":
-                # :83 features first, xyz last, one row per SOURCE point -- split straight into the first layer's operand planes from the
-                # two tables (pccx_group_planes without indices): the concatenated rows (two torch copies per level in round 3) never exist
-                f2 = feats.reshape(-1, feats.shape[-1]).contiguous() if feats is not None else None
-                x2 = xyz.reshape(-1, 3).contiguous()
-                rows_n = x2.shape[0]
-                C0 = int(f2.shape[1]) if f2 is not None else 0
-                pl = torch.empty(_lib.load().pccx_planes_floats(rows_n, C0 + 3), device=xyz.device, dtype=torch.float32)
-                _lib.call("pccx_group_planes", f2.data_ptr() if f2 is not None else None, C0, C0, x2.data_ptr(), 3, 3, None, rows_n, 1, 1,
-                          pl.data_ptr(), _stream())
-                if chain4_fits(stack):
-                    # :90 Conv-BN-ReLU x 4 on the source rows in ONE kernel (the chain of planes.hip with its row epilogue, group = 1)
-                    if getattr(self, "_chain_of", None) is not stack:               # new pack -> new stream
-                        self._chain_of, self._chain_cache = stack, {}
-                    ws, a = _chain_args(stack, self._chain_cache)
-                    y = torch.empty(rows_n, stack[3].N, device=xyz.device, dtype=torch.float32)
-                    _lib.call("pccx_planes_chain4", pl.data_ptr(), rows_n, stack[0].K, ws.data_ptr(), *a, 1, y.data_ptr(), stack[3].N, _stream())
-                else:
-                    y = run_stack_planes(stack, pl, rows_n)                         # :90 Conv-BN-ReLU, (B * N, C) rows
+            if ar == "f32":
+                y = stack.rows(cat_rows([feats, xyz] if feats is not None else [xyz]))      # :83 features first, xyz last; :90
             else:
-                rows = cat_rows([feats, xyz] if feats is not None else [xyz])
-                y = run_stack(stack, rows)
+                # rows -> planes of [features, xyz] (f16x2: times sigma_0 s) unless the previous level wrote them as PaddedRows, then ONE
+                # chain kernel (sa1 / sa2) or the layers one by one (sa3); f16x2 un-scales and records the output's maximum in the last
+                x = feats if isinstance(feats, PaddedRows) else \
+                    group_planes(feats, xyz, ar=ar, sig=stack[0].h2["sig"] if dyn is not None else None, dyn=dyn)[0]
+                if member is not None:
+                    return run_planes(stack, x, B * N, "member", N, member=member, ar=ar, dyn=dyn)   # :44 and :91 in one epilogue
+                y = run_planes(stack, x, B * N, ar=ar, dyn=dyn, amax=amax)                  # :90 Conv-BN-ReLU, (B * N, C) rows
         with stage("gather_max"):
             if pad_xyz is not None:
-                return gather_max_rows(y.view(B, xyz.shape[1], -1), idx, pad_xyz)   # :91, written as the next level's input rows
-            return gather_max(y.view(B, xyz.shape[1], -1), idx)                     # :91 max over the group's members
+                return gather_max_rows(y.view(B, N, -1), idx, pad_xyz)                      # :91, written as the next level's input rows
+            return gather_max(y.view(B, N, -1), idx)                                        # :91 max over the group's members
 
     def _run_grouped(self, stack, xyz, feats, idx, new_xyz, B):
+        """the literal form: the stack on all npoint * nsample gathered rows (what dedup=False compares against)"""
         if stack[0].mode() == "bf16x3" and self.nsample in (32, 64, 128) and B > 0:
-            # gather + concat + split in one pass, every layer on planes, the max over nsample in the last layer's epilogue
-            if getattr(self, "_chain_of", None) is not stack:                       # new pack -> new stream
-                self._chain_of, self._chain_cache = stack, {}
-            # :73-91 gather (features first, xyz last, not centred) inside the first kernel, max over nsample in the last
-            return new_xyz, stack_max_gather(stack, feats, xyz, idx, self._chain_cache).view(B, self.npoint, -1)
+            # :73-91 gather (features first, xyz last, not centred) inside the first kernel, every layer on planes, max over nsample in the last
+            return new_xyz, stack_max_gather(stack, feats, xyz, idx).view(B, self.npoint, -1)
         grouped = ops.index_points(xyz, idx)                                        # :81 (not centred)
         x = cat_rows([ops.index_points(feats, idx), grouped] if feats is not None else [grouped])   # :83 features first, xyz last
-        for layer in stack:
-            x = layer(x)                                                            # :90 Conv-BN-ReLU
+        x = stack.rows(x)                                                           # :90 Conv-BN-ReLU
         return new_xyz, group_max(x.view(B * self.npoint, self.nsample, -1)).view(B, self.npoint, -1)   # :91
 
 
@@ -658,10 +600,51 @@ class FoldingNet(nn.Module):                            # PPPF_AE.py:50-80
                                   nn.Conv1d(128, 3, 1))
 
 
+class H2Scales:
+    """The f16x2 scale bookkeeping of one packed PPPF_AE, rewritten by every forward on the device: amax = 6 slots of 8 floats that
+    receive a largest |value| (0 coordinates, 1 / 2 outputs of levels 1 / 2, 3 / 5 per-patch parts of mlp1 / mlp2, 4 coarse points),
+    dyn = 5 slots {s, 1 / s}, one per planes stack (levels 0..2, mlp1, mlp2): the power of two s <= 1 that normalises its input.
+    wsum = the largest absolute row sums of the two folding MLPs' per-point weights."""
+
+    def __init__(self, device, wsum):
+        self.amax = torch.zeros(6 * 8, device=device, dtype=torch.float32)
+        self.dyn = torch.ones(5 * 2, device=device, dtype=torch.float32)
+        self.wsum = wsum
+
+    def __getitem__(self, name):                           # ._packed["h2"]["dyn"], as tests and bench.py read it
+        return getattr(self, name)
+
+    def am(self, i):
+        return self.amax[8 * i:8 * i + 8] if i is not None else None
+
+    def dy(self, i):
+        return self.dyn[2 * i:2 * i + 2]
+
+    def reset(self):
+        _lib.call("pccx_zero_bytes", self.amax.data_ptr(), self.amax.numel() * 4, _stream())
+
+    def absmax(self, t, i):
+        """fold max |t| into amax slot i"""
+        _lib.call("pccx_absmax", t.data_ptr(), t.numel(), self.am(i).data_ptr(), _stream())
+
+    def scale(self, out, m1, m2=None, a2=0.0, add=0.0, comb=1):
+        """dyn slot `out` from amax slot m1 and (comb 1: the larger of the two, comb 0: plus) a2 * amax slot m2 + add (pccx_dyn_scale)"""
+        _lib.call("pccx_dyn_scale", self.am(m1).data_ptr(), 1.0, _ptr(self.am(m2)), float(a2), float(add), int(comb), self.dy(out).data_ptr(),
+                  _stream())
+
+
+def _pow2x4(n):
+    """the widths pccx_rows_affine_small takes"""
+    return n % 4 == 0 and n <= 1024 and (n // 4) & (n // 4 - 1) == 0
+
+
 class PPPF_AE(_Packable):
     """PPPF_AE.PPPF_AE (PPPF_AE.py:114-150)."""
 
-    split_fold = True       # FoldingNet's first layers evaluated as per-patch + per-point parts (forward()); False = the literal rows
+    split_fold = True       # FoldingNet's first layers evaluated as per-patch + per-point parts (_fold()); False = the literal rows
+    # amax / dyn slots of the two folding MLPs in the f16x2 arithmetic: per-patch part, per-point input (None: the grid, within [-1, 1]),
+    # the chain's normalisation, the chain's output
+    _FOLD_SLOTS = {"mlp1": (3, None, 3, 4), "mlp2": (5, 4, 4, None)}
 
     def __init__(self, K=512, k=0, d=16, L=7, dim=1024):
         super().__init__()
@@ -678,11 +661,13 @@ class PPPF_AE(_Packable):
                             enc=FoldedLinear(self.enc_proj.weight, self.enc_proj.bias, False, None, device),
                             dec=FoldedLinear(self.dec_proj.weight, self.dec_proj.bias, False, None, device),
                             mlp1=_fold_stack(dcd.mlp1, device), mlp2=_fold_stack(dcd.mlp2, device))
-        # first layers of the two folding MLPs split into their per-patch (latent) and per-point (grid / coarse) parts, see forward()
+        # first layers of the two folding MLPs split into their per-patch (latent) and per-point (grid / coarse) parts, see _fold();
+        # _rest = the layers after the first, a Stack of its own
         for name, seq, ks in (("mlp1", dcd.mlp1, 2), ("mlp2", dcd.mlp2, 3)):
             w = seq[0].weight.detach().to("cpu", torch.float32).reshape(seq[0].weight.shape[0], -1)
             self._packed[name + "_lat"] = FoldedLinear(w[:, ks:], seq[0].bias, False, None, device)
             self._packed[name + "_small"] = w[:, :ks].contiguous().to(device)
+            self._packed[name + "_rest"] = self._packed[name][1:]
         x = torch.linspace(-1, 1, dcd.grid_size)
         gx, gy = torch.meshgrid(x, x, indexing="ij")
         self._packed["grid"] = torch.stack([gx, gy], dim=-1).reshape(-1, 2).to(device)            # :82-88
@@ -702,12 +687,55 @@ class PPPF_AE(_Packable):
             h2_prepare_stack(stack, np.concatenate([np.zeros(c_prev), -np.ones(3)]), np.ones(c_prev + 3))   # :83 features first, xyz last
             c_prev = stack[-1].N
         for name in ("mlp1", "mlp2"):
-            first, rest = pk[name][0], pk[name][1:]
+            first, rest = pk[name][0], pk[name + "_rest"]
             h2_prepare_stack(rest, np.zeros(rest[0].K) if first.relu else -np.ones(rest[0].K), np.ones(rest[0].K))
         wsum = lambda w: float(np.abs(w.detach().cpu().numpy().astype(np.float64)).sum(axis=1).max() * 1.001)
-        pk["h2"] = dict(amax=torch.zeros(6 * 8, device=device, dtype=torch.float32), dyn=torch.ones(5 * 2, device=device, dtype=torch.float32),
-                        wsum1=wsum(pk["mlp1_small"]), wsum2=wsum(pk["mlp2_small"]))
+        pk["h2"] = H2Scales(device, {"mlp1": wsum(pk["mlp1_small"]), "mlp2": wsum(pk["mlp2_small"])})
         return pk["h2"]
+
+    def _splits(self, B):
+        """FoldingNet's first layers can be evaluated as per-patch + per-point parts"""
+        pk = self._packed
+        return self.split_fold and B > 0 and _pow2x4(pk["mlp1"][0].N) and _pow2x4(pk["mlp2"][0].N)
+
+    def _h2_eligible(self, B):
+        """every planes stack of the forward has an f16x2 form: asked for, source-row levels, split folding"""
+        pk = self._packed
+        return (pk["sa"][0][0].planes_mode() == "f16x2" and PointnetSAModule.dedup and self._splits(B)
+                and all(st[-1].N % 4 == 0 for st in pk["sa"]))
+
+    def _fold(self, name, lat_dec, pts, mod, B, split, form, sc):
+        """One folding MLP (PPPF_AE.py:99-107) on [pts | latent] -> (B * P, 3) rows.  pts: the grid (mod = P: the same for every patch) or
+        the coarse points (mod = 0: one row each).  form: "f16x2" / "bf16x3" planes, or "rows" (fp32 rows layer by layer).
+        split: the input [pts | latent] is never built: its 1024-wide latent part is the same for the P points of a patch, so the first
+        layer is W_lat latent + bias once per PATCH (a Linear on B rows) plus a 2- / 3-term per-point update with ReLU, which on planes
+        writes the next layer's operand PLANES directly (the fp32 rows of the 512-wide MLP were 1 GB written, read back and split per 2048
+        patches); the remaining layers run on the P rows.  Otherwise the literal form, on planes without concatenating or repeating
+        anything in memory (fold_planes), or on rows (:99-101, :106)."""
+        pk, P = self._packed, self.decoder.num_points
+        M = B * P
+        with stage("fold_" + name):
+            if not split:
+                if form == "rows":
+                    rep = lat_dec[:, None, :].expand(B, P, self.dim)
+                    return pk[name].rows(cat_rows([pts[None].expand(B, P, -1) if mod else pts.view(B, P, -1), rep]))
+                return run_planes(pk[name], fold_planes(pts, mod, lat_dec, P, M), M)
+            base, rest, relu = pk[name + "_lat"](lat_dec), pk[name + "_rest"], pk[name][0].relu
+            if form == "rows":
+                return rest.rows(rows_affine_small(base, P, pts, mod, pk[name + "_small"], relu, M))
+            rho = dyn = amax = None
+            if form == "f16x2":
+                # the chain's input relu(base + point part) is bounded from the data: max |base| + the per-point update's largest row sum
+                # times max |point input| (the grid lies in [-1, 1], the coarse points' maximum comes out of the first chain's row epilogue)
+                s_base, s_pts, s_dyn, s_out = self._FOLD_SLOTS[name]
+                sc.absmax(base, s_base)
+                if s_pts is None:
+                    sc.scale(s_dyn, s_base, add=sc.wsum[name], comb=0)
+                else:
+                    sc.scale(s_dyn, s_base, s_pts, a2=sc.wsum[name], comb=0)
+                rho, dyn, amax = rest[0].h2["sig"], sc.dy(s_dyn), sc.am(s_out)
+            pl = rows_affine_small(base, P, pts, mod, pk[name + "_small"], relu, M, planes=form, rho=rho, dyn=dyn)
+            return run_planes(rest, pl, M, ar=form, dyn=dyn, amax=amax)
 
     def forward(self, xyz):
         """xyz (B,N,3) on the GPU -> (recon (B,d*d,3), latent (B,dim), latent_quantized (B,d))."""
@@ -716,87 +744,31 @@ class PPPF_AE(_Packable):
         pk = self._packed
         B = xyz.shape[0]
         pts, feats = ops._f32c(xyz, "PPPF_AE"), None
-        pow2x4 = lambda n: n % 4 == 0 and n <= 1024 and (n // 4) & (n // 4 - 1) == 0     # widths pccx_rows_affine_small takes
-        h2 = None
-        if (B > 0 and pk["sa"][0][0].planes_mode() == "f16x2" and PointnetSAModule.dedup and self.split_fold
-                and all(st[-1].N % 4 == 0 for st in pk["sa"]) and pow2x4(pk["mlp1"][0].N) and pow2x4(pk["mlp2"][0].N)):
-            h2 = self._ensure_h2(pts.device)
-            am, dy = (lambda i: h2["amax"][8 * i:8 * i + 8]), (lambda i: h2["dyn"][2 * i:2 * i + 2])
-            scale_of = lambda m1, a1, m2, a2, add, comb, out: _lib.call(
-                "pccx_dyn_scale", m1.data_ptr(), float(a1), m2.data_ptr() if m2 is not None else None, float(a2), float(add), int(comb),
-                out.data_ptr(), _stream())
-            absmax = lambda t, slot: _lib.call("pccx_absmax", t.data_ptr(), t.numel(), slot.data_ptr(), _stream())
-            _lib.call("pccx_zero_bytes", h2["amax"].data_ptr(), h2["amax"].numel() * 4, _stream())
-            absmax(pts, am(0))                                                      # max |coordinate|: every level's centroids are a subset
+        sc = None
+        if self._h2_eligible(B):
+            sc = self._ensure_h2(pts.device)
+            sc.reset()
+            sc.absmax(pts, 0)                                                       # max |coordinate|: every level's centroids are a subset
         for lvl, (mod, stack) in enumerate(zip((self.encoder.sa1, self.encoder.sa2, self.encoder.sa3), pk["sa"])):
-            if h2 is None:
+            if sc is None:
                 pts, feats = mod.run(stack, pts, feats)
                 continue
             # the level's input = [maxima of the previous level's output rows, coordinates]: s from the larger of the two bounds
-            if lvl == 0:
-                scale_of(am(0), 1.0, None, 0.0, 0.0, 1, dy(0))
-            else:
-                scale_of(am(lvl), 1.0, am(0), 1.0, 0.0, 1, dy(lvl))
-            if (lvl == 2 and mod.union_max and pts.shape[1] in (32, 64, 128) and stack[-1].relu and not chain4_fits(stack)):
-                feats = mod.run_union_max(stack, pts, feats, (dy(lvl), None))       # (B, dim): :44 and :91 of the level in one epilogue
-                continue
-            pts, feats = mod.run(stack, pts, feats, h2=(dy(lvl), am(lvl + 1) if lvl < 2 else None),
-                                 pad_out=lvl < 2 and PointnetSAModule.padded_levels)
+            sc.scale(lvl, lvl, 0 if lvl else None, a2=1.0 if lvl else 0.0)
+            union = lvl == 2 and mod.union_max and pts.shape[1] in (32, 64, 128) and stack[-1].relu and not chain4_fits(stack)
+            pts, feats = mod.run(stack, pts, feats, dyn=sc.dy(lvl), amax=sc.am(lvl + 1) if lvl < 2 else None,
+                                 pad_out=lvl < 2 and PointnetSAModule.padded_levels, union=union)
         with stage("latent"):
             g = group_max(feats) if feats.dim() == 3 else feats                     # :44 max over the 32 points
             latent = sigmoid_spread(g, self.L)                                      # :136-137
             q = round_(pk["enc"](latent))                                           # :139-142
             lat_dec = pk["dec"](q)                                                  # :145
-        P = self.decoder.num_points
-        if h2 is not None:
-            # the split folding form (below) in the f16x2 arithmetic.  A chain's input relu(base + point part) is bounded from the data:
-            # max |base| (+ the per-point update's largest row sum times max |point input|: the grid lies in [-1, 1], the coarse points'
-            # maximum comes out of the first chain's row epilogue)
-            with stage("fold_mlp1"):
-                base1 = pk["mlp1_lat"](lat_dec)
-                absmax(base1, am(3))
-                scale_of(am(3), 1.0, None, 0.0, h2["wsum1"], 0, dy(3))
-                st = pk["mlp1"][1:]
-                pl = rows_affine_planes_h2(base1, P, pk["grid"], P, pk["mlp1_small"], pk["mlp1"][0].relu, B * P, st[0].h2["sig"], dy(3))
-                x = run_stack_planes_h2(st, pl, B * P, dy(3), am(4))                                         # :104 coarse
-            with stage("fold_mlp2"):
-                base2 = pk["mlp2_lat"](lat_dec)
-                absmax(base2, am(5))
-                scale_of(am(5), 1.0, am(4), h2["wsum2"], 0.0, 0, dy(4))
-                st = pk["mlp2"][1:]
-                pl = rows_affine_planes_h2(base2, P, x, 0, pk["mlp2_small"], pk["mlp2"][0].relu, B * P, st[0].h2["sig"], dy(4))
-                x = run_stack_planes_h2(st, pl, B * P, dy(4))                                                # :107 fine
-            return x.view(B, P, 3), latent, q
-        if self.split_fold and B > 0 and pow2x4(pk["mlp1"][0].N) and pow2x4(pk["mlp2"][0].N):
-            # The folding inputs [grid | latent] and [coarse | latent] (:99-106) are never built: their 1024-wide latent part is the
-            # same for the P points of a patch, so the first layer of each MLP is W_lat latent + bias once per PATCH (a Linear on B
-            # rows) plus a 2- / 3-term per-point update with ReLU (pccx_rows_affine_small); the remaining layers run on the P rows.
-            if pk["mlp1"][1].mode() == "bf16x3":
-                # ... and the per-point update writes the next layer's operand PLANES directly (the fp32 rows of the 512-wide MLP were 1 GB
-                # written, read back and split per 2048 patches)
-                with stage("fold_mlp1"):
-                    pl = rows_affine_planes(pk["mlp1_lat"](lat_dec), P, pk["grid"], P, pk["mlp1_small"], pk["mlp1"][0].relu, B * P)
-                    x = run_stack_planes(pk["mlp1"][1:], pl, B * P)                                          # :104 coarse
-                with stage("fold_mlp2"):
-                    pl = rows_affine_planes(pk["mlp2_lat"](lat_dec), P, x, 0, pk["mlp2_small"], pk["mlp2"][0].relu, B * P)
-                    x = run_stack_planes(pk["mlp2"][1:], pl, B * P)                                          # :107 fine
-                return x.view(B, P, 3), latent, q
-            h = rows_affine_small(pk["mlp1_lat"](lat_dec), P, pk["grid"], P, pk["mlp1_small"], pk["mlp1"][0].relu, B * P)
-            x = run_stack(pk["mlp1"][1:], h)                                                                 # :104 coarse
-            h = rows_affine_small(pk["mlp2_lat"](lat_dec), P, x, 0, pk["mlp2_small"], pk["mlp2"][0].relu, B * P)
-            x = run_stack(pk["mlp2"][1:], h)                                                                 # :107 fine
-            return x.view(B, P, 3), latent, q
-        if pk["mlp1"][0].mode() == "bf16x3" and B > 0:
-            # the literal form on operand planes: nothing is concatenated or repeated in memory either
-            x = run_stack_planes(pk["mlp1"], fold_planes(pk["grid"], P, lat_dec, P, B * P), B * P)          # :104 coarse
-            x = run_stack_planes(pk["mlp2"], fold_planes(x, 0, lat_dec, P, B * P), B * P)                   # :107 fine
-            return x.view(B, P, 3), latent, q
-        rep = lat_dec[:, None, :].expand(B, P, self.dim)
-        x = cat_rows([pk["grid"][None].expand(B, P, 2), rep])                                             # :99-101
-        x = run_stack(pk["mlp1"], x)                                                # :104 coarse
-        x = cat_rows([x.view(B, P, 3), rep])                                                                # :106
-        x = run_stack(pk["mlp2"], x)                                                # :107 fine
-        return x.view(B, P, 3), latent, q
+        # the FoldingNet form, chosen once: split or literal; f16x2 planes, bf16x3 planes, or fp32 rows (f32, and the empty batch)
+        split = self._splits(B)
+        form = "f16x2" if sc is not None else "bf16x3" if B > 0 and pk["mlp1"][0].mode() == "bf16x3" else "rows"
+        x = self._fold("mlp1", lat_dec, pk["grid"], self.decoder.num_points, B, split, form, sc)   # :104 coarse
+        x = self._fold("mlp2", lat_dec, x, 0, B, split, form, sc)                                   # :107 fine
+        return x.view(B, self.decoder.num_points, 3), latent, q
 
 
 def pppf_flops_per_patch(model, executed=False, n_points=512):
@@ -847,9 +819,7 @@ class PointNetSetAbstraction(nn.Module):                # pppe_pcd_ae.py:573-611
         new_xyz = xyz if S == N else ops.index_points(xyz, ops.farthest_point_sample_batch(xyz, S, start))   # :593-597
         nn_ = ops.knn_points(new_xyz, xyz, self.K, patch_scale=1.0)                  # :599-600 (nn - centre) * 1
         x = cat_rows([nn_.knn, ops.index_points(feats, nn_.idx)] if feats is not None else [nn_.knn])   # :606 xyz first
-        for layer in stack:
-            x = layer(x)
-        return new_xyz, group_max(x.view(B * S, self.K, -1)).view(B, S, -1)          # :610
+        return new_xyz, group_max(stack.rows(x).view(B * S, self.K, -1)).view(B, S, -1)   # :610
 
 
 class PointNetSetAbstractionMSG(nn.Module):             # pppe_pcd_ae.py:614-632
@@ -903,10 +873,9 @@ class PointCloudAE(_Packable):
 
     def pack(self, device="cuda"):
         sa = self.encoder.sa_modules
+        conv_bn_relu = lambda mods: Stack(FoldedLinear(l[0].weight, None, True, l[1], device) for l in mods)
         self._packed = dict(
-            msg=[[FoldedLinear(l[0].weight, None, True, l[1], device) for l in br.mlp_stack] for br in sa[0].branches],
-            sa1=[FoldedLinear(l[0].weight, None, True, l[1], device) for l in sa[1].mlp_stack],
-            sa2=[FoldedLinear(l[0].weight, None, True, l[1], device) for l in sa[2].mlp_stack],
+            msg=[conv_bn_relu(br.mlp_stack) for br in sa[0].branches], sa1=conv_bn_relu(sa[1].mlp_stack), sa2=conv_bn_relu(sa[2].mlp_stack),
             gconv=_fold_stack(self.encoder.global_conv, device),
             coarse=_fold_stack(self.decoder.fc_coarse, device), expand=_fold_stack(self.decoder.expansion_mlp, device))
         return self
@@ -929,17 +898,11 @@ class PointCloudAE(_Packable):
         xyz, feats = sa[1].run(pk["sa1"], new_xyz, feats, starts[1])
         xyz, feats = sa[2].run(pk["sa2"], xyz, feats, starts[2])
         cond = group_max(feats)                                                      # :682 global max
-        latent = cond
-        for layer in pk["gconv"]:
-            latent = layer(latent)                                                   # :684
+        latent = pk["gconv"].rows(cond)                                              # :684
         # quantize_st (:719-735) then dequantise (:873); the mean over N tiled copies (:875) is the value itself
         y_q, y_deq = torch.empty_like(latent), torch.empty_like(latent)
         _lib.call("pccx_quantize_st", latent.data_ptr(), latent.numel(), float(self.q_min), float(self.q_max),
                   int(self.latent_bins), y_q.data_ptr(), y_deq.data_ptr(), _stream())
-        c = y_deq
-        for layer in pk["coarse"]:
-            c = layer(c)                                                             # :710
-        e = torch.cat([c, y_deq], dim=1).contiguous()                                # :711
-        for layer in pk["expand"]:
-            e = layer(e)                                                             # :712
+        c = pk["coarse"].rows(y_deq)                                                 # :710
+        e = pk["expand"].rows(torch.cat([c, y_deq], dim=1).contiguous())             # :711-712
         return c.view(B, -1, 3), e.view(B, -1, 3), cond, y_q, latent

@@ -211,11 +211,11 @@ def test_third_level_union_maximum_equals_gather_max_then_group_max_bit_for_bit(
     xin = torch.from_numpy(rows_in).cuda()
     _lib.call("pccx_group_planes_h2", xin.data_ptr(), layer.K, layer.K, None, 0, 0, None, M, 1, 1, float(layer.h2["sig"]), None, pl.data_ptr(),
               torch.cuda.current_stream().cuda_stream)
-    rows = layer.planes_h2(pl, M, 1)
-    got = layer.planes_h2(pl, M, 2, group=N, member=member)
+    rows = layer.planes(pl, M, 1, ar="f16x2")
+    got = layer.planes(pl, M, 2, group=N, member=member, ar="f16x2")
     ref = torch.where(want.view(B, N, 1).bool(), rows.view(B, N, -1), torch.full_like(rows.view(B, N, -1), float("-inf"))).amax(dim=1)
     assert torch.equal(got, ref)
-    none = layer.planes_h2(pl, M, 2, group=N, member=torch.zeros_like(member))
+    none = layer.planes(pl, M, 2, group=N, member=torch.zeros_like(member), ar="f16x2")
     assert torch.equal(none, torch.zeros_like(none))                                  # no member: relu(-inf) = 0
 
 
@@ -260,6 +260,45 @@ def test_padded_rows_between_the_levels_equal_the_operand_plane_pass_bit_for_bit
     assert torch.equal(pr.src[..., :C], families.gather_max(y, idx)) and torch.equal(pr.src[..., C:C + 3], cxyz) and not pr.src[..., C + 3:].any()
     with pytest.raises(_lib.PccxError):
         _lib.call("pccx_gather_max_rows", y.data_ptr(), B, N, C, idx.data_ptr(), M, ns, cxyz.data_ptr(), pr.src.data_ptr(), 136, None)
+
+
+@pytest.mark.gpu
+def test_reload_drops_every_derived_stream():
+    """Everything derived from the packed weights -- the bf16x3 planes and chain streams, the f16x2 operands, chain stream and scales,
+    the "h2" buffers -- belongs to the packed stacks, and load_state_dict() drops those: a model that has run in bf16x3 and in f16x2
+    with weights A and is then loaded with weights B gives, in both arithmetics, outputs IDENTICAL to a freshly constructed model
+    loaded with B (and not those of A)."""
+    import pccx
+    from pccx import families
+
+    def weights(g, seed):
+        return synth.family_tweak(rf.seeded_with_bn(g, seed), "pppf")
+
+    xc = torch.from_numpy(synth.pppf_input()).cuda()
+    old = pccx.DEFAULT_MATMUL
+
+    def both(g):
+        outs = []
+        for arith in ("bf16x3", "f16x2"):
+            pccx.DEFAULT_MATMUL = arith
+            outs.append([t.clone() for t in g(xc)])
+        return outs
+
+    try:
+        g = families.PPPF_AE(512, 0, 16, 7)
+        g.load_state_dict(weights(g, synth.PPPF_SEED))
+        with_a = both(g)
+        assert "h2" in g._packed, "the f16x2 stacks did not run"
+        g.load_state_dict(weights(g, synth.PPPF_SEED + 100))
+        got = both(g)
+        fresh = families.PPPF_AE(512, 0, 16, 7)
+        fresh.load_state_dict(weights(fresh, synth.PPPF_SEED + 100))
+        want = both(fresh)
+    finally:
+        pccx.DEFAULT_MATMUL = old
+    for a, u, v in zip(with_a, got, want):
+        assert len(u) == len(v) == 3 and all(torch.equal(s_, t_) for s_, t_ in zip(u, v))
+        assert not torch.equal(a[1], u[1])                   # ... and the two sets of weights do tell the outputs apart
 
 
 @pytest.mark.gpu
@@ -370,7 +409,7 @@ def test_planes_layers_ragged_shapes():
                           (1000, 259, 7, True), (4096, 512, 512, True)]:
         lyr, W, b = layer(N, K, relu)
         x = rng.standard_normal((M, K)).astype(np.float32)
-        got = lyr.planes(families.rows_planes(torch.from_numpy(x).cuda()), M, 1).cpu().numpy()
+        got = lyr.planes(families.group_planes(torch.from_numpy(x).cuda())[0], M, 1).cpu().numpy()
         want = x.astype(np.float64) @ W.T + b
         if relu:
             want = np.maximum(want, 0)
@@ -379,16 +418,16 @@ def test_planes_layers_ragged_shapes():
     a, b2 = rng.standard_normal((10, 2)).astype(np.float32), rng.standard_normal((7, 37)).astype(np.float32)
     cat = np.concatenate([np.tile(a, (7, 1)), np.repeat(b2, 10, axis=0)], axis=1)
     got = families.fold_planes(torch.from_numpy(a).cuda(), 10, torch.from_numpy(b2).cuda(), 10, 70)
-    assert torch.equal(got, families.rows_planes(torch.from_numpy(cat).cuda()))
+    assert torch.equal(got, families.group_planes(torch.from_numpy(cat).cuda())[0])
     a3 = rng.standard_normal((70, 3)).astype(np.float32)
     cat = np.concatenate([a3, np.repeat(b2, 10, axis=0)], axis=1)
     got = families.fold_planes(torch.from_numpy(a3).cuda(), 0, torch.from_numpy(b2).cuda(), 10, 70)
-    assert torch.equal(got, families.rows_planes(torch.from_numpy(cat).cuda()))
+    assert torch.equal(got, families.group_planes(torch.from_numpy(cat).cuda())[0])
     # chain of two layers through planes (odd number of 16-channel tiles in the middle: 48 channels)
     l0, W0, b0 = layer(48, 35, True)
     l1, W1, b1 = layer(40, 48, False)
     x = rng.standard_normal((300, 35)).astype(np.float32)
-    got = families.run_stack([l0, l1], torch.from_numpy(x).cuda()).cpu().numpy()
+    got = families.run_stack(families.Stack([l0, l1]), torch.from_numpy(x).cuda()).cpu().numpy()
     want = np.maximum(x.astype(np.float64) @ W0.T + b0, 0) @ W1.T + b1
     np.testing.assert_allclose(got, want, atol=2e-5, rtol=1e-5)
     # gather + concat + layer + max over nsample
@@ -408,9 +447,9 @@ def test_planes_layers_ragged_shapes():
         np.testing.assert_allclose(got, want, atol=2e-5, rtol=1e-5, err_msg=str((ns, C)))
         # the same through the gathering form of the layer kernel (and of a two-layer stack): bit-identical
         f_, z_, i_ = torch.from_numpy(feats).cuda() if C else None, torch.from_numpy(xyz).cuda(), torch.from_numpy(idx).cuda()
-        assert np.array_equal(families.stack_max_gather([lyr], f_, z_, i_, {}).cpu().numpy(), got)
+        assert np.array_equal(families.stack_max_gather(families.Stack([lyr]), f_, z_, i_).cpu().numpy(), got)
         l2, _, _ = layer(33, 70, True)
-        two = families.stack_max_gather([lyr, l2], f_, z_, i_, {}).cpu().numpy()
+        two = families.stack_max_gather(families.Stack([lyr, l2]), f_, z_, i_).cpu().numpy()
         assert np.array_equal(two, l2.planes(lyr.planes(pl, rows, 0), rows, 2, ns).cpu().numpy())
 
 
@@ -431,11 +470,12 @@ def test_planes_chain4_matches_layer_by_layer_and_float64():
             stack.append(families.FoldedLinear(torch.from_numpy(W), torch.from_numpy(b), True, matmul="bf16x3"))
             Ws.append((W.astype(np.float64), b.astype(np.float64)))
             k = nw
+        stack = families.Stack(stack)
         assert families.chain4_fits(stack)
         rows = groups * ns
         x = rng.standard_normal((rows, K0)).astype(np.float32)
-        pl = families.rows_planes(torch.from_numpy(x).cuda())
-        got = families.stack_max_planes(stack, pl, rows, ns, {}).cpu().numpy()
+        pl = families.group_planes(torch.from_numpy(x).cuda())[0]
+        got = families.stack_max_planes(stack, pl, rows, ns).cpu().numpy()
         p2 = pl
         for layer in stack[:-1]:
             p2 = layer.planes(p2, rows, 0)
@@ -455,8 +495,8 @@ def test_planes_chain4_matches_layer_by_layer_and_float64():
             idx = torch.from_numpy(rng.integers(-1, Nsrc, (Bq, Mq, ns))).cuda()
             f, z = torch.from_numpy(feats).cuda(), torch.from_numpy(xyz).cuda()
             pl2, rows2 = families.group_planes(f, z, idx)
-            want = families.stack_max_planes(stack, pl2, rows2, ns, {}).cpu().numpy()
-            got2 = families.stack_max_gather(stack, f, z, idx, {}).cpu().numpy()
+            want = families.stack_max_planes(stack, pl2, rows2, ns).cpu().numpy()
+            got2 = families.stack_max_gather(stack, f, z, idx).cpu().numpy()
             assert np.array_equal(got2, want), (K0, widths)
 
 
@@ -476,15 +516,16 @@ def test_planes_chain_wide_matches_layer_by_layer_and_float64():
             stack.append(families.FoldedLinear(torch.from_numpy(W), torch.from_numpy(b), True, matmul="bf16x3"))
             Ws.append((W.astype(np.float64), b.astype(np.float64)))
             k = nw
+        stack = families.Stack(stack)
         assert families.wide3_fits(stack) and not families.chain4_fits(stack)
         feats = rng.standard_normal((Bq, Nsrc, C)).astype(np.float32)
         xyz = rng.standard_normal((Bq, Nsrc, 3)).astype(np.float32)
         idx_np = rng.integers(-1, Nsrc, (Bq, Mq, ns))
         f, z, idx = torch.from_numpy(feats).cuda(), torch.from_numpy(xyz).cuda(), torch.from_numpy(idx_np).cuda()
-        got = families.stack_max_gather(stack, f, z, idx, {}).cpu().numpy()
+        got = families.stack_max_gather(stack, f, z, idx).cpu().numpy()
         src, Cc = families.padded_rows(f, z)
         rows = Bq * Mq * ns
-        pl = stack[0].planes_gather(src, Cc, idx)
+        pl = stack[0].planes(src, rows, idx=idx)
         for layer in stack[1:-1]:
             pl = layer.planes(pl, rows, 0)
         ref = stack[-1].planes(pl, rows, 2, ns).cpu().numpy()

@@ -156,15 +156,14 @@ def main():
             W = torch.from_numpy((rng.standard_normal((nw, kk)) / np.sqrt(kk)).astype(np.float32))
             out.append(families.FoldedLinear(W, torch.zeros(nw), True, matmul="bf16x3"))
             kk = nw
-        return out
+        return families.Stack(out)
     for name, k0, widths, npoint, ns, nsrc in (("sa1 3-3-64-64-128, 32 samples", 3, (3, 64, 64, 128), 512, 32, 512),
                                                 ("sa2 131-128-128-128-256, 64 samples", 131, (128, 128, 128, 256), 128, 64, 512)):
         st = stack(widths, k0)
         feats = torch.randn(PB, nsrc, k0 - 3, device=dev) if k0 > 3 else None
         xyz_s = torch.rand(PB, nsrc, 3, device=dev)
         idx = torch.randint(0, nsrc, (PB, npoint, ns), device=dev)
-        cache = {}
-        ms = timed(lambda: families.stack_max_gather(st, feats, xyz_s, idx, cache), args.iters)
+        ms = timed(lambda: families.stack_max_gather(st, feats, xyz_s, idx), args.iters)
         fl = 2.0 * PB * npoint * ns * sum(l.N * l.K for l in st)
         row(f"planes_chain4 (gather inside) {name}", ms, "mfma", fl, "TFLOP/s", round(MFMA_B3_PEAK, 1),
             "pointnet_sa_module.py:73-91 in one kernel; algorithmic flops of the unpadded layers")
@@ -192,9 +191,9 @@ def main():
         del src
         if epi == 3:
             member = (torch.rand(M_, device=dev) < 0.9).to(torch.uint8)
-            ms = timed(lambda: lyr.planes_h2(pin, M_, 2, group=128, dyn=dyn1, member=member), args.iters)
+            ms = timed(lambda: lyr.planes(pin, M_, 2, 128, member=member, ar="f16x2", dyn=dyn1), args.iters)
         else:
-            ms = timed(lambda: lyr.planes_h2(pin, M_, epi, 0, sig_next=lyr.h2["sig"], dyn=dyn1), args.iters)
+            ms = timed(lambda: lyr.planes(pin, M_, epi, 0, ar="f16x2", sig_next=lyr.h2["sig"], dyn=dyn1), args.iters)
         row(f"planes_gemm f16x2 {K_}->{N_} on {M_} rows ({what})", ms, "mfma", 2.0 * M_ * K_ * N_, "TFLOP/s", round(MFMA_H2_PEAK, 1),
             "csrc/planes.hip <2>: three fp16 MFMA products per fp32 product; 4 B per activation in" +
             (" and out" if epi == 0 else ", fp32 rows out" if epi == 1 else ", one fp32 row per 128 out"))
@@ -202,10 +201,10 @@ def main():
     for name, k0, widths, nsrc in (("sa1 3-3-64-64-128", 3, (3, 64, 64, 128), 512), ("sa2 131-128-128-128-256", 131, (128, 128, 128, 256), 512)):
         st = stack(widths, k0)
         families.h2_prepare_stack(st, np.concatenate([np.zeros(k0 - 3), -np.ones(3)]), np.ones(k0))
-        mod = families.PointnetSAModule(nsrc, 0.2, 32, list(widths), True, k0 - 3)
         f2 = torch.rand(PB * nsrc, k0 - 3, device=dev) if k0 > 3 else None
         x2 = torch.rand(PB * nsrc, 3, device=dev)
-        ms = timed(lambda: mod._run_dedup_h2(st, f2, x2, PB * nsrc, k0 - 3, (dyn1, None)), args.iters)
+        ms = timed(lambda: families.run_planes(st, families.group_planes(f2, x2, ar="f16x2", sig=st[0].h2["sig"], dyn=dyn1)[0], PB * nsrc,
+                                               ar="f16x2", dyn=dyn1), args.iters)
         row(f"rows -> planes + planes_chain4 f16x2 {name} on {PB * nsrc} source rows", ms, "mfma", 2.0 * PB * nsrc * sum(l.N * l.K for l in st), "TFLOP/s",
             round(MFMA_H2_PEAK, 1), "the stack once per SOURCE row (PointnetSAModule.dedup), fp32 rows out; algorithmic flops of the unpadded layers")
     # ---- round 3: PointnetSAModule on source rows (families.PointnetSAModule.dedup): the group maxima and FoldingNet's per-point update
