@@ -116,6 +116,29 @@ PCCX_API int pccx_nn_dist_split_count(int B, int P, int Q);
 PCCX_API int pccx_nn_dist_split(const float *X, int B, int P, const float *Y, int Q, int split, float *scratch_d, int32_t *scratch_nn,
                                 float *d2, int32_t *nn, void *stream);
 
+/* Exact nearest-neighbour search through a uniform grid index, for whole rooms (10^5 .. 10^6 points) where the all-pairs kernels
+ * above cost P * Q pairs: what open3d's KDTreeFlann.search_knn_vector_3d answers in eval.py:55-81 (30-NN for the normals, 1-NN for
+ * D1 / D2) and pytorch3d.ops.knn_points in eval.py:132.  Results are bit for bit those of pccx_nn_dist / pccx_knn: same fp32
+ * distance expression, ties to the lower index (csrc/grid_nn.hip carries the argument).
+ * pccx_grid_dims: the grid a cloud of N points with bounding-box extents (ex, ey, ez) gets -- dims[3] cells per axis and the cubic
+ * cell's side; host only, a pure function (about 2 points per cell of the box, at most 2^21 cells and 1024 per axis; an axis of no
+ * extent has one cell).  pccx_grid_index_workspace_bytes / pccx_grid_query_workspace_bytes: host only; 0 for an empty batch.
+ * pccx_grid_index_build: the index of Y (B,N,3) into `workspace` (16-byte aligned, kept by the caller for as long as the index is
+ * queried; Y itself is not read again): bounding box and grid per cloud on the device, pccx_sort_keys_u64 over (cloud, cell) keys,
+ * the points in that order and a cell-start table.  B <= 65535, B * N < 2^31. */
+PCCX_API int pccx_grid_dims(int N, float ex, float ey, float ez, int32_t *dims, float *cell);
+PCCX_API size_t pccx_grid_index_workspace_bytes(int B, int N);
+PCCX_API size_t pccx_grid_query_workspace_bytes(int B, int M);
+PCCX_API int pccx_grid_index_build(const float *Y, int B, int N, void *workspace, void *stream);
+/* pccx_nn_dist(X, Y) through the index of Y (B,Q,3): d2 (B,P) f32, nn (B,P) int32 or NULL.  query_workspace:
+ * pccx_grid_query_workspace_bytes(B, P) bytes of scratch, 16-byte aligned.  Stands in for the KD-tree's 1-NN of eval.py:73-81. */
+PCCX_API int pccx_grid_nn(const float *X, int B, int P, int Q, const void *index, void *query_workspace, float *d2, int32_t *nn,
+                          void *stream);
+/* pccx_knn(q, ref) through the index of ref (B,N,3), 1 <= K <= min(N, 32): dists (B,M,K) f32 and idx (B,M,K) int64, ascending by
+ * (distance, index).  Stands in for search_knn_vector_3d(knn=30) of eval.py:59-60 and knn_points of eval.py:132 at room size. */
+PCCX_API int pccx_grid_knn(const float *q, int B, int M, int N, int K, const void *index, void *query_workspace, float *dists,
+                           int64_t *idx, void *stream);
+
 /* chamfer_distance's value from the two pccx_nn_dist passes dxy (B,P), dyx (B,Q) (pytorch3d defaults: point and batch mean, both
  * directions summed; AE.py:67): out[0] = batch mean of (mean_p dxy + mean_q dyx), accumulated in double */
 PCCX_API int pccx_chamfer_mean(const float *dxy, const float *dyx, int B, int P, int Q, float *out, void *stream);

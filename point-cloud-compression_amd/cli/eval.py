@@ -20,14 +20,41 @@ parser.add_argument('--compressed_path', default='./data/ModelNet40_K256_compres
 parser.add_argument('--decompressed_path', default='./data/ModelNet40_K256_decompressed/')
 parser.add_argument('--output_file', default='./eval/ModelNet40_K256.csv')
 parser.add_argument('--device', default='cuda')
+parser.add_argument('--search', choices=['brute', 'grid'], default='brute',
+                    help='nearest-neighbour search of the metrics: all-pairs kernels (files of at most 32768 points), or the exact grid index '
+                         '(same values, files of any size)')
 
 
-def calc_uc(input_pc, decomp_pc):
-    """eval.py:127-151: variance ratio of nearest-neighbour distances inside the 1024-NN region of point 0."""
+KNN_POINTS_MAX = 32768          # reference points pccx_knn takes (csrc/knn.hip)
+
+
+def region_of_point0(pc, K, search='brute', chunk=KNN_POINTS_MAX):
+    """The K points nearest to point 0 of pc (1,N,3), as offsets from point 0: (1,K,3), nearest first (eval.py:130-136).  One query with K = 1024
+    is a single scan of the cloud, beyond the grid walk's K <= 32, so it stays with knn_points.  That kernel takes at most `chunk`
+    reference points; search='grid' lifts the limit by chunks: the K nearest of every chunk of the cloud, then the K nearest among those
+    candidates, again by chunks while they are too many.  The same points in the same order as one scan would give: each pair keeps
+    its fp32 distance, a chunk's candidates come out ascending by (distance, index) and the chunks follow in index order, so a tie
+    between candidates still goes to the lower index of the cloud."""
+    centre = pc[:, :1].contiguous()
+    if search == 'grid':
+        while pc.shape[1] > chunk:
+            if chunk < 2 * K:
+                raise ValueError(f"region_of_point0: chunks of {chunk} points cannot narrow a search for {K}")
+            parts = pc.split(chunk, dim=1)
+            pc = torch.cat([ops.knn_points(centre, p.contiguous(), min(K, p.shape[1]), return_dists=False, return_idx=False).knn[:, 0]
+                            for p in parts], dim=1)
+    return ops.knn_points(centre, pc, K, patch_scale=1.0).knn[:, 0]
+
+
+def calc_uc(input_pc, decomp_pc, search='brute'):
+    """eval.py:127-151: variance ratio of nearest-neighbour distances inside the 1024-NN region of point 0.  search='grid' finds the
+    region in clouds of any size (region_of_point0) and takes the 2-NN inside it from the index; 'brute' is limited to
+    KNN_POINTS_MAX points by knn_points."""
     def nn_var(pc):
         K = min(1024, pc.shape[1])
-        region = ops.knn_points(pc[:, :1].contiguous(), pc, K, patch_scale=1.0).knn[:, 0]   # (1,K,3), centred on point 0 (:130-136)
-        d2 = ops.knn_points(region, region, 2).dists[..., 1]                        # nearest other point (:138-144)
+        region = region_of_point0(pc, K, search)                                    # (1,K,3), centred on point 0
+        nn2 = ops.GridIndex(region).knn(region, 2) if search == 'grid' else ops.knn_points(region, region, 2)
+        d2 = nn2.dists[..., 1]                                                      # nearest other point (:138-144)
         return torch.sqrt(d2).double().var(unbiased=False)
     return float(nn_var(decomp_pc) / nn_var(input_pc))
 
@@ -47,10 +74,11 @@ def main():
         a = torch.from_numpy(plyio.read_point_cloud(f))[None].to(args.device)
         b = torch.from_numpy(plyio.read_point_cloud(decomp_f))[None].to(args.device)
         bits = sum(os.stat(os.path.join(args.compressed_path, name + e)).st_size * 8 for e in ('.s.bin', '.p.bin', '.c.bin'))
-        rows.append(dict(filename=name, p2pointPSNR=round(float(codec.d1_psnr(a, b)[0]), 3), p2planePSNR=round(float(codec.d2_psnr(a, b)[0]), 3),
-                         chamfer_distance=float(codec.normalized_chamfer(a, b)[0]), n_points_input=a.shape[1],
+        rows.append(dict(filename=name, p2pointPSNR=round(float(codec.d1_psnr(a, b, search=args.search)[0]), 3),
+                         p2planePSNR=round(float(codec.d2_psnr(a, b, search=args.search)[0]), 3),
+                         chamfer_distance=float(codec.normalized_chamfer(a, b, search=args.search)[0]), n_points_input=a.shape[1],
                          n_points_output=b.shape[1], bpp=bits / a.shape[1],                 # eval.py:189
-                         **{'uniformity coefficient': round(calc_uc(a, b), 3)}))
+                         **{'uniformity coefficient': round(calc_uc(a, b, args.search), 3)}))
     if world > 1:                                            # per-file rows travel to rank 0 (a few hundred bytes per file)
         import torch.distributed as tdist
         gathered = [None] * world

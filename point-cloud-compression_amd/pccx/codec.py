@@ -257,30 +257,35 @@ class Codec:
                                   matmul=self.decoder_matmul, group=self.group_duplicates)
 
 
-def d1_psnr(orig, recon):
+def d1_psnr(orig, recon, search=None, index=None):
     """eval.py:43-98 D1 (point-to-point) PSNR, batched: 10*log10(diag^2 / mean_recon min_orig |.|^2),
-    diag = bounding-box diagonal of the original.  (B,N,3),(B,M,3) -> (B,) f64."""
-    d2 = ops.nn_dist(recon, orig).double()
+    diag = bounding-box diagonal of the original.  (B,N,3),(B,M,3) -> (B,) f64.  search="grid": the nearest original through an
+    ops.GridIndex of the original (``index``: one the caller already built), same value."""
+    d2 = ops.nn_dist(recon, index if search == "grid" and index is not None else orig, search=search).double()
     mse = d2.mean(dim=1)
     rng = orig.amax(dim=1).double() - orig.amin(dim=1).double()
     diag2 = (rng * rng).sum(dim=1)
     return 10 * torch.log10(diag2 / mse)
 
 
-def d2_psnr(orig, recon, knn=30):
+def d2_psnr(orig, recon, knn=30, search=None, index=None):
     """eval.py:43-98 D2 (point-to-plane) PSNR: normals of the ORIGINAL by 30-NN PCA, error = squared
-    projection of (recon - nearest original) on that normal.  (B,) f64."""
-    normals = ops.estimate_normals(orig, knn)
-    mse = ops.point_plane_err(recon, orig, normals).double().mean(dim=1)
+    projection of (recon - nearest original) on that normal.  (B,) f64.  search="grid": ONE ops.GridIndex of the original
+    (``index``, or built here) serves the normals' 30-NN and the nearest-original lookup, same value."""
+    if search == "grid" and index is None:
+        index = ops.GridIndex(orig)
+    normals = ops.estimate_normals(orig, knn, search=search, index=index)
+    mse = ops.point_plane_err(recon, orig, normals, search=search, index=index).double().mean(dim=1)
     rng = orig.amax(dim=1).double() - orig.amin(dim=1).double()
     return 10 * torch.log10((rng * rng).sum(dim=1) / mse)
 
 
-def normalized_chamfer(orig, recon):
+def normalized_chamfer(orig, recon, search=None):
     """eval.py:198-205: both clouds min-max normalised by the ORIGINAL's global min/max, then
-    pytorch3d chamfer_distance.  Returns (B,) f64."""
+    pytorch3d chamfer_distance.  Returns (B,) f64.  search="grid": both directions through an ops.GridIndex of the normalised
+    clouds, same value."""
     lo = orig.amin(dim=(1, 2), keepdim=True)
     hi = orig.amax(dim=(1, 2), keepdim=True)
     a = ((orig - lo) / (hi - lo)).contiguous()
     b = ((recon - lo) / (hi - lo)).contiguous()
-    return ops.nn_dist(b, a).double().mean(dim=1) + ops.nn_dist(a, b).double().mean(dim=1)
+    return ops.nn_dist(b, a, search=search).double().mean(dim=1) + ops.nn_dist(a, b, search=search).double().mean(dim=1)

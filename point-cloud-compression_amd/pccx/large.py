@@ -236,3 +236,24 @@ def decompress_large_many(codec, parts, metas, block=8192, outs=None, S=64):
             _, _, order, n = metas[ci]
             unsplit_blocks(rec[slot:slot + cnt], [j0 + q * stride for q in range(cnt)], order, n, block, outs[ci])
     return outs
+
+
+def evaluate_large(orig, recon, knn=30):
+    """Whole-room quality of a reconstruction: orig (N,3), recon (M,3) on the GPU -> dict of Python floats: d1_psnr, d2_psnr, chamfer
+    (the normalised one of eval.py:198-205), n_points_input, n_points_output -- eval.py:43-98,198-205 over the room as ONE cloud (a
+    reconstructed point's nearest original may lie in a neighbouring block, so per-block figures are not the room's).  Every search goes
+    through ops.GridIndex, exact: the values equal codec.d1_psnr / d2_psnr / normalized_chamfer on the same clouds.  One index of the
+    original serves D1 and D2 (30-NN normals and nearest original); the Chamfer distance is defined on the min-max-normalised clouds,
+    so each of its two directions builds the index of its normalised target.
+    Single rank only: with world > 1 a rank's decompress_large holds only its own blocks' rows, and bringing the room together in one
+    place is the caller's business -- nothing is exchanged here."""
+    from . import codec, ops
+    a = _f32c(orig, "evaluate_large.orig").reshape(1, -1, 3)
+    b = _f32c(recon, "evaluate_large.recon").reshape(1, -1, 3)
+    index = ops.GridIndex(a)
+    d1 = codec.d1_psnr(a, b, search="grid", index=index)
+    d2 = codec.d2_psnr(a, b, knn=knn, search="grid", index=index)
+    del index
+    ch = codec.normalized_chamfer(a, b, search="grid")
+    return dict(d1_psnr=float(d1[0]), d2_psnr=float(d2[0]), chamfer=float(ch[0]), n_points_input=float(a.shape[1]),
+                n_points_output=float(b.shape[1]))

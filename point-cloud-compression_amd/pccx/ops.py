@@ -206,8 +206,66 @@ def ball_query(p1, p2, K, radius, method="auto", extent=1.0):
     return KNN(dists, idx, None)
 
 
-def nn_dist(x, y, return_idx=False):
-    """min_j |x_i - y_j|^2 for every i: (B,P,3),(B,Q,3) -> (B,P) [, idx (B,P) int32]."""
+def _search(search, who):
+    """search=None / "brute": the all-pairs kernels; "grid": through a GridIndex.  Anything else is an error."""
+    if search is None or search == "brute":
+        return False
+    if search == "grid":
+        return True
+    raise ValueError(f"{who}: search must be None, 'brute' or 'grid', got {search!r}")
+
+
+class GridIndex:
+    """Exact grid index over the reference clouds y (B,Q,3) (csrc/grid_nn.hip): built once, queried any number of times.  .nn and
+    .knn return what nn_dist and knn_points return for the same clouds, bit for bit (same fp32 distances, ties to the lower index);
+    they stand in for open3d's KDTreeFlann.search_knn_vector_3d (eval.py:55-81) at sizes where the all-pairs scans cost P * Q pairs.
+    The index keeps its own copy of the points in cell order, so y need not stay alive."""
+
+    def __init__(self, y):
+        y = _f32c(y, "GridIndex.y")
+        if y.dim() != 3 or y.shape[2] != 3:
+            raise _lib.PccxError(f"GridIndex: expected (B,Q,3), got {tuple(y.shape)}")
+        self.B, self.Q = int(y.shape[0]), int(y.shape[1])
+        self.device = y.device
+        self.ws = torch.empty(max(int(_lib.load().pccx_grid_index_workspace_bytes(self.B, self.Q)), 16), device=y.device, dtype=torch.uint8)
+        with stage("grid_index"):
+            _lib.call("pccx_grid_index_build", y.data_ptr(), self.B, self.Q, self.ws.data_ptr(), _stream())
+
+    def _queries(self, x, who):
+        x = _f32c(x, who)
+        if x.dim() != 3 or x.shape[2] != 3 or x.shape[0] != self.B or x.device != self.device:
+            raise _lib.PccxError(f"{who}: expected ({self.B},P,3) on {self.device}, got {tuple(x.shape)} on {x.device}")
+        qws = torch.empty(max(int(_lib.load().pccx_grid_query_workspace_bytes(self.B, int(x.shape[1]))), 16), device=x.device, dtype=torch.uint8)
+        return x, qws
+
+    def nn(self, x, return_idx=False):
+        """nn_dist(x, y, return_idx) through the index."""
+        x, qws = self._queries(x, "GridIndex.nn")
+        P = int(x.shape[1])
+        d2 = torch.empty(self.B, P, device=x.device, dtype=torch.float32)
+        nn = torch.empty(self.B, P, device=x.device, dtype=torch.int32) if return_idx else None
+        with stage("grid_nn"):
+            _lib.call("pccx_grid_nn", x.data_ptr(), self.B, P, self.Q, self.ws.data_ptr(), qws.data_ptr(), d2.data_ptr(),
+                      nn.data_ptr() if nn is not None else None, _stream())
+        return (d2, nn) if return_idx else d2
+
+    def knn(self, x, K):
+        """knn_points(x, y, K, return_nn=False) through the index, 1 <= K <= min(Q, 32): KNN(dists, idx, None)."""
+        x, qws = self._queries(x, "GridIndex.knn")
+        M = int(x.shape[1])
+        dists = torch.empty(self.B, M, int(K), device=x.device, dtype=torch.float32)
+        idx = torch.empty(self.B, M, int(K), device=x.device, dtype=torch.int64)
+        with stage("grid_knn"):
+            _lib.call("pccx_grid_knn", x.data_ptr(), self.B, M, self.Q, int(K), self.ws.data_ptr(), qws.data_ptr(), dists.data_ptr(),
+                      idx.data_ptr(), _stream())
+        return KNN(dists, idx, None)
+
+
+def nn_dist(x, y, return_idx=False, search=None):
+    """min_j |x_i - y_j|^2 for every i: (B,P,3),(B,Q,3) -> (B,P) [, idx (B,P) int32].  search="grid": through a GridIndex of y
+    (y may be that index itself), same results."""
+    if _search(search, "nn_dist"):
+        return (y if isinstance(y, GridIndex) else GridIndex(y)).nn(x, return_idx)
     x, y = _f32c(x, "nn_dist.x"), _f32c(y, "nn_dist.y")
     B, P, _ = x.shape
     d2 = torch.empty(B, P, device=x.device, dtype=torch.float32)
@@ -225,21 +283,28 @@ def nn_dist(x, y, return_idx=False):
     return (d2, nn) if return_idx else d2
 
 
-def estimate_normals(xyz, knn=30):
-    """open3d estimate_normals(KDTreeSearchParamKNN(knn)) (eval.py:59-60): unoriented PCA normals (B,N,3)."""
+def estimate_normals(xyz, knn=30, search=None, index=None):
+    """open3d estimate_normals(KDTreeSearchParamKNN(knn)) (eval.py:59-60): unoriented PCA normals (B,N,3).  search="grid": the
+    neighbours come from a GridIndex of xyz (``index``: one the caller already built over xyz), same normals."""
+    grid = _search(search, "estimate_normals")
     xyz = _f32c(xyz, "estimate_normals")
     B, N, _ = xyz.shape
-    idx = knn_points(xyz, xyz, min(knn, N), return_nn=False).idx
+    if grid:
+        idx = (index if index is not None else GridIndex(xyz)).knn(xyz, min(knn, N)).idx
+    else:
+        idx = knn_points(xyz, xyz, min(knn, N), return_nn=False).idx
     out = torch.empty(B, N, 3, device=xyz.device, dtype=torch.float32)
     _lib.call("pccx_estimate_normals", xyz.data_ptr(), B, N, idx.data_ptr(), idx.shape[2], out.data_ptr(), _stream())
     return out
 
 
-def point_plane_err(x, y, normals_y):
-    """Squared projection of (x - nearest y) on that y's normal, eval.py:79-81: (B,P)."""
+def point_plane_err(x, y, normals_y, search=None, index=None):
+    """Squared projection of (x - nearest y) on that y's normal, eval.py:79-81: (B,P).  search="grid": the nearest y through a
+    GridIndex of y (``index``: one already built), same values."""
+    grid = _search(search, "point_plane_err")
     x, y, normals_y = _f32c(x, "point_plane_err.x"), _f32c(y, "point_plane_err.y"), _f32c(normals_y, "point_plane_err.n")
     B, P, _ = x.shape
-    _, nn = nn_dist(x, y, return_idx=True)
+    _, nn = (index if index is not None else GridIndex(y)).nn(x, return_idx=True) if grid else nn_dist(x, y, return_idx=True)
     err = torch.empty(B, P, device=x.device, dtype=torch.float32)
     _lib.call("pccx_point_plane_err", x.data_ptr(), B, P, y.data_ptr(), normals_y.data_ptr(), y.shape[1], nn.data_ptr(),
               err.data_ptr(), _stream())
