@@ -67,8 +67,9 @@
 #define DEC_STREAM_CHUNKS (2 * ((DEC_STREAM_FRAGS + 2 * DEC_WS_CHUNK - 1) / (2 * DEC_WS_CHUNK)))
 #define DEC_G_W(k) (DEC_G_B + (k) * 128)
 #define DEC_BLOB_FLOATS(k) (DEC_G_W(k) + (size_t)(k) * DEC_STREAM_CHUNKS * DEC_WS_CHUNK * 256)
+#define DEC_GROUP 64                      // blocks of 128 patches per group of the decoders' block order (dec_main_kernel, all three arithmetics)
 
-// ---- bf16x3 mode: decoder GEMM as fp32 products of three bf16 pieces per operand (decoder.hip, dec_main_kernel<true>).
+// ---- bf16x3 mode: decoder GEMM as fp32 products of three bf16 pieces per operand (decoder.hip, dec_main_kernel_b3).
 // Per point p: [32 k-steps of 32][8 m-tiles][3 planes hi/mid/lo] bf16 A fragments of v_mfma_f32_16x16x32_bf16
 // (1 KiB each: lane (m = lane%16, kg = lane/16) holds 8 bf16 of k-slots 8*kg + j <-> channel 32t + 16*(j>>2) + 4*kg + (j&3),
 // the order in which two fp32 C tiles concatenate), then the inv_mlp layers in the same form (L0 [5][8][3] with the odd ninth

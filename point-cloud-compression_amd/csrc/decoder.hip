@@ -10,13 +10,15 @@
 //                     accumulators feed inv_mlp directly from registers (n index = patch).  The
 //                     (BS,16384) activation of the reference never exists in memory.
 // MFMA-bound; weights (64 MiB) and activations stream from L2 / Infinity Cache as 1 KiB fragments.
-// dec_main_kernel<true> is the bf16x3 variant (the host layer's default mode); <false> is the exact-fp32 product.
+// dec_main_kernel is the exact-fp32 product; dec_main_kernel_b3 the bf16x3 variant, whose GEMM is the plane-ring
+// loop of plane_ring.h -- the one k loop, with its named-set counted waits, that planes.hip and decoder_h2.hip run too.
 #include <math.h>
 #include <stdlib.h>
 
 #include "blobs.h"
 #include "common.h"
 #include "mfma_chain.h"
+#include "plane_ring.h"
 
 // uniq / n_uniq (patch_groups.hip; null = every patch): slot `patch` of the tiles holds patch uniq[patch], *n_uniq slots are live;
 // `ntiles` stays the host's tile count of all P patches, the stride of the fragment arrays
@@ -62,11 +64,6 @@ int pccx_dec_head_launch(const float *latent_q, int P, int d, int ntiles, const 
     return PCCX_OK;
 }
 
-#ifndef DEC_GROUP
-#define DEC_GROUP 64                       // patch blocks per group of the block order (dec_main_kernel)
-#endif
-
-
 // ---- bf16x3 operands: x = hi + mid + lo exactly, each a bf16 (round to nearest even)
 __device__ __forceinline__ unsigned b3_rne(float x)
 {
@@ -107,23 +104,44 @@ __global__ __launch_bounds__(256) void b3_split_kernel(const f32x4 *__restrict__
     d[128] = make_uint4(l[0] | (l[1] << 16), l[2] | (l[3] << 16), l[4] | (l[5] << 16), l[6] | (l[7] << 16));
 }
 
-__device__ __forceinline__ uint4 b3_load_async(const uint4 *p)    // placed exactly here; completion is covered by the ring's s_waitcnt
+// ---- epilogue of both kernels below: rows 0..2 of the last tile (g == 0, r = 0..2) are x,y,z of (patch, point p)
+template <int NT>
+__device__ __forceinline__ void dec_store_points(const f32x4 (&m3)[NT][1], int tile0, int ntiles, int g, int n, int P, int k, int p,
+                                                 float *__restrict__ patches_out, float inv_scale_div, const float *__restrict__ centres,
+                                                 const float *__restrict__ nrm_center, const float *__restrict__ nrm_longest, int S,
+                                                 float one_minus_margin, float *__restrict__ pc_out)
 {
-    uint4 v;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-    return v;
+    if (g != 0) return;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int patch = (tile0 + nt) * 16 + n;
+        if (tile0 + nt < ntiles && patch < P) {
+            float v[3] = {m3[nt][0][0], m3[nt][0][1], m3[nt][0][2]};
+            if (patches_out) {
+                float *o = patches_out + ((size_t)patch * k + p) * 3;       // new_xyz.transpose(2,1)
+                o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
+            }
+            if (pc_out) {
+                const int b = patch / S;
+                const float lg = nrm_longest[b];
+                float *o = pc_out + ((size_t)patch * k + p) * 3;            // (B, S*k, 3): index s*k + p
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    float t = __fdiv_rn(v[a], inv_scale_div);                            // decompress.py:107
+                    t = __fadd_rn(t, centres[(size_t)patch * 3 + a]);                     // decompress.py:110
+                    t = __fsub_rn(t, 0.5f);                                               // pn_kit.py:63
+                    t = __fdiv_rn(__fmul_rn(t, lg), one_minus_margin);                   // pn_kit.py:64
+                    o[a] = __fadd_rn(t, nrm_center[3 * b + a]);                           // pn_kit.py:65
+                }
+            }
+        }
+    }
 }
 
-// grid: x = patch block (8 n-tiles = 128 patches), y = point p.  4 waves, wave w owns n-tiles 2w, 2w+1.
-// B3 = false: exact fp32 MFMA GEMM (the product path).  B3 = true (the bf16x3 mode): the K = 1024 GEMM runs as six
-// v_mfma_f32_16x16x32_bf16 passes over pre-split operands (blob3 / h2p hold bf16 planes) and inv_mlp as a bf16x3 chain on registers.
-// NT = patch tiles per wave.  2 (the default): two workgroups of four waves per CU, two waves per SIMD.  4 (bf16x3 only): ONE wave per
-// SIMD on the 512-register budget, a workgroup covers 256 patches -- point p's weight stream enters LDS and is read from it half as
-// often per MFMA (the untried lever of round 2's review; selected with PCCX_DEC_NT=4, measured in DESIGN.md section 4).
-template <bool B3, int NT = 2>
-__global__ __launch_bounds__(256, NT == 2 ? 2 : 1) void dec_main_kernel(const f32x4 *__restrict__ h2p, const float *__restrict__ latent_q,
+// grid: x = patch block (8 n-tiles = 128 patches), y = point p.  4 waves, wave w owns n-tiles 2w, 2w+1.  The exact fp32 MFMA GEMM
+// (the product path of --matmul f32); two workgroups of four waves per CU.
+__global__ __launch_bounds__(256, 2) void dec_main_kernel(const f32x4 *__restrict__ h2p, const float *__restrict__ latent_q,
                                                           int P, int d, int k, int ntiles, const float *__restrict__ blob,
-                                                          const float *__restrict__ blob3,
                                                           float *__restrict__ patches_out, float inv_scale_div,
                                                           const float *__restrict__ centres, const float *__restrict__ nrm_center,
                                                           const float *__restrict__ nrm_longest, int S, float one_minus_margin,
@@ -135,33 +153,24 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 1) void dec_main_kernel(const f3
     // the group.  Consecutive workgroups share point p's weight stream (L2), and a group's activation fragments
     // (DEC_GROUP x 8 tiles, 32-48 MB) stay in the Infinity Cache while all k points sweep over them, instead of the whole
     // activation array being re-streamed from HBM once per point.
-    constexpr int GRP = DEC_GROUP * 2 / NT;                   // patch blocks per group: the same number of PATCHES per group for any NT
-    const int nblk = (ntiles + 4 * NT - 1) / (4 * NT);
-    const int grp = blockIdx.x / (GRP * k), rem = blockIdx.x % (GRP * k);
-    const int p = rem / GRP, blk = grp * GRP + rem % GRP;
+    const int nblk = (ntiles + 7) / 8;
+    const int grp = blockIdx.x / (DEC_GROUP * k), rem = blockIdx.x % (DEC_GROUP * k);
+    const int p = rem / DEC_GROUP, blk = grp * DEC_GROUP + rem % DEC_GROUP;
     if (blk >= nblk) return;                                  // whole workgroup (before any barrier)
-    const int tile0 = blk * 4 * NT + NT * w;
-    constexpr int CH = B3 ? DEC_B3_CHUNK : DEC_WS_CHUNK;
-    constexpr int NB = B3 ? 4 : 2;                                        // ring depth: B3 chunks are short, their DMA needs 3 chunks of lead
-    __shared__ __attribute__((aligned(16))) f32x4 swt[NB * CH * 64];     // ring: one k-tile (8 m-tiles) per chunk; B3: 4 m-tiles x 3 planes
+    const int tile0 = blk * 8 + 2 * w;
+    __shared__ __attribute__((aligned(16))) f32x4 swt[2 * DEC_WS_CHUNK * 64];     // ring: one k-tile (8 m-tiles) per chunk
     const int wu = __builtin_amdgcn_readfirstlane(w);
-    const WStreamT<CH, NB> ws{B3 ? blob3 + (size_t)p * DEC_B3_STREAM_CHUNKS * DEC_B3_CHUNK * 256
-                             : blob + DEC_G_W(k) + (size_t)p * DEC_STREAM_CHUNKS * DEC_WS_CHUNK * 256,
-                          swt, B3 ? DEC_B3_STREAM_CHUNKS : DEC_STREAM_CHUNKS, lane, wu, false};
+    const WStreamT<DEC_WS_CHUNK, 2> ws{blob + DEC_G_W(k) + (size_t)p * DEC_STREAM_CHUNKS * DEC_WS_CHUNK * 256, swt, DEC_STREAM_CHUNKS, lane, wu, false};
     ws.prologue();
 
-    f32x4 acc[NT][8];
+    f32x4 acc[2][8];
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) {
         const f32x4 b = *(const f32x4 *)(blob + DEC_G_B + p * 128 + 16 * mt + 4 * g);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[nt][mt] = b;
+        acc[0][mt] = b; acc[1][mt] = b;
     }
-    int tq[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) tq[nt] = tile0 + nt < ntiles ? tile0 + nt : ntiles - 1;
-    const int t0 = tq[0], t1 = tq[NT > 1 ? 1 : 0];
-    if constexpr (!B3) {
+    const int t0 = tile0 < ntiles ? tile0 : ntiles - 1, t1 = tile0 + 1 < ntiles ? tile0 + 1 : ntiles - 1;
+    {
         // ---- GEMM over K = 1024 (64 k-tiles).  A (weights of point p, shared by the 4 waves) comes through
         // the LDS ring one chunk (2 k-tiles) ahead; B (this wave's 2 patch tiles) is prefetched one k-tile
         // ahead from global.
@@ -193,75 +202,9 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 1) void dec_main_kernel(const f3
                 b_cur[0] = b_nxt[0]; b_cur[1] = b_nxt[1];
             }
         }
-    } else {
-        // ---- GEMM over K = 1024 as 32 k-steps of 32.  A planes come through the 4-deep LDS ring (chunk = 4 m-tiles x 3
-        // planes, DMA three chunks ahead); the B planes of this wave's two patch tiles sit in three rotating register sets,
-        // loaded two k-steps ahead by asm loads whose completion rides on the ring's waits.  VMEM issue order per wave:
-        //   boundary(2t):   DMA(2t+3) [3 loads], B(t+2) [6 loads]        boundary(2t+1): DMA(2t+4) [3 loads]
-        // so boundary(2t) needs all but its 12 youngest loads (DMA(2t) was issued at boundary(2t-3), B(t) at 2t-4) and
-        // boundary(2t+1) all but its 18 youngest; loads complete in order.
-        const uint4 *h3 = (const uint4 *)h2p;
-        uint4 bs[3][NT][3];
-        auto load_b = [&](uint4 (&dst)[NT][3], int t) {
-            const int tc = t < 32 ? t : 31;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) dst[nt][pl] = b3_load_async(h3 + (((size_t)tc * ntiles + tq[nt]) * 3 + pl) * 64 + lane);
-        };
-        auto kstep = [&](int t, const uint4 (&bc)[NT][3], uint4 (&bload)[NT][3], bool first) {
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const int c = 2 * t + half;
-                if (half == 0) {
-                    if (first) ws.boundary(c); else ws.template boundary_keep<6 + 3 * NT>(c);      // NT = 2: 12 youngest may fly
-                    load_b(bload, t + 2);
-                } else
-                    ws.template boundary_keep<6 + 6 * NT>(c);                                       // NT = 2: 18
-                const f32x4 *buf = ws.chunk(c);
-                bf16x8 a[4][3];
-#pragma unroll
-                for (int mq = 0; mq < 4; ++mq)
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) a[mq][pl] = __builtin_bit_cast(bf16x8, buf[(mq * 3 + pl) * 64]);
-                __builtin_amdgcn_sched_barrier(0);
-                // six products, smallest first: (lo,hi) (hi,lo) (mid,mid) (mid,hi) (hi,mid) (hi,hi)
-                constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-                for (int q = 0; q < 6; ++q)
-#pragma unroll
-                    for (int mq = 0; mq < 4; ++mq)
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt)
-                            acc[nt][4 * half + mq] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                                a[mq][PA[q]], __builtin_bit_cast(bf16x8, bc[nt][PB[q]]), acc[nt][4 * half + mq], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        load_b(bs[0], 0);
-        load_b(bs[1], 1);
-        kstep(0, bs[0], bs[2], true);                     // boundary(0) waits for everything issued so far
-        kstep(1, bs[1], bs[0], false);
-#pragma unroll 1
-        for (int t = 2; t < 32; t += 3) {                 // t = 2, 5, ..., 29: three k-steps per trip, static register sets
-            kstep(t, bs[2], bs[1], false);
-            kstep(t + 1, bs[0], bs[2], false);
-            kstep(t + 2, bs[1], bs[0], false);
-        }
-        // The last B loads (k-steps 32 and 33, clamped, unused) are still in flight.  Their registers are dead to the compiler, which is
-        // free to reuse them -- and to hoist register-only work of the tail above a bare wait: a build of the f16x2 form of this kernel (decoder_h2.hip) with a larger
-        // ring chunk did exactly that and had its tail's operands overwritten by the late loads (tools/asm_load_lint.py finds it).
-        // Naming the registers after the wait keeps them allocated until the loads have landed.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) asm volatile("" ::"v"(__builtin_bit_cast(f32x4, bs[i][nt][pl])));
     }
-    f32x4 m3[NT][1];
-    if constexpr (!B3) {
+    f32x4 m3[2][1];
+    {
         // ---- inv_mlp on registers: channels 0..127 = relu(inv_pool.4) of point p, 128..143 = latent
         f32x4 in[2][9];
 #pragma unroll
@@ -278,7 +221,7 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 1) void dec_main_kernel(const f3
         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
             for (int mt = 0; mt < 8; ++mt) m0[nt][mt] = *(const f32x4 *)(blob + DEC_M_B0 + 16 * mt + 4 * g);
-        int f = B3 ? DEC_B3_GEMM_FRAGS : DEC_STREAM_GEMM_FRAGS;   // the inv_mlp fragments follow in the same LDS ring
+        int f = DEC_STREAM_GEMM_FRAGS;                     // the inv_mlp fragments follow in the same LDS ring
         dense_acc_stream<9, 8, 2>(ws, f, in, m0);
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt)
@@ -307,10 +250,56 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 1) void dec_main_kernel(const f3
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) m3[nt][0] = *(const f32x4 *)(blob + DEC_M_B3 + 4 * g);
         dense_acc_stream<2, 1, 2>(ws, f, m2, m3);          // last layer: no ReLU (AE.py:27)
-    } else {
+    }
+    ws.drain();
+    dec_store_points<2>(m3, tile0, ntiles, g, n, P, k, p, patches_out, inv_scale_div, centres, nrm_center, nrm_longest, S, one_minus_margin, pc_out);
+}
+
+// The bf16x3 mode: the K = 1024 GEMM as six v_mfma_f32_16x16x32_bf16 passes over pre-split operands (blob3 / h3
+// hold bf16 planes) in the shared plane-ring loop (plane_ring.h: 32 k-steps, ring chunk = 4 m-tiles x 3 planes, three register sets), and
+// inv_mlp as a bf16x3 chain on registers.  Grid and block order as dec_main_kernel.
+// NT = patch tiles per wave.  2 (the default): two workgroups of four waves per CU, two waves per SIMD.  4: ONE wave per SIMD on the
+// 512-register budget, a workgroup covers 256 patches -- point p's weight stream enters LDS and is read from it half as often per MFMA
+// (the untried lever of round 2's review; selected with PCCX_DEC_NT=4, measured in DESIGN.md section 4).
+template <int NT>
+__global__ __launch_bounds__(256, NT == 2 ? 2 : 1) void dec_main_kernel_b3(const uint4 *__restrict__ h3, const float *__restrict__ latent_q,
+                                                          int P, int d, int k, int ntiles, const float *__restrict__ blob,
+                                                          const float *__restrict__ blob3,
+                                                          float *__restrict__ patches_out, float inv_scale_div,
+                                                          const float *__restrict__ centres, const float *__restrict__ nrm_center,
+                                                          const float *__restrict__ nrm_longest, int S, float one_minus_margin,
+                                                          float *__restrict__ pc_out)
+{
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int g = lane >> 4, n = lane & 15;
+    constexpr int GRP = DEC_GROUP * 2 / NT;                   // patch blocks per group: the same number of PATCHES per group for any NT
+    const int nblk = (ntiles + 4 * NT - 1) / (4 * NT);
+    const int grp = blockIdx.x / (GRP * k), rem = blockIdx.x % (GRP * k);
+    const int p = rem / GRP, blk = grp * GRP + rem % GRP;
+    if (blk >= nblk) return;                                  // whole workgroup (before any barrier)
+    const int tile0 = blk * 4 * NT + NT * w;
+    __shared__ __attribute__((aligned(16))) f32x4 swt[4 * DEC_B3_CHUNK * 64];     // ring of four chunks: their DMA needs 3 chunks of lead
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    const WStreamT<DEC_B3_CHUNK, 4> ws{blob3 + (size_t)p * DEC_B3_STREAM_CHUNKS * DEC_B3_CHUNK * 256, swt, DEC_B3_STREAM_CHUNKS, lane, wu, false};
+    ws.prologue();
+
+    f32x4 acc[NT][8];
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) {
+        const f32x4 b = *(const f32x4 *)(blob + DEC_G_B + p * 128 + 16 * mt + 4 * g);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[nt][mt] = b;
+    }
+    int tq[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) tq[nt] = tile0 + nt < ntiles ? tile0 + nt : ntiles - 1;
+    pg_ring_gemm<3, NT, 3, 4, 2, true, 32, false>(
+        ws, 32, [&](int nt, int pl, int t) { return h3 + (((size_t)t * ntiles + tq[nt]) * 3 + pl) * 64 + lane; }, 1.f, acc);
+    f32x4 m3[NT][1];
+    {
         // ---- inv_mlp as a bf16x3 chain: every layer's input is split in registers (relu, then three bf16 planes per pair
         // of 16-channel tiles); the ninth input tile (the latent) pairs with zeros.
-        int f = DEC_B3_GEMM_FRAGS;
+        int f = DEC_B3_GEMM_FRAGS;                         // the inv_mlp fragments follow in the same LDS ring
         bf16x8 i0[NT][5][3];
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -359,34 +348,7 @@ __global__ __launch_bounds__(256, NT == 2 ? 2 : 1) void dec_main_kernel(const f3
         dense_b3_stream<1, 1, NT>(ws, f, i3, m3);          // last layer: no ReLU (AE.py:27)
     }
     ws.drain();
-
-    // ---- epilogue: rows 0..2 of the last tile (g == 0, r = 0..2) are x,y,z of (patch, point p)
-    if (g == 0) {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int patch = (tile0 + nt) * 16 + n;
-            if (tile0 + nt < ntiles && patch < P) {
-                float v[3] = {m3[nt][0][0], m3[nt][0][1], m3[nt][0][2]};
-                if (patches_out) {
-                    float *o = patches_out + ((size_t)patch * k + p) * 3;       // new_xyz.transpose(2,1)
-                    o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
-                }
-                if (pc_out) {
-                    const int b = patch / S;
-                    const float lg = nrm_longest[b];
-                    float *o = pc_out + ((size_t)patch * k + p) * 3;            // (B, S*k, 3): index s*k + p
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) {
-                        float t = __fdiv_rn(v[a], inv_scale_div);                            // decompress.py:107
-                        t = __fadd_rn(t, centres[(size_t)patch * 3 + a]);                     // decompress.py:110
-                        t = __fsub_rn(t, 0.5f);                                               // pn_kit.py:63
-                        t = __fdiv_rn(__fmul_rn(t, lg), one_minus_margin);                   // pn_kit.py:64
-                        o[a] = __fadd_rn(t, nrm_center[3 * b + a]);                           // pn_kit.py:65
-                    }
-                }
-            }
-        }
-    }
+    dec_store_points<NT>(m3, tile0, ntiles, g, n, P, k, p, patches_out, inv_scale_div, centres, nrm_center, nrm_longest, S, one_minus_margin, pc_out);
 }
 
 static unsigned dec_grid(int ntiles, int k, int NT = 2)
@@ -418,9 +380,8 @@ extern "C" int pccx_ae_decode(const float *latent_q, int P, int d, int k, const 
     hipLaunchKernelGGL(dec_head_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, st, latent_q, P, d, ntiles, dec_blob,
                        (f32x4 *)workspace, (const int *)nullptr, (const int *)nullptr);
     PCCX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dec_main_kernel<false>, dim3(dec_grid(ntiles, k)), dim3(256), 0, st, (const f32x4 *)workspace, latent_q, P, d,
-                       k, ntiles, dec_blob, (const float *)nullptr, patches_out, scale, centres, nrm_center, nrm_longest,
-                       S > 0 ? S : 1, (float)(1.0 - margin), pc_out);
+    hipLaunchKernelGGL(dec_main_kernel, dim3(dec_grid(ntiles, k)), dim3(256), 0, st, (const f32x4 *)workspace, latent_q, P, d,
+                       k, ntiles, dec_blob, patches_out, scale, centres, nrm_center, nrm_longest, S > 0 ? S : 1, (float)(1.0 - margin), pc_out);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }
@@ -521,13 +482,14 @@ extern "C" int pccx_ae_decode_b3(const float *latent_q, int P, int d, int k, con
     hipLaunchKernelGGL(b3_split_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, (const f32x4 *)h2p, h3, 1, 64, ntiles,
                        (size_t)0, (size_t)0, ntiles);
     PCCX_CHECK_LAUNCH();
-    static const int dec_nt = []() { const char *e = getenv("PCCX_DEC_NT"); return e && atoi(e) == 4 ? 4 : 2; }();
-    if (dec_nt == 4)
-        hipLaunchKernelGGL((dec_main_kernel<true, 4>), dim3(dec_grid(ntiles, k, 4)), dim3(256), 0, st, (const f32x4 *)h3, latent_q, P, d, k,
+    // two patch tiles per wave unless PCCX_DEC_NT=4 asks for the four-tile form (same results; read per call for A/B and tests)
+    const char *e = getenv("PCCX_DEC_NT");
+    if (e && atoi(e) == 4)
+        hipLaunchKernelGGL((dec_main_kernel_b3<4>), dim3(dec_grid(ntiles, k, 4)), dim3(256), 0, st, (const uint4 *)h3, latent_q, P, d, k,
                            ntiles, dec_blob, b3_blob, patches_out, scale, centres, nrm_center, nrm_longest, S > 0 ? S : 1,
                            (float)(1.0 - margin), pc_out);
     else
-        hipLaunchKernelGGL((dec_main_kernel<true, 2>), dim3(dec_grid(ntiles, k)), dim3(256), 0, st, (const f32x4 *)h3, latent_q, P, d, k,
+        hipLaunchKernelGGL((dec_main_kernel_b3<2>), dim3(dec_grid(ntiles, k)), dim3(256), 0, st, (const uint4 *)h3, latent_q, P, d, k,
                            ntiles, dec_blob, b3_blob, patches_out, scale, centres, nrm_center, nrm_longest, S > 0 ? S : 1,
                            (float)(1.0 - margin), pc_out);
     PCCX_CHECK_LAUNCH();

@@ -1,6 +1,7 @@
 // decoder_h2.hip -- the synthesis transform of AE.AE (AE.py:48-53; decompress.py:97-116) in f16x2 arithmetic.
 // Same structure as decoder.hip's bf16x3 form: dec_head_kernel (fp32, unchanged) -> operand preparation -> dec_main: the
 // 1024 -> k*128 Linear as a GEMM whose accumulators feed inv_mlp from registers, point p's weight stream through an LDS-DMA ring.
+// The GEMM is the plane-ring loop of plane_ring.h, the one k loop (with its named-set counted waits) of planes.hip and decoder.hip too.
 // What differs is the arithmetic of the products: two fp16 pieces per operand and three v_mfma_f32_16x16x32_f16 passes
 // (mfma_chain.h, "f16x2 operands") with the static power-of-two scales of pack_h2.hip, plus ONE dynamic scale per patch:
 //   s_n = 2^-e <= 1 with max(largest head activation, largest |latent|) * s_n <= 1   (dec_h2_prep_kernel)
@@ -12,13 +13,10 @@
 #include "blobs.h"
 #include "common.h"
 #include "mfma_chain.h"
+#include "plane_ring.h"
 
 int pccx_dec_head_launch(const float *latent_q, int P, int d, int ntiles, const float *dec_blob, float *h2p, const int32_t *uniq,
                          const int32_t *n_uniq, hipStream_t st);   // decoder.hip
-
-#ifndef DEC_GROUP
-#define DEC_GROUP 64                       // patch blocks per group of the block order (as decoder.hip)
-#endif
 
 // one wave per tile of 16 patches: the patch scales, then the two fp16 planes of the head activation
 // h2p: [64 kt][ntiles][64 lanes] f32x4 (lane (g, n): channels 16 kt + 4 g + r of patch n); h3: [32 t][ntiles][2][64 lanes] uint4
@@ -56,13 +54,6 @@ __global__ __launch_bounds__(256) void dec_h2_prep_kernel(const f32x4 *__restric
     }
 }
 
-__device__ __forceinline__ uint4 h2_load_async(const uint4 *p)    // placed exactly here; completion is covered by the ring's s_waitcnt
-{
-    uint4 v;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-    return v;
-}
-
 // grid: groups of DEC_GROUP patch blocks outermost, then the point p, then the block inside the group (decoder.hip); 4 waves, wave w
 // owns patch tiles NT w .. NT w + NT - 1 of its block.
 // NT = 2: the shape of decoder.hip's bf16x3 kernel.  NT = 4 (the default): FOUR patch tiles per wave in the GEMM -- every weight block read
@@ -94,7 +85,6 @@ __global__ __launch_bounds__(256, 2) void dec_main_h2_kernel(const uint4 *__rest
     if (blk >= nblk) return;                                  // whole workgroup (before any barrier)
     const int tile0 = blk * 4 * NT + NT * w;
     constexpr int CH = DEC_H2_CHUNK, NB = 4;
-    constexpr int DPW = CH / 4;                               // DMA loads per wave per chunk
     __shared__ __attribute__((aligned(16))) f32x4 swt[NB * CH * 64];
     const int wu = __builtin_amdgcn_readfirstlane(w);
     const WStreamT<CH, NB> ws{hb + DEC_H2_G_W(k) + (size_t)p * DEC_H2_STREAM_CHUNKS * DEC_H2_CHUNK * 256, swt, DEC_H2_STREAM_CHUNKS, lane, wu, false};
@@ -107,97 +97,21 @@ __global__ __launch_bounds__(256, 2) void dec_main_h2_kernel(const uint4 *__rest
         tq[nt] = tile0 + nt < ntl ? tile0 + nt : ntl - 1;
         sn[nt] = pscale[tq[nt] * 16 + n];
     }
-    f32x4 acc[NP][2][8];
+    f32x4 acc[NT][8];
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) {
         const f32x4 b = *(const f32x4 *)(hb + DEC_H2_G_B + (size_t)p * 128 + 16 * mt + 4 * g);
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[nt >> 1][nt & 1][mt] = b * sn[nt];
+        for (int nt = 0; nt < NT; ++nt) acc[nt][mt] = b * sn[nt];
     }
-    {
-        // ---- GEMM over K = 1024 as 32 k-steps of 32.  A planes through the 4-deep LDS ring (chunk = 4 m-tiles x 2 planes, DMA
-        // three chunks ahead); the B planes of this wave's patch tiles in SETS rotating register sets, loaded SETS - 1 k-steps ahead by
-        // asm loads whose completion rides on the ring's waits.  VMEM issue order per wave:
-        //   boundary(2t):   DMA(2t+3) [DPW loads], B(t + SETS - 1) [2 NT loads]        boundary(2t+1): DMA(2t+4) [DPW loads]
-        // three sets: boundary(2t) needs all but its 2 DPW + 2 NT youngest loads, boundary(2t+1) all but its 2 DPW + 4 NT youngest;
-        // two sets:   boundary(2t) needs B(t), issued one k-step ago: all but the DPW loads of DMA(2t+2); boundary(2t+1) as above.
-        uint4 bs[SETS][NT][2];
-        auto load_b = [&](uint4 (&dst)[NT][2], int t) {
-            const int tc = t < 32 ? t : 31;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) dst[nt][pl] = h2_load_async(h3 + (((size_t)tc * ntiles + tq[nt]) * 2 + pl) * 64 + lane);
-        };
-        auto kstep = [&](int t, const uint4 (&bc)[NT][2], uint4 (&bload)[NT][2], bool first) {
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const int c = 2 * t + half;
-                if (half == 0) {
-                    if (first) ws.boundary(c); else ws.template boundary_keep<SETS == 3 ? 2 * DPW + 2 * NT : DPW>(c);
-                    load_b(bload, t + SETS - 1);
-                } else
-                    ws.template boundary_keep<2 * DPW + 4 * NT>(c);
-                const f32x4 *buf = ws.chunk(c);
-                f16x8 a[4][2];
-#pragma unroll
-                for (int mq = 0; mq < 4; ++mq)
-#pragma unroll
-                    for (int pl = 0; pl < 2; ++pl) a[mq][pl] = __builtin_bit_cast(f16x8, buf[(mq * 2 + pl) * 64]);
-                __builtin_amdgcn_sched_barrier(0);
-                constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};          // (lo,hi) (hi,lo) (hi,hi)
-#pragma unroll
-                for (int q = 0; q < 3; ++q)
-#pragma unroll
-                    for (int mq = 0; mq < 4; ++mq)
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt)
-                            acc[nt >> 1][nt & 1][4 * half + mq] =
-                                H2_MFMA(a[mq][PA[q]], __builtin_bit_cast(f16x8, bc[nt][PB[q]]), acc[nt >> 1][nt & 1][4 * half + mq]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        if constexpr (SETS == 3) {
-            load_b(bs[0], 0);
-            load_b(bs[1], 1);
-            kstep(0, bs[0], bs[2], true);                     // boundary(0) waits for everything issued so far
-            kstep(1, bs[1], bs[0], false);
-#pragma unroll 1
-            for (int t = 2; t < 32; t += 3) {                 // t = 2, 5, ..., 29: three k-steps per trip, static register sets
-                kstep(t, bs[2], bs[1], false);
-                kstep(t + 1, bs[0], bs[2], false);
-                kstep(t + 2, bs[1], bs[0], false);
-            }
-        } else {
-            load_b(bs[0], 0);
-            kstep(0, bs[0], bs[1], true);
-            kstep(1, bs[1], bs[0], false);
-#pragma unroll 1
-            for (int t = 2; t < 32; t += 2) {                 // two k-steps per trip, static register sets
-                kstep(t, bs[0], bs[1], false);
-                kstep(t + 1, bs[1], bs[0], false);
-            }
-        }
-        // The last B loads (clamped, unused) are still in flight.  Their registers are dead to the compiler, which is
-        // free to reuse them -- and to hoist register-only work of the tail above a bare wait: a build of this kernel with a larger
-        // ring chunk did exactly that and had its tail's operands overwritten by the late loads (tools/asm_load_lint.py finds it).
-        // Naming the registers after the wait keeps them allocated until the loads have landed.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int i = 0; i < SETS; ++i)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl) asm volatile("" ::"v"(__builtin_bit_cast(f32x4, bs[i][nt][pl])));
-    }
+    // ---- GEMM over K = 1024: the plane-ring loop (plane_ring.h), 32 k-steps, ring chunk = 4 m-tiles x 2 planes, SETS rotating B register sets
+    pg_ring_gemm<2, NT, SETS, 4, 2, true, 32, false>(
+        ws, 32, [&](int nt, int pl, int t) { return h3 + (((size_t)t * ntiles + tq[nt]) * 2 + pl) * 64 + lane; }, 1.f, acc);
     // ---- inv_mlp as an f16x2 chain on registers, two tiles at a time: channels 0..127 = relu(inv_pool.4) of point p, 128..143 = latent.
     // Pair pr reads the tail's fragments from their pr-th copy in the stream, which simply continues.
     // Everything the tail needs per lane (tile and patch indices, bias / latent / output addresses, the patch scales) is derived HERE from a
     // laundered thread id and re-read from L2, not carried through the GEMM loop: the loop holds 224 registers of accumulators and operand
     // planes, and values computed in the prologue for the tail were spilled around it (41 VGPRs, 152 B of scratch per lane, round 3).
-#ifdef DEC_TAIL_PRIO                 // experiment knob (round 4): issue priority of the VALU-heavy tail over the other workgroup's GEMM waves
-    __builtin_amdgcn_s_setprio(DEC_TAIL_PRIO);
-#endif
     int lane_t = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     asm volatile("" : "+v"(lane_t));
     const int g_t = lane_t >> 4, n_t = lane_t & 15;
@@ -231,7 +145,7 @@ __global__ __launch_bounds__(256, 2) void dec_main_h2_kernel(const uint4 *__rest
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
 #pragma unroll
-                for (int t = 0; t < 4; ++t) h2_split8(relu4(acc[pr][nt][2 * t]), relu4(acc[pr][nt][2 * t + 1]), rho0, i0[nt][t]);
+                for (int t = 0; t < 4; ++t) h2_split8(relu4(acc[2 * pr + nt][2 * t]), relu4(acc[2 * pr + nt][2 * t + 1]), rho0, i0[nt][t]);
                 const int patch = (tile0_t + 2 * pr + nt) * 16 + n_t;
                 const int src = patch < P_t ? (uniq ? uniq[patch] : patch) : 0;
                 f32x4 lat;

@@ -12,8 +12,8 @@
 //                         + split  ->  planes of the first layer; without indices: fp32 rows -> planes.
 //   planes_gemm_kernel  : one layer.  Workgroup = 128 rows x (16*MB) output channels, 4 waves x (2 row tiles x MB m-tiles);
 //                         the weight planes of the m-block stream through a 4-deep LDS-DMA ring shared by the waves, the B
-//                         planes of the wave's two tiles are loaded two k-steps ahead into rotating register sets (the scheme
-//                         of dec_main_kernel<true>, decoder.hip).  Epilogues: planes (bias + ReLU + split), fp32 rows, or the
+//                         planes of the wave's two tiles are loaded two k-steps ahead into rotating register sets (the k loop
+//                         of plane_ring.h, which the decoders run too).  Epilogues: planes (bias + ReLU + split), fp32 rows, or the
 //                         max over groups of `group` consecutive rows (torch.max over nsample, pointnet_sa_module.py:91).
 // MFMA-bound for K, N >= 256; narrower layers are bound by the 6 bytes per activation they read and write.
 #include <math.h>
@@ -21,29 +21,10 @@
 
 #include "common.h"
 #include "mfma_chain.h"
+#include "plane_ring.h"
 
 #define PG_NB 4                          // ring depth (DMA three chunks ahead)
 
-// The arithmetic of a planes kernel: P = 3 -> bf16x3 (three bf16 planes per operand, six products), P = 2 -> f16x2 (two fp16 planes of the
-// operand times an exact power of two, three products; mfma_chain.h).  A ring chunk holds 4 m-tiles x P planes (1 KiB fragments), so a wave
-// issues P DMA loads per chunk and 2 P plane loads per k-step: the counted waits below are written in terms of P.
-template <int P> struct PgArith;
-template <> struct PgArith<3> {
-    typedef bf16x8 vec;
-    static constexpr int NQ = 6;
-    static __device__ __forceinline__ constexpr int pa(int q) { return q == 0 ? 2 : (q == 1 ? 0 : (q == 2 ? 1 : (q == 3 ? 1 : 0))); }   // (lo,hi) (hi,lo) (mid,mid)
-    static __device__ __forceinline__ constexpr int pb(int q) { return q == 0 ? 0 : (q == 1 ? 2 : (q == 2 ? 1 : (q == 3 ? 0 : (q == 4 ? 1 : 0)))); }   // (mid,hi) (hi,mid) (hi,hi)
-    static __device__ __forceinline__ void split(const f32x4 &a, const f32x4 &b, float, vec (&pl)[3]) { b3_split8(a, b, pl); }
-    static __device__ __forceinline__ f32x4 mfma(const vec &a, const vec &b, const f32x4 &c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct PgArith<2> {
-    typedef f16x8 vec;
-    static constexpr int NQ = 3;
-    static __device__ __forceinline__ constexpr int pa(int q) { return q == 0 ? 1 : 0; }      // smallest first: (lo,hi) (hi,lo) (hi,hi)
-    static __device__ __forceinline__ constexpr int pb(int q) { return q == 1 ? 1 : 0; }
-    static __device__ __forceinline__ void split(const f32x4 &a, const f32x4 &b, float rho, vec (&pl)[2]) { h2_split8(a, b, rho, pl); }
-    static __device__ __forceinline__ f32x4 mfma(const vec &a, const vec &b, const f32x4 &c) { return H2_MFMA(a, b, c); }
-};
 // f16x2 only: the stack's dynamic input normalisation (pccx_dyn_scale): dyn[0] = s, a power of two with |input| s <= 1, dyn[1] = 1 / s.
 // Conv / ReLU stacks are positively homogeneous in (input, biases): the kernels multiply the gathered input and every bias by s and the
 // stack's final rows by 1 / s, so the static interval bounds of the layers (for inputs of magnitude <= 1) hold whatever the data.
@@ -396,85 +377,37 @@ extern "C" int pccx_pack_linear_h2(const float *wp_dev, int N, int K, float tau,
 }
 
 // ---- one layer ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint4 pg_load_async(const uint4 *p)    // placed exactly here; completion rides on the ring's s_waitcnt
-{
-    uint4 v;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-    return v;
-}
-
-// The end of a layer-0 k loop: wait for every load still in flight -- the B loads of the last two (clamped, unused) k-steps among them --
-// with the three rotating register sets named as read-write operands of the wait.  The compiler does not know that an asm load's
-// result arrives later: on paths where a set's value is dead (a layer with one or two k-steps never reads the third set) it would
-// hand the registers to something else while the load is still in flight, and the data landing afterwards would overwrite that
-// something (found by tools/asm_load_lint.py on the f16x2 chain of sa1, one k-step: the next layer's operand planes were built in
-// those registers -- results changed from call to call).  Tied to the wait, the sets stay allocated until their loads have landed.
-typedef unsigned int pg_u32x4 __attribute__((ext_vector_type(4)));
-#define PG_R(x) __builtin_bit_cast(pg_u32x4, x)
-#define PG_SETS2(bs)                                                                                                                          \
-    "v"(PG_R(bs[0][0][0])), "v"(PG_R(bs[0][0][1])), "v"(PG_R(bs[0][1][0])), "v"(PG_R(bs[0][1][1])), "v"(PG_R(bs[1][0][0])),                     \
-        "v"(PG_R(bs[1][0][1])), "v"(PG_R(bs[1][1][0])), "v"(PG_R(bs[1][1][1])), "v"(PG_R(bs[2][0][0])), "v"(PG_R(bs[2][0][1])),                 \
-        "v"(PG_R(bs[2][1][0])), "v"(PG_R(bs[2][1][1]))
-#define PG_SETS3(bs)                                                                                                                          \
-    "v"(PG_R(bs[0][0][0])), "v"(PG_R(bs[0][0][1])), "v"(PG_R(bs[0][0][2])), "v"(PG_R(bs[0][1][0])), "v"(PG_R(bs[0][1][1])),                     \
-        "v"(PG_R(bs[0][1][2])), "v"(PG_R(bs[1][0][0])), "v"(PG_R(bs[1][0][1])), "v"(PG_R(bs[1][0][2])), "v"(PG_R(bs[1][1][0])),                 \
-        "v"(PG_R(bs[1][1][1])), "v"(PG_R(bs[1][1][2])), "v"(PG_R(bs[2][0][0])), "v"(PG_R(bs[2][0][1])), "v"(PG_R(bs[2][0][2])),                 \
-        "v"(PG_R(bs[2][1][0])), "v"(PG_R(bs[2][1][1])), "v"(PG_R(bs[2][1][2]))
-// inputs only (as native vectors: a HIP_vector_type is an aggregate the constraint cannot take): the statement READS the sets, so their
-// values (as the compiler sees them) must still sit in their registers here
-template <int NBV>
-__device__ __forceinline__ void pg_drain_loads(const uint4 (&bs)[3][2][NBV])
-{
-    if constexpr (NBV == 2) asm volatile("s_waitcnt vmcnt(0)" ::PG_SETS2(bs) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::PG_SETS3(bs) : "memory");
-}
-// A counted wait that covers the register set about to be CONSUMED: the set goes through the statement as read-write operands, so no
-// instruction that uses the loaded values can be scheduled above the wait (a "memory" clobber does not order register arithmetic: the
-// compiler hoisted a conversion of gathered rows above a bare s_waitcnt once the register allocation shifted), and the registers stay
-// allocated to the set until it.  Sets still in flight are untouched until their own wait (or the final drain) names them.
-template <int N, int NBV>
-__device__ __forceinline__ void pg_wait_set(uint4 (&b)[2][NBV])
-{
-    pg_u32x4 r00 = PG_R(b[0][0]), r01 = PG_R(b[0][1]), r10 = PG_R(b[1][0]), r11 = PG_R(b[1][1]);
-    if constexpr (NBV == 2) {
-        asm volatile("s_waitcnt vmcnt(%4)" : "+v"(r00), "+v"(r01), "+v"(r10), "+v"(r11) : "n"(N) : "memory");
-    } else {
-        pg_u32x4 r02 = PG_R(b[0][2]), r12 = PG_R(b[1][2]);
-        asm volatile("s_waitcnt vmcnt(%6)" : "+v"(r00), "+v"(r01), "+v"(r02), "+v"(r10), "+v"(r11), "+v"(r12) : "n"(N) : "memory");
-        b[0][2] = __builtin_bit_cast(uint4, r02);
-        b[1][2] = __builtin_bit_cast(uint4, r12);
-    }
-    b[0][0] = __builtin_bit_cast(uint4, r00);
-    b[0][1] = __builtin_bit_cast(uint4, r01);
-    b[1][0] = __builtin_bit_cast(uint4, r10);
-    b[1][1] = __builtin_bit_cast(uint4, r11);
-}
-#undef PG_SETS2
-#undef PG_SETS3
-#undef PG_R
-
-// The barrier of a ring boundary WITHOUT __syncthreads()' fences.  The release fence in __syncthreads() makes the compiler wait for
-// EVERY outstanding vector-memory operation (s_waitcnt vmcnt(0)) in front of the s_barrier -- LDS-DMA fills are tracked by vmcnt and
-// write LDS, so it cannot tell them from the plane loads -- which throws away the counted waits above it: the plane loads of k-step
-// t + 2 and the ring fills of the next chunks, issued to stay in flight across the boundary, were all drained at every boundary
-// (matrix pipe 0.43 busy in the 512 -> 1024 layer).  What the protocol needs is already explicit: each wave's counted wait covers its own
-// pieces of chunk c (in-order completion), the barrier then says everyone's have landed and everyone has finished reading chunk c - 1
-// (those reads feed MFMAs issued before the barrier; the compiler's own lgkmcnt wait for them precedes their use).
-// BARE = false keeps __syncthreads(): the bf16x3 forms, the one-chunk forms and the chains gain nothing measurable from the bare barrier,
-// and with the compiler's drain in place tools/asm_load_lint.py can check them.
-template <bool BARE>
-__device__ __forceinline__ void pg_ring_barrier()
-{
-    if constexpr (BARE) {
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    } else {
-        __syncthreads();
-    }
-}
-
 enum { PG_EPI_PLANES = 0, PG_EPI_ROWS = 1, PG_EPI_MAX = 2 };
+
+// The B operand of a layer's k loop (pg_ring_gemm) for the wave's two row tiles t0, t1: operand planes [t][tile][plane][lane], or --
+// GATHER -- bin = fp32 source rows (n_src per batch, ldp = 32 * KT32 floats, zero padded): row r reads source row
+// (r / rows_per_batch) * n_src + max(idx[r], 0) (pointnet_sa_module.py:27,73-83), lane (g, n) the channels 32 t + 16 pl + 4 g .. + 3 of
+// row n of the tile, split in registers at use.
+template <int P, bool GATHER>
+struct PgBSource {
+    const uint4 *bin, *gsrc[2] = {nullptr, nullptr};
+    long long ntiles, t0, t1;
+    int lane;
+    __device__ __forceinline__ PgBSource(const uint4 *bin_, const int64_t *idx, long long rows_per_batch, long long n_src, int ldp, long long M,
+                                         long long ntiles_, long long t0_, long long t1_, int lane_)
+        : bin(bin_), ntiles(ntiles_), t0(t0_), t1(t1_), lane(lane_)
+    {
+        if constexpr (GATHER) {
+            const int g = lane >> 4, n = lane & 15;
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                long long r = (nt ? t1 : t0) * 16 + n;
+                if (r >= M) r = M - 1;
+                const long long j = idx[r];
+                gsrc[nt] = (const uint4 *)((const float *)bin + (size_t)((r / rows_per_batch) * n_src + (j < 0 ? 0 : j)) * ldp + 4 * g);
+            }
+        }
+    }
+    __device__ __forceinline__ const uint4 *operator()(int nt, int pl, int t) const
+    {
+        return GATHER ? gsrc[nt] + 8 * t + 4 * pl : bin + (((size_t)t * ntiles + (nt ? t1 : t0)) * P + pl) * 64 + lane;
+    }
+};
 
 // P = 2 (f16x2): the accumulators are sigma_in tau (W y + b s); `bias` holds sigma_in tau b, rho_in = sigma_in scales gathered rows,
 // scale_out = sigma_next / (sigma_in tau) for the planes epilogue, 1 / (sigma_in tau) for the row / max epilogues (times 1 / s there).
@@ -496,7 +429,6 @@ __global__ __launch_bounds__(256, 2) void planes_gemm_kernel(const uint4 *__rest
     constexpr int MQC = (P == 2 && MB == 8) ? 8 : 4;
     constexpr int PG_CHUNK = MQC * P;
     constexpr int NBUF = MQC == 8 ? 3 : PG_NB;                 // ring depth
-    constexpr int DMA = PG_CHUNK / 4;                          // LDS-DMA loads per wave and chunk
     constexpr int HALVES = MB / MQC;                           // ring chunks per k-step
     const float dyn_s = P == 2 ? pg_dyn(dyn, 0) : 1.f;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -514,11 +446,8 @@ __global__ __launch_bounds__(256, 2) void planes_gemm_kernel(const uint4 *__rest
     const int wu = __builtin_amdgcn_readfirstlane(w);
     const int nch = HALVES * KT32;
     const WStreamT<PG_CHUNK, NBUF> ws{wstream + (size_t)mb * nch * PG_CHUNK * 256, swt, nch, lane, wu, false};
-    // DMA of chunk c (a chunk past the end re-reads chunk 0 into a free buffer, so every boundary issues the same loads and
-    // the counted waits below hold to the last k-step)
-    auto dma = [&](int c) { ws.issue(c < nch ? c : 0, c % NBUF); };
 #pragma unroll
-    for (int c = 0; c < NBUF - 1; ++c) dma(c);
+    for (int c = 0; c < NBUF - 1; ++c) pg_ring_issue(ws, c);
 
     f32x4 acc[2][MB];
 #pragma unroll
@@ -532,92 +461,8 @@ __global__ __launch_bounds__(256, 2) void planes_gemm_kernel(const uint4 *__rest
         acc[0][mt] = b; acc[1][mt] = b;
     }
     const long long t0 = tile0 < ntiles ? tile0 : ntiles - 1, t1 = tile0 + 1 < ntiles ? tile0 + 1 : ntiles - 1;
-    {
-        // VMEM issue order per wave and k-step t:  HALVES = 2:  boundary(2t): DMA(2t+3) [DMA], B(t+2) [2 P];  boundary(2t+1): DMA(2t+4) [DMA]
-        //                                          HALVES = 1:  boundary(t):  DMA(t+NBUF-1) [DMA],  B(t+2) [2 P]
-        // loads complete in order, so boundary(c) may leave in flight everything issued after the youngest load it needs.
-        // GATHER: bin = fp32 source rows (n_src per batch, ldp = 32 * KT32 floats, zero padded); row r reads source row
-        // (r / rows_per_batch) * n_src + max(idx[r], 0) and is split in registers at use (4 loads per k-step instead of 6).
-        constexpr int NBL = GATHER ? 4 : 2 * P, NBV = GATHER ? 2 : P;
-        const float rho_g = rho_in * dyn_s;
-        uint4 bs[3][2][NBV];
-        const uint4 *gsrc[2] = {nullptr, nullptr};
-        if constexpr (GATHER) {
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                long long r = (nt ? t1 : t0) * 16 + n;
-                if (r >= M) r = M - 1;
-                const long long j = idx[r];
-                gsrc[nt] = (const uint4 *)((const float *)bin + (size_t)((r / rows_per_batch) * n_src + (j < 0 ? 0 : j)) * ldp + 4 * g);
-            }
-        }
-        auto load_b = [&](uint4 (&dst)[2][NBV], int t) {
-            const int tc = t < KT32 ? t : KT32 - 1;
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int pl = 0; pl < NBV; ++pl)
-                    dst[nt][pl] = GATHER ? pg_load_async(gsrc[nt] + 8 * tc + 4 * pl)
-                                         : pg_load_async(bin + (((size_t)tc * ntiles + (nt ? t1 : t0)) * P + pl) * 64 + lane);
-        };
-        auto kstep = [&](int t, uint4 (&braw)[2][NBV], uint4 (&bload)[2][NBV], bool first) {
-            avec bc[2][P];
-#pragma unroll
-            for (int half = 0; half < HALVES; ++half) {
-                const int c = HALVES * t + half;
-                if (half == 0) {
-                    if (first) pg_wait_set<0, NBV>(braw);
-                    else if (HALVES == 2) pg_wait_set<2 * DMA + NBL, NBV>(braw);
-                    else pg_wait_set<DMA + NBL, NBV>(braw);
-                    pg_ring_barrier<P == 2 && MB == 8>();
-                    dma(c + NBUF - 1);
-                    load_b(bload, t + 2);
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) {
-                        if constexpr (GATHER)
-                            AR::split(__builtin_bit_cast(f32x4, braw[nt][0]), __builtin_bit_cast(f32x4, braw[nt][1]), rho_g, bc[nt]);
-                        else
-#pragma unroll
-                            for (int pl = 0; pl < P; ++pl) bc[nt][pl] = __builtin_bit_cast(avec, braw[nt][pl < NBV ? pl : 0]);
-                    }
-                } else {
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * DMA + 2 * NBL) : "memory");
-                    pg_ring_barrier<P == 2 && MB == 8>();
-                    dma(c + NBUF - 1);
-                }
-                const f32x4 *buf = ws.chunk(c);
-#pragma unroll
-                for (int sub = 0; sub < MQC / 4; ++sub) {
-                    avec a[4][P];
-#pragma unroll
-                    for (int mq = 0; mq < 4; ++mq)
-#pragma unroll
-                        for (int pl = 0; pl < P; ++pl) a[mq][pl] = __builtin_bit_cast(avec, buf[((4 * sub + mq) * P + pl) * 64]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    // the products, smallest first (bf16x3: (lo,hi) (hi,lo) (mid,mid) (mid,hi) (hi,mid) (hi,hi); f16x2: (lo,hi) (hi,lo) (hi,hi))
-#pragma unroll
-                    for (int q = 0; q < AR::NQ; ++q)
-#pragma unroll
-                        for (int mq = 0; mq < 4; ++mq)
-#pragma unroll
-                            for (int nt = 0; nt < 2; ++nt)
-                                acc[nt][MQC * half + 4 * sub + mq] = AR::mfma(a[mq][AR::pa(q)], bc[nt][AR::pb(q)], acc[nt][MQC * half + 4 * sub + mq]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        };
-        load_b(bs[0], 0);
-        load_b(bs[1], 1);
-        kstep(0, bs[0], bs[2], true);                     // waits for everything issued so far
-        if (KT32 > 1) kstep(1, bs[1], bs[0], false);
-#pragma unroll 1
-        for (int t = 2; t < KT32; t += 3) {               // three k-steps per trip: static register sets
-            kstep(t, bs[2], bs[1], false);
-            if (t + 1 < KT32) kstep(t + 1, bs[0], bs[2], false);
-            if (t + 2 < KT32) kstep(t + 2, bs[1], bs[0], false);
-        }
-        pg_drain_loads<NBV>(bs);                                          // the last (clamped, unused) B loads and DMAs
-    }
+    const PgBSource<P, GATHER> bsrc(bin, idx, rows_per_batch, n_src, ldp, M, ntiles, t0, t1, lane);
+    pg_ring_gemm<P, 2, 3, MQC, HALVES, P == 2 && MB == 8, 0, GATHER>(ws, KT32, bsrc, rho_in * dyn_s, acc);
 
     if constexpr (EPI == PG_EPI_PLANES) {
         // next layer's operand: k-tile j of this m-block = C tiles 2j, 2j+1
@@ -932,94 +777,15 @@ __global__ __launch_bounds__(256, 2) void planes_chain4_kernel(const uint4 *__re
     const int wu = __builtin_amdgcn_readfirstlane(w);
     const int nch = MQ0 * KT0 + KT1 * MQ1 + KT2 * MQ2 + NP * KT3 * 2;
     const WStreamT<PG_CHUNK, PG_NB> ws{wstream, swt, nch, lane, wu, false};
-    auto dma = [&](int c) { ws.issue(c < nch ? c : 0, c % PG_NB); };
 #pragma unroll
-    for (int c = 0; c < PG_NB - 1; ++c) dma(c);
+    for (int c = 0; c < PG_NB - 1; ++c) pg_ring_issue(ws, c);
 
     const long long t0 = tile0 < ntiles ? tile0 : ntiles - 1, t1 = tile0 + 1 < ntiles ? tile0 + 1 : ntiles - 1;
-    // ---- layer 0: as planes_gemm_kernel (HALVES = MQ0).  GATHER: the B operand is not read as planes but gathered here --
-    // bin = fp32 source rows (n_src per batch, ldp = 32 * KT0 floats each, zero padded), row r reads source row
-    // (r / rows_per_batch) * n_src + max(idx[r], 0) (pointnet_sa_module.py:27,73-83) -- and split in registers at use.
+    // ---- layer 0: the k loop of planes_gemm_kernel (HALVES = MQ0), operand planes or gathered rows alike
     f32x4 acc0[2][4 * MQ0];
     pg_bias_init<4 * MQ0>(acc0, b0, N0, 0, g, dyn_s, H2);
-    {
-        constexpr int NBL = GATHER ? 4 : 2 * P;              // B loads per k-step
-        constexpr int NBV = GATHER ? 2 : P;
-        const float rho_g = sc.rho_in * dyn_s;
-        uint4 bs[3][2][NBV];
-        const uint4 *gsrc[2] = {nullptr, nullptr};
-        if constexpr (GATHER) {
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                long long r = (nt ? t1 : t0) * 16 + n;
-                if (r >= M) r = M - 1;
-                const long long j = idx[r];
-                gsrc[nt] = (const uint4 *)((const float *)bin + (size_t)((r / rows_per_batch) * n_src + (j < 0 ? 0 : j)) * ldp + 4 * g);
-            }
-        }
-        auto load_b = [&](uint4 (&dst)[2][NBV], int t) {
-            const int tc = t < KT0 ? t : KT0 - 1;
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int pl = 0; pl < NBV; ++pl)
-                    dst[nt][pl] = GATHER ? pg_load_async(gsrc[nt] + 8 * tc + 4 * pl)
-                                         : pg_load_async(bin + (((size_t)tc * ntiles + (nt ? t1 : t0)) * P + pl) * 64 + lane);
-        };
-        auto kstep = [&](int t, uint4 (&braw)[2][NBV], uint4 (&bload)[2][NBV], bool first) {
-            avec bc[2][P];
-#pragma unroll
-            for (int half = 0; half < MQ0; ++half) {
-                const int c = MQ0 * t + half;
-                if (half == 0) {
-                    if (first) pg_wait_set<0, NBV>(braw);
-                    else if (MQ0 == 2) pg_wait_set<2 * P + NBL, NBV>(braw);
-                    else pg_wait_set<P + NBL, NBV>(braw);
-                    pg_ring_barrier<false>();
-                    dma(c + PG_NB - 1);
-                    load_b(bload, t + 2);
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) {
-                        if constexpr (GATHER)
-                            AR::split(__builtin_bit_cast(f32x4, braw[nt][0]), __builtin_bit_cast(f32x4, braw[nt][1]), rho_g, bc[nt]);
-                        else
-#pragma unroll
-                            for (int pl = 0; pl < P; ++pl) bc[nt][pl] = __builtin_bit_cast(avec, braw[nt][pl < NBV ? pl : 0]);
-                    }
-                } else {
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * P + 2 * NBL) : "memory");
-                    pg_ring_barrier<false>();
-                    dma(c + PG_NB - 1);
-                }
-                const f32x4 *buf = ws.chunk(c);
-                avec a[4][P];
-#pragma unroll
-                for (int mq = 0; mq < 4; ++mq)
-#pragma unroll
-                    for (int pl = 0; pl < P; ++pl) a[mq][pl] = __builtin_bit_cast(avec, buf[(mq * P + pl) * 64]);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int q = 0; q < AR::NQ; ++q)
-#pragma unroll
-                    for (int mq = 0; mq < 4; ++mq)
-#pragma unroll
-                        for (int nt = 0; nt < 2; ++nt)
-                            acc0[nt][4 * half + mq] = AR::mfma(a[mq][AR::pa(q)], bc[nt][AR::pb(q)], acc0[nt][4 * half + mq]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        load_b(bs[0], 0);
-        load_b(bs[1], 1);
-        kstep(0, bs[0], bs[2], true);
-        if (KT0 > 1) kstep(1, bs[1], bs[0], false);
-#pragma unroll 1
-        for (int t = 2; t < KT0; t += 3) {
-            kstep(t, bs[2], bs[1], false);
-            if (t + 1 < KT0) kstep(t + 1, bs[0], bs[2], false);
-            if (t + 2 < KT0) kstep(t + 2, bs[1], bs[0], false);
-        }
-        pg_drain_loads<NBV>(bs);                                          // the last (clamped, unused) B loads land before their
-    }                                                                     // registers are reused; the ring's DMAs with them
+    const PgBSource<P, GATHER> bsrc(bin, idx, rows_per_batch, n_src, ldp, M, ntiles, t0, t1, lane);
+    pg_ring_gemm<P, 2, 3, 4, MQ0, false, 0, GATHER>(ws, KT0, bsrc, sc.rho_in * dyn_s, acc0);
     int c = MQ0 * KT0;
     // ---- layers 1, 2: registers to registers
     avec i1[2][KT1][P];

@@ -622,6 +622,31 @@ def test_f16x2_decoder_four_tile_form_equals_two_tile_form_bit_for_bit(kx, P, mo
     assert float((a - ref).abs().max()) <= 2e-6 * max(1.0, float(ref.abs().max()))
 
 
+@pytest.mark.parametrize("P", [1, 17, 129, 257])
+def test_bf16x3_decoder_four_tile_form_equals_two_tile_form_bit_for_bit(P, monkeypatch):
+    """dec_main_kernel_b3<4> (PCCX_DEC_NT=4: four patch tiles per wave, one wave per SIMD) against <2> (the default): both run the same
+    k loop over the same operands and every accumulator sees the same products in the same order, so the outputs are IDENTICAL, as
+    patches and as the reassembled cloud.  P = 1 and 17 leave all but one wave on clamped tiles, 129 starts a second workgroup of the
+    two-tile form inside the first of the four-tile form, 257 a second one of the four-tile form."""
+    kx = 32
+    ae = _seeded_ae(2 * kx, kx)
+    rng = np.random.default_rng(100 + P)
+    lq = torch.from_numpy(rng.integers(-3, 4, size=(P, d)).astype(np.float32)).cuda()
+    centres = torch.from_numpy(((rng.integers(0, 128, size=(1, P, 3)) + 0.5) / 128).astype(np.float32)).cuda()
+    center = torch.from_numpy(rng.normal(size=(1, 3)).astype(np.float32)).cuda()
+    longest = torch.from_numpy((1 + rng.random(1)).astype(np.float32)).cuda()
+    cloud = dict(centres=centres, center=center, longest=longest, S=P, scale=float((P * kx / 1024) ** (1 / 3)))
+    monkeypatch.delenv("PCCX_DEC_NT", raising=False)
+    a, pa = ae.decode(lq, matmul="bf16x3"), ae.decode(lq, matmul="bf16x3", **cloud)
+    monkeypatch.setenv("PCCX_DEC_NT", "4")
+    b, pb = ae.decode(lq, matmul="bf16x3"), ae.decode(lq, matmul="bf16x3", **cloud)
+    monkeypatch.delenv("PCCX_DEC_NT", raising=False)
+    c = ae.decode(lq, matmul="bf16x3")
+    assert a.shape == (P, kx, 3) and pa.shape == (1, P * kx, 3)
+    assert torch.isfinite(a).all() and torch.equal(a, b) and torch.equal(a, c)
+    assert torch.isfinite(pa).all() and torch.equal(pa, pb)
+
+
 @pytest.mark.parametrize("scale", [1e-6, 1e-3, 1.0, 0.99999994, 2.0, 37.0, 3000.0, 1e6])
 def test_f16x2_per_patch_normalisation_over_input_magnitudes(scale):
     """fp16 has five exponent bits; the f16x2 kernels bring every operand into range with exact power-of-two scales, one of them

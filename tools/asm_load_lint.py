@@ -28,7 +28,7 @@ CSRC = os.path.join(ROOT, "point-cloud-compression_amd", "csrc")
 TARGETS = {
     "encoder_fused_h2.hip": ["_Z23sa_pn_forward_h2_kernel"],
     "decoder_h2.hip": ["_Z18dec_main_h2_kernel"],
-    "decoder.hip": ["_Z15dec_main_kernelILb1E"],
+    "decoder.hip": ["_Z18dec_main_kernel_b3"],
     # the planes kernels load their B operand from inline assembly into three rotating register sets.  Covered: the two-chunks-per-k-step
     # forms (MB = 8) in both arithmetics, the f16x2 chains and the wide bf16x3 chain.  NOT covered: the one-chunk-per-k-step forms
     # (planes_gemm_kernel<P, 4, ..>, planes_chain4_kernel<3, 1, ..>): their three-k-step trips have early-outs whose backward branches

@@ -40,7 +40,7 @@ VARIANTS = {
     "ch16nb4": (["-DFH_CHUNK=16", "-DFH_NB=4"], []),
     "samg4": (["-DFH_SA_MG=4"], []),
     "nosplit": ([], [("encoder_fused_h2.hip", '#define FH_CHUNK', FAKE_DEF + '#define FH_CHUNK'), ("encoder_fused_h2.hip",) + FAKE_SPLIT,
-                     ("decoder_h2.hip", '#ifndef DEC_GROUP', FAKE_DEF + '#ifndef DEC_GROUP'), ("decoder_h2.hip",) + FAKE_SPLIT]),
+                     ("decoder_h2.hip", '#include "plane_ring.h"\n', '#include "plane_ring.h"\n' + FAKE_DEF), ("decoder_h2.hip",) + FAKE_SPLIT]),
 }
 _extra = os.path.join(os.path.dirname(os.path.abspath(__file__)), "h2_variants_extra.py")
 if os.path.exists(_extra):
