@@ -445,10 +445,18 @@ PCCX_API int pccx_linear_b3(const float *x, int M, int K, int ldx, const float *
  *   pccx_pack_planes_gemm : pccx_pack_linear_b3's planes reordered into per-m-block streams (pccx_planes_gemm_weight_floats).
  *   pccx_planes_gemm  : one Conv1x1 / Linear (+ folded BatchNorm) (+ ReLU, bit 0 of relu) on planes.  epilogue 0: out = planes of
  *       the N output channels; 1: out = fp32 rows (M, ldo); 2: out (M / group, ldo) = max over each `group` consecutive rows
- *       (torch.max over nsample, pointnet_sa_module.py:91; group in {32, 64, 128} dividing M). */
+ *       (torch.max over nsample, pointnet_sa_module.py:91; group in {16, 32, 64, 128} dividing M). */
 PCCX_API size_t pccx_planes_floats(int64_t M, int K);
 PCCX_API int pccx_group_planes(const float *f0, int C0, int ld0, const float *f1, int C1, int ld1, const int64_t *idx, int64_t M,
                                int64_t rows_per_batch, int64_t n_src, float *planes, void *stream);
+/* The kNN grouping of the pppe set abstraction, pppe_pcd_ae.py:599-606 (index_points of xyz and features, the centre subtracted, xyz first),
+ * written as the operand planes of the stack's first layer: row r = (b, s, j) holds offsets[r] = xyz[b, idx[r]] - centre[b, s] (M rows of 3
+ * floats: pccx_knn_list's nn field with patch_scale 1) and feats[b * n_src + idx[r]] (C channels, row stride ldf; C = 0: no features, idx
+ * unused).  The planes hold [C features | 3 offsets | zeros] -- the layout of pccx_group_planes -- so the first layer's weight columns are
+ * permuted to match when it is packed; the (M, 3 + C) fp32 tensor of :606 never exists.  amax8 (device, 8 floats, or NULL): the largest
+ * |offset| is folded into it as pccx_absmax does. */
+PCCX_API int pccx_group_planes_centred(const float *feats, int C, int ldf, const float *offsets, const int64_t *idx, int64_t M,
+                                       int64_t rows_per_batch, int64_t n_src, float *amax8, float *planes, void *stream);
 /* torch.cat([a, b.unsqueeze(1).repeat(1, P, 1)], -1) written directly as planes (FoldingNet's inputs, PPPF_AE.py:99-106): row r =
  * the C0 channels of f0 row (mod0 > 0 ? r % mod0 : r) then the C1 channels of f1 row r / div1. */
 PCCX_API int pccx_fold_planes(const float *f0, int C0, int ld0, int64_t mod0, const float *f1, int C1, int ld1, int64_t div1, int64_t M,
@@ -502,7 +510,8 @@ PCCX_API int pccx_planes_chain4_gather(const float *src, int ldp, const int64_t 
  * NULL for 1) is the stack's dynamic input normalisation -- Conv / ReLU stacks are positively homogeneous in (input, biases), so the
  * kernels multiply gathered inputs and biases by s and the stack's final rows by 1 / s; no input can overflow whatever the data.
  * amax8 (device, 8 floats, or NULL): the row epilogues fold the largest |value| they write into it (atomic max over 8 replicas) --
- * the next stack's input bound.  Same shapes, epilogues and restrictions as the bf16x3 entry points above. */
+ * the next stack's input bound (for a max epilogue: pccx_planes_gemm_h2_max_amax).  Same shapes, epilogues and restrictions as the
+ * bf16x3 entry points above. */
 PCCX_API size_t pccx_planes_floats_h2(int64_t M, int K);
 PCCX_API size_t pccx_packed_linear_h2_floats(int N, int K);
 /* wp_dev: the f32 fragments of pccx_pack_linear (uploaded) -> the two fp16 planes [t][MT][2] of tau * W */
@@ -511,6 +520,9 @@ PCCX_API size_t pccx_planes_gemm_weight_floats_h2(int N, int K);
 PCCX_API int pccx_pack_planes_gemm_h2(const float *wplanes_dev, int N, int K, float *wstream_dev, void *stream);
 PCCX_API int pccx_group_planes_h2(const float *f0, int C0, int ld0, const float *f1, int C1, int ld1, const int64_t *idx, int64_t M,
                                   int64_t rows_per_batch, int64_t n_src, float rho, const float *dyn, float *planes, void *stream);
+PCCX_API int pccx_group_planes_centred_h2(const float *feats, int C, int ldf, const float *offsets, const int64_t *idx, int64_t M,
+                                          int64_t rows_per_batch, int64_t n_src, float *amax8, float rho, const float *dyn, float *planes,
+                                          void *stream);
 PCCX_API int pccx_fold_planes_h2(const float *f0, int C0, int ld0, int64_t mod0, const float *f1, int C1, int ld1, int64_t div1, int64_t M,
                                  float rho, const float *dyn, float *planes, void *stream);
 PCCX_API int pccx_rows_affine_planes_h2(const float *base, int C, int64_t div, const float *x, int ldx, int Ks, int64_t mod, const float *w,
@@ -525,6 +537,11 @@ PCCX_API int pccx_planes_gemm_h2(const float *planes_in, int64_t M, int K, const
 PCCX_API int pccx_planes_gemm_h2_member_max(const float *planes_in, int64_t M, int K, const float *wstream, const float *bias, int N, int relu,
                                             int group, const unsigned char *member, float scale_out, const float *dyn, float *out, int ldo,
                                             void *stream);
+/* The last layer of a pppe set-abstraction stack (the max over the K neighbours, pppe_pcd_ae.py:607-610): pccx_planes_gemm_h2's max epilogue
+ * (group in {16, 32, 64, 128}, M % group == 0 -> out (M / group, ldo)) that also folds the largest |maximum| it writes into amax8 (required):
+ * the bound of the next level's input features. */
+PCCX_API int pccx_planes_gemm_h2_max_amax(const float *planes_in, int64_t M, int K, const float *wstream, const float *bias, int N, int relu,
+                                          int group, float scale_out, const float *dyn, float *amax8, float *out, int ldo, void *stream);
 /* member (n_idx / per_batch, n_src) bytes: 1 where the row is named by an entry of idx (per_batch entries per batch element; -1 -> row 0, the
  * clamp of pointnet_sa_module.py:27), else 0.  The table's size and address must be multiples of 4 (cleared in words by a kernel). */
 PCCX_API int pccx_group_members(const int64_t *idx, int64_t n_idx, int64_t per_batch, int64_t n_src, unsigned char *member, void *stream);

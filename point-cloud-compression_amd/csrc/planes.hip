@@ -114,13 +114,14 @@ extern "C" size_t pccx_planes_floats_h2(int64_t M, int K) { return pg_planes_flo
 
 // ---- gather + concat + split ------------------------------------------------------------------------------------
 // One wave per row tile.  Row r takes source row s = idx ? (r / rows_per_batch) * n_src + max(idx[r], 0) : r; its channels are
-// f0[s][0..C0) followed by f1[s][0..C1).
-template <int P>
+// f0[s][0..C0) followed by f1[s][0..C1).  OWN1 (the centred grouping of pppe_pcd_ae.py:599-606): f1 holds one row per OUTPUT row -- the
+// neighbour's offset from its centre, f1[r][0..C1) -- and the largest |f1 value| is folded into amax (as absmax_kernel does).
+template <int P, bool OWN1>
 __global__ __launch_bounds__(256) void group_planes_kernel(const float *__restrict__ f0, int C0, int ld0, const float *__restrict__ f1,
                                                            int C1, int ld1, const int64_t *__restrict__ idx, long long M,
                                                            long long rows_per_batch, long long n_src, int KT32, long long ntiles,
                                                            uint4 *__restrict__ planes, long long mod0, long long div1, float rho,
-                                                           const float *__restrict__ dyn)
+                                                           const float *__restrict__ dyn, float *__restrict__ amax)
 {
     typedef PgArith<P> AR;
     rho *= pg_dyn(dyn, 0);
@@ -136,7 +137,14 @@ __global__ __launch_bounds__(256) void group_planes_kernel(const float *__restri
     }
     // without indices the two sources may be rows of different tables: f0 row r % mod0 (mod0 > 0), f1 row r / div1
     const float *p0 = f0 ? f0 + (size_t)(mod0 > 0 ? s % mod0 : s) * ld0 : nullptr;
-    const float *p1 = f1 ? f1 + (size_t)(s / div1) * ld1 : nullptr;
+    const float *p1 = f1 ? f1 + (size_t)(OWN1 ? r : s / div1) * ld1 : nullptr;
+    if constexpr (OWN1) {
+        if (amax) {                                          // wave-uniform; padded rows repeat a real one, so they cannot raise the maximum
+            float m = 0.f;
+            for (int q = 0; q < C1; ++q) m = fmaxf(m, fabsf(p1[q]));
+            pg_amax_commit(amax, m);
+        }
+    }
     const bool vec0 = p0 && (ld0 % 4 == 0) && ((uintptr_t)f0 % 16 == 0);
     const int C = C0 + C1;
     for (int t = 0; t < KT32; ++t) {
@@ -173,9 +181,9 @@ static int group_planes_launch(const float *f0, int C0, int ld0, const float *f1
     PCCX_CHECK_ARG(!idx || (rows_per_batch >= 1 && n_src >= 1), "%s: indices need rows_per_batch and n_src", who);
     const long long ntiles = (M + 15) / 16;
     PCCX_CHECK_ARG((ntiles + 3) / 4 <= 0x7fffffffLL, "%s: M too large", who);
-    hipLaunchKernelGGL(group_planes_kernel<P>, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, C0 ? f0 : nullptr, C0,
-                       ld0, C1 ? f1 : nullptr, C1, ld1, idx, (long long)M, (long long)(idx ? rows_per_batch : 1),
-                       (long long)(idx ? n_src : 1), pg_kt32(C0 + C1), ntiles, (uint4 *)planes, 0LL, 1LL, rho, dyn);
+    hipLaunchKernelGGL((group_planes_kernel<P, false>), dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, C0 ? f0 : nullptr,
+                       C0, ld0, C1 ? f1 : nullptr, C1, ld1, idx, (long long)M, (long long)(idx ? rows_per_batch : 1),
+                       (long long)(idx ? n_src : 1), pg_kt32(C0 + C1), ntiles, (uint4 *)planes, 0LL, 1LL, rho, dyn, (float *)nullptr);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }
@@ -192,6 +200,43 @@ extern "C" int pccx_group_planes_h2(const float *f0, int C0, int ld0, const floa
     return group_planes_launch<2>(f0, C0, ld0, f1, C1, ld1, idx, M, rows_per_batch, n_src, planes, rho, dyn, stream, "pccx_group_planes_h2");
 }
 
+// The kNN grouping of the pppe set abstraction (pppe_pcd_ae.py:599-606): row r = (b, s, j) of the stack's input is
+// [xyz[b, idx[r]] - centre[b, s] | feats[b, idx[r]]].  offsets (M, 3) holds the centred neighbours (pccx_knn_list with patch_scale 1: the
+// one fp32 subtraction the rows path sees), feats (n_src rows per batch element, C channels, row stride ldf) is gathered through idx.
+// The planes are written FEATURES FIRST -- [C features | 3 offsets | zeros], the layout of group_planes_kernel with its 16-byte feature
+// loads -- so the caller permutes the first layer's weight columns once at pack time.  C = 0 (the MSG level): offsets only, idx unused.
+template <int P>
+static int group_planes_centred_launch(const float *feats, int C, int ldf, const float *offsets, const int64_t *idx, int64_t M,
+                                       int64_t rows_per_batch, int64_t n_src, float *amax8, float *planes, float rho, const float *dyn,
+                                       void *stream, const char *who)
+{
+    if (M == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
+    PCCX_CHECK_ARG(planes && offsets && M > 0, "%s: null pointer or negative M", who);
+    PCCX_CHECK_ARG(C >= 0 && (C == 0 || (feats && idx && ldf >= C && rows_per_batch >= 1 && n_src >= 1)),
+                   "%s: C=%d features need their table, the indices, rows_per_batch and n_src", who, C);
+    const long long ntiles = (M + 15) / 16;
+    PCCX_CHECK_ARG((ntiles + 3) / 4 <= 0x7fffffffLL, "%s: M too large", who);
+    hipLaunchKernelGGL((group_planes_kernel<P, true>), dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, C ? feats : nullptr, C,
+                       ldf, offsets, 3, 3, C ? idx : nullptr, (long long)M, (long long)(C ? rows_per_batch : 1), (long long)(C ? n_src : 1),
+                       pg_kt32(C + 3), ntiles, (uint4 *)planes, 0LL, 1LL, rho, dyn, amax8);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+extern "C" int pccx_group_planes_centred(const float *feats, int C, int ldf, const float *offsets, const int64_t *idx, int64_t M,
+                                         int64_t rows_per_batch, int64_t n_src, float *amax8, float *planes, void *stream)
+{
+    return group_planes_centred_launch<3>(feats, C, ldf, offsets, idx, M, rows_per_batch, n_src, amax8, planes, 1.f, nullptr, stream,
+                                          "pccx_group_planes_centred");
+}
+extern "C" int pccx_group_planes_centred_h2(const float *feats, int C, int ldf, const float *offsets, const int64_t *idx, int64_t M,
+                                            int64_t rows_per_batch, int64_t n_src, float *amax8, float rho, const float *dyn, float *planes,
+                                            void *stream)
+{
+    PCCX_CHECK_ARG(rho > 0.f, "pccx_group_planes_centred_h2: rho must be a positive power of two");
+    return group_planes_centred_launch<2>(feats, C, ldf, offsets, idx, M, rows_per_batch, n_src, amax8, planes, rho, dyn, stream,
+                                          "pccx_group_planes_centred_h2");
+}
+
 // torch.cat([a, b.unsqueeze(1).repeat(1, P, 1)], -1) as planes (the inputs of FoldingNet's two stacks, PPPF_AE.py:99-106): row r has
 // the C0 channels of f0 row (mod0 > 0 ? r % mod0 : r) followed by the C1 channels of f1 row r / div1.  Nothing is concatenated or
 // repeated in memory.
@@ -204,9 +249,9 @@ static int fold_planes_launch(const float *f0, int C0, int ld0, int64_t mod0, co
     PCCX_CHECK_ARG(C0 >= 1 && C1 >= 1 && ld0 >= C0 && ld1 >= C1 && mod0 >= 0 && div1 >= 1, "%s: bad arguments", who);
     const long long ntiles = (M + 15) / 16;
     PCCX_CHECK_ARG((ntiles + 3) / 4 <= 0x7fffffffLL, "%s: M too large", who);
-    hipLaunchKernelGGL(group_planes_kernel<P>, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, f0, C0, ld0, f1, C1, ld1,
-                       (const int64_t *)nullptr, (long long)M, 1LL, 1LL, pg_kt32(C0 + C1), ntiles, (uint4 *)planes, (long long)mod0,
-                       (long long)div1, rho, dyn);
+    hipLaunchKernelGGL((group_planes_kernel<P, false>), dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, f0, C0, ld0, f1, C1,
+                       ld1, (const int64_t *)nullptr, (long long)M, 1LL, 1LL, pg_kt32(C0 + C1), ntiles, (uint4 *)planes, (long long)mod0,
+                       (long long)div1, rho, dyn, (float *)nullptr);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }
@@ -513,10 +558,12 @@ __global__ __launch_bounds__(256, 2) void planes_gemm_kernel(const uint4 *__rest
             if (amax) pg_amax_commit(amax, vmax);                     // whole waves reach this (no divergent exit above)
         }
     } else {
-        // max over groups of `group` rows (32, 64 or 128; M is a multiple of it, so no group holds padded rows).  In the wave:
-        // the two tiles elementwise, then the 16 rows of the tile by DPP; across the waves of a group through LDS.
+        // max over groups of `group` rows (16, 32, 64 or 128; M is a multiple of it, so no group holds padded rows).  In the wave:
+        // the two tiles elementwise, then the 16 rows of the tile by DPP; across the waves of a group through LDS.  group = 16 (the
+        // narrow MSG branch of pppe_pcd_ae.py:655): every tile is a group of its own, the wave's two tiles stay apart.
         __syncthreads();                                   // every wave is done with the ring
-        float *smax = (float *)swt;                        // [4 waves][16 * MB channels]
+        float *smax = (float *)swt;                        // [4 waves][16 * MB channels]; group 16: [8 tiles][16 * MB channels]
+        const int wpg = group >> 5;                        // waves per group (0: a tile per group)
         if (member) {                                      // the maximum over the MEMBER rows of each group only (pccx_group_members)
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) {
@@ -526,32 +573,52 @@ __global__ __launch_bounds__(256, 2) void planes_gemm_kernel(const uint4 *__rest
                 for (int mt = 0; mt < MB; ++mt) acc[nt][mt] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
             }
         }
+        if (wpg == 0) {
 #pragma unroll
-        for (int mt = 0; mt < MB; ++mt)
+            for (int mt = 0; mt < MB; ++mt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float v = fmaxf(acc[0][mt][r], acc[1][mt][r]);
-                v = row16_max(v);
-                if (n == 0) smax[w * (16 * MB) + 16 * mt + 4 * g + r] = v;
-            }
+                for (int r = 0; r < 4; ++r) {
+                    const float v0 = row16_max(acc[0][mt][r]), v1 = row16_max(acc[1][mt][r]);
+                    if (n == 0) {
+                        smax[(2 * w) * (16 * MB) + 16 * mt + 4 * g + r] = v0;
+                        smax[(2 * w + 1) * (16 * MB) + 16 * mt + 4 * g + r] = v1;
+                    }
+                }
+        } else {
+#pragma unroll
+            for (int mt = 0; mt < MB; ++mt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float v = fmaxf(acc[0][mt][r], acc[1][mt][r]);
+                    v = row16_max(v);
+                    if (n == 0) smax[w * (16 * MB) + 16 * mt + 4 * g + r] = v;
+                }
+        }
         __syncthreads();
-        const int gpb = 128 / group, wpg = group / 32;     // groups per block, waves per group
+        const int gpb = 128 / group;                       // groups per block
         const long long G = M / group;
+        float vmax = 0.f;                                  // f16x2: the largest |value| written (the next stack's input bound)
         for (int e = tid; e < gpb * 16 * MB; e += 256) {
             const int gi = e / (16 * MB), c = e % (16 * MB);
-            float v = smax[(gi * wpg) * (16 * MB) + c];
+            float v = smax[(wpg ? gi * wpg : gi) * (16 * MB) + c];
             for (int q = 1; q < wpg; ++q) v = fmaxf(v, smax[(gi * wpg + q) * (16 * MB) + c]);
             if (relu) v = fmaxf(v, 0.f);                   // max(relu(x)) = relu(max(x))
             if constexpr (P == 2) v *= scale_out * pg_dyn(dyn, 1);       // a positive power of two commutes with max and relu
             const long long grp = blk * gpb + gi;
             const int ch = mb * 16 * MB + c;
-            if (grp < G && ch < N) out[(size_t)grp * ldo + ch] = v;
+            if (grp < G && ch < N) {
+                out[(size_t)grp * ldo + ch] = v;
+                vmax = fmaxf(vmax, fabsf(v));
+            }
+        }
+        if constexpr (P == 2) {
+            if (amax) pg_amax_commit(amax, vmax);          // every wave reaches this
         }
     }
 }
 
 // out: epilogue 0 -> planes of the N output channels (pccx_planes_floats(M, N) floats); 1 -> fp32 rows (M, ldo);
-// 2 -> fp32 (M / group, ldo), the max over each `group` consecutive rows (group in {32, 64, 128}, M % group == 0).
+// 2 -> fp32 (M / group, ldo), the max over each `group` consecutive rows (group in {16, 32, 64, 128}, M % group == 0).
 template <int P>
 static int planes_gemm_launch(const float *x, const int64_t *idx, int64_t rows_per_batch, int64_t n_src, int ldp, int64_t M, int K,
                               const float *wstream, const float *bias, int N, int relu, int epilogue, int group, float *out, int ldo,
@@ -563,8 +630,8 @@ static int planes_gemm_launch(const float *x, const int64_t *idx, int64_t rows_p
     PCCX_CHECK_ARG(M > 0 && K >= 1 && N >= 1, "%s: bad shape M=%lld K=%d N=%d", who, (long long)M, K, N);
     PCCX_CHECK_ARG(epilogue >= 0 && epilogue <= 2, "%s: epilogue %d", who, epilogue);
     PCCX_CHECK_ARG(epilogue == PG_EPI_PLANES || ldo >= N, "%s: ldo=%d < N=%d", who, ldo, N);
-    PCCX_CHECK_ARG(epilogue != PG_EPI_MAX || ((group == 32 || group == 64 || group == 128) && M % group == 0),
-                   "%s: group max needs group in {32,64,128} dividing M (group=%d M=%lld)", who, group, (long long)M);
+    PCCX_CHECK_ARG(epilogue != PG_EPI_MAX || ((group == 16 || group == 32 || group == 64 || group == 128) && M % group == 0),
+                   "%s: group max needs group in {16,32,64,128} dividing M (group=%d M=%lld)", who, group, (long long)M);
     const long long ntiles = (M + 15) / 16, nblk = (ntiles + 7) / 8;
     const int MT = (N + 15) / 16, MB = pg_mb(N), MBS = (MT + MB - 1) / MB, KT32 = pg_kt32(K);
     const long long blocks = (nblk + 7) / 8 * 8 * MBS;
@@ -608,6 +675,18 @@ extern "C" int pccx_planes_gemm_h2(const float *planes_in, int64_t M, int K, con
     PCCX_CHECK_ARG(!amax8 || epilogue == PG_EPI_ROWS, "pccx_planes_gemm_h2: the |value| maximum is collected by the row epilogue only");
     return planes_gemm_launch<2>(planes_in, nullptr, 1, 1, 0, M, K, wstream, bias, N, relu, epilogue, group, out, ldo, stream,
                                  "pccx_planes_gemm_h2", 1.f, scale_out, dyn, amax8);
+}
+
+// The last layer of a set-abstraction stack whose maxima are the next stack's input (the pppe encoder's levels, pppe_pcd_ae.py:607-610):
+// the max epilogue of pccx_planes_gemm_h2 (group in {16, 32, 64, 128}), which also folds the largest |maximum| it writes into amax8 -- the
+// bound the next level's dynamic normalisation is taken from, without another pass over the level's output.
+extern "C" int pccx_planes_gemm_h2_max_amax(const float *planes_in, int64_t M, int K, const float *wstream, const float *bias, int N, int relu,
+                                            int group, float scale_out, const float *dyn, float *amax8, float *out, int ldo, void *stream)
+{
+    PCCX_CHECK_ARG(scale_out > 0.f, "pccx_planes_gemm_h2_max_amax: scale_out must be a positive power of two");
+    PCCX_CHECK_ARG(amax8 || M == 0, "pccx_planes_gemm_h2_max_amax: null amax8");
+    return planes_gemm_launch<2>(planes_in, nullptr, 1, 1, 0, M, K, wstream, bias, N, relu, PG_EPI_MAX, group, out, ldo, stream,
+                                 "pccx_planes_gemm_h2_max_amax", 1.f, scale_out, dyn, amax8);
 }
 
 // The last layer of a set-abstraction stack whose groups are only ever reduced TOGETHER (PPPF_AE's third level: PPPF_AE.py:44 takes the

@@ -16,7 +16,8 @@ PPPF_AE is a tuned path: its Conv/Linear stacks run on operand plan
 one of three arithmetics -- f16x2 or bf16x3 planes, or exact-fp32 rows -- each stack on its SOURCE rows
 only, in one chain kernel where one fits.  The file states that machinery once: _PLANES (the entry points
 of the two planes arithmetics), Stack (the packed layers and every operand derived from them) and
-run_planes (the one stack runner).  The pppe PointCloudAE forward is layer by layer on fp32 rows
+run_planes (the one stack runner).  The pppe PointCloudAE forward runs its stacks through the same runner in f16x2 (the centred kNN
+grouping written straight as operand planes, PointCloudAE._forward_h2); in the f32 and bf16x3 modes it is layer by layer on fp32 rows
 (pccx_linear / pccx_linear_b3).
 """
 import math
@@ -42,11 +43,11 @@ def _ptr(t):
 # The two planes arithmetics (the host mirror of PgArith<P> in csrc/planes.hip): the size function and the entry points by role.  An
 # f16x2 entry point takes its bf16x3 sibling's arguments plus scale arguments in front of `out`: _pcall() puts them there.
 _PLANES = {
-    "bf16x3": dict(floats="pccx_planes_floats", operand="pccx_group_planes", gemm="pccx_planes_gemm", gemm_gather="pccx_planes_gemm_gather",
+    "bf16x3": dict(floats="pccx_planes_floats", operand="pccx_group_planes", operand_centred="pccx_group_planes_centred", gemm="pccx_planes_gemm", gemm_gather="pccx_planes_gemm_gather",
                    chain4="pccx_planes_chain4", chain4_gather="pccx_planes_chain4_gather", rows_affine="pccx_rows_affine_planes"),
-    "f16x2": dict(floats="pccx_planes_floats_h2", operand="pccx_group_planes_h2", gemm="pccx_planes_gemm_h2", gemm_gather="pccx_planes_gemm_gather_h2",
+    "f16x2": dict(floats="pccx_planes_floats_h2", operand="pccx_group_planes_h2", operand_centred="pccx_group_planes_centred_h2", gemm="pccx_planes_gemm_h2", gemm_gather="pccx_planes_gemm_gather_h2",
                   chain4="pccx_planes_chain4_h2", chain4_gather="pccx_planes_chain4_gather_h2", rows_affine="pccx_rows_affine_planes_h2",
-                  member_max="pccx_planes_gemm_h2_member_max"),
+                  member_max="pccx_planes_gemm_h2_member_max", max_amax="pccx_planes_gemm_h2_max_amax"),
 }
 
 
@@ -139,7 +140,7 @@ class FoldedLinear:
 
     def mode(self):
         m = _arith(self.matmul)
-        return "bf16x3" if m == "f16x2" else m              # a layer called by itself on fp32 rows has no f16x2 form: bf16x3
+        return "bf16x3" if m == "f16x2" else m              # pccx_linear has no f16x2 form (f16x2 is an arithmetic of planes stacks): bf16x3
 
     def planes_mode(self):
         """the arithmetic of the layer as part of a planes stack: "f16x2" when asked for (the stacks of PPPF_AE.forward), else mode()"""
@@ -157,13 +158,14 @@ class FoldedLinear:
             _lib.call("pccx_pack_planes_gemm", self._planes3().data_ptr(), self.N, self.K, self.ws3.data_ptr(), _stream())
         return self.ws3
 
-    def planes(self, x, M, epilogue=0, group=0, idx=None, member=None, ar="bf16x3", sig_next=None, dyn=None, amax=None):
+    def planes(self, x, M, epilogue=0, group=0, idx=None, member=None, ar="bf16x3", sig_next=None, dyn=None, amax=None, max_amax=False):
         """The layer on an activation kept in planes (csrc/planes.hip): x = the planes of the (M, K) input in the arithmetic `ar`, or,
         with idx (B, Mq, ns) int64 (-1 -> row 0), the source rows (B, N, ldp) of padded_rows() that the kernel gathers itself.
         epilogue 0 -> planes of the (M, N) output, 1 -> fp32 rows (M, N), 2 -> (M // group, N) max over `group` consecutive rows; member
         (M bytes, epilogue 2, f16x2): the maxima run over the rows marked 1 only.
         f16x2 (h2_prepare_stack first): x holds sigma * input; epilogue 0 writes sig_next * output, 1 / 2 write un-scaled values (times
-        dyn[1]); amax: 8 floats the row epilogue folds the largest |value| into."""
+        dyn[1]); amax: 8 floats the row epilogue folds the largest |value| into -- and the max epilogue (epilogue 2 on planes) with
+        max_amax, which goes through pccx_planes_gemm_h2_max_amax."""
         if ar == "f16x2":
             h = self.h2
             ws, b, sig_in = h["ws"], h["b"], [float(h["sig"])]
@@ -174,6 +176,10 @@ class FoldedLinear:
         layer, to = [ws.data_ptr(), b.data_ptr(), self.N, self.relu], [out.data_ptr(), self.N]
         if member is not None:
             _pcall(ar, "member_max", [x.data_ptr(), M, self.K] + layer + [group, member.data_ptr()], scales[:2], to)
+        elif max_amax:
+            if ar != "f16x2" or epilogue != 2 or idx is not None or amax is None:
+                raise _lib.PccxError("FoldedLinear.planes: max_amax is the f16x2 max epilogue on planes, with amax")
+            _pcall(ar, "max_amax", [x.data_ptr(), M, self.K] + layer + [group], scales, to)
         elif idx is not None:
             _pcall(ar, "gemm_gather", [x.data_ptr(), x.shape[2], idx.data_ptr(), idx.shape[1] * idx.shape[2], x.shape[1], M, self.K] + layer +
                    [epilogue, group], sig_in + scales, to)
@@ -287,6 +293,32 @@ def group_planes(feats, xyz=None, idx=None, ar="bf16x3", sig=None, dyn=None):
     return out, rows
 
 
+def group_planes_centred(offsets, feats=None, idx=None, ar="bf16x3", sig=None, dyn=None, amax=None):
+    """The kNN grouping of pppe_pcd_ae.py:599-606 as the operand planes of a stack's first layer, in the arithmetic `ar` (f16x2: times
+    sig * dyn[0]): offsets (B, S, K, 3) = the centred neighbours (knn_points(..., patch_scale=1.0).knn), feats (B, N, C) channels-last
+    gathered through idx (B, S, K) int64, or None.  The planes hold [C features | 3 offsets] -- features FIRST, the layout of
+    group_planes -- so the layer that reads them has the reference's weight columns rotated by three (centred_first_layer()).  amax:
+    8 floats that receive the largest |offset|.  Returns (planes, rows)."""
+    B, S, K = int(offsets.shape[0]), int(offsets.shape[1]), int(offsets.shape[2])
+    rows = B * S * K
+    offsets = offsets.contiguous()
+    f, C, ld = _rows2d(feats)
+    if f is not None:
+        idx = idx.contiguous()
+    out = _planes_out(ar, rows, C + 3, 0, 0, offsets.device)
+    _pcall(ar, "operand_centred", [_ptr(f), C, ld, offsets.data_ptr(), _ptr(idx) if f is not None else None, rows, S * K,
+                                   int(feats.shape[1]) if f is not None else 1, _ptr(amax)],
+           [float(sig) if sig is not None else None, _ptr(dyn)], [out.data_ptr()])
+    return out, rows
+
+
+def centred_first_layer(conv, bn, device):
+    """The first Conv-BN-ReLU of a pppe set-abstraction stack (input [3 offsets | C features], pppe_pcd_ae.py:606) packed for the
+    features-first planes of group_planes_centred: the same weights, columns rotated to [C features | 3 offsets]."""
+    w = conv.weight.detach().reshape(conv.weight.shape[0], -1)
+    return FoldedLinear(torch.cat([w[:, 3:], w[:, :3]], dim=1), None, True, bn, device)
+
+
 def chain4_fits(stack):
     """The width patterns pccx_planes_chain4 is built for (sa1 / sa2 of PPPF_AE.py:29-34), every layer with ReLU."""
     if len(stack) != 4 or not all(l.relu for l in stack) or any(stack[i + 1].K != stack[i].N for i in range(3)):
@@ -337,8 +369,9 @@ def run_planes(stack, x, M, want="rows", group=0, idx=None, member=None, ar="bf1
     x: the operand planes of the (M, K) input in the arithmetic `ar`; or a PaddedRows, which the first kernel gathers row by row (an
     identity index); or, with idx (B, Mq, ns) int64 (-1 -> row 0), the source rows (B, N, ldp) of padded_rows() -- the grouped tensor of
     pointnet_sa_module.py:73-83 never exists.
-    want: "rows" -> fp32 rows (M, N_last); "max" -> (M // group, N_last), the maximum over `group` consecutive rows (:91); "member" ->
-    the same maximum over the rows marked 1 in `member` (M bytes; f16x2); "planes" -> the output as planes (bf16x3).
+    want: "rows" -> fp32 rows (M, N_last); "max" -> (M // group, N_last), the maximum over `group` consecutive rows (:91; layer by layer
+    also group 16, and in f16x2 on planes with amax the last layer is pccx_planes_gemm_h2_max_amax, which folds amax like the rows);
+    "member" -> the same maximum over the rows marked 1 in `member` (M bytes; f16x2); "planes" -> the output as planes (bf16x3).
     ONE kernel where the stack fits pccx_planes_chain4 (rows / max); three wide layers in one kernel and the last by itself for a gathered
     bf16x3 input that fits pccx_planes_chain_wide; else layer by layer, the first layer gathering and the last one reducing.
     f16x2: dyn = the stack's dynamic input normalisation {s, 1 / s} on the device, amax = 8 floats that receive the largest |value| of
@@ -365,7 +398,8 @@ def run_planes(stack, x, M, want="rows", group=0, idx=None, member=None, ar="bf1
         x, idx, first = wide3_planes(stack, x, idx, M), None, 3
     for i, layer in enumerate(stack[first:-1], start=first):
         x, idx = layer.planes(x, M, 0, idx=idx, ar=ar, sig_next=stack[i + 1].h2["sig"] if h2 else None, dyn=dyn), None
-    return stack[-1].planes(x, M, _EPILOGUE[want], group, idx=idx, member=member, ar=ar, dyn=dyn, amax=amax)
+    return stack[-1].planes(x, M, _EPILOGUE[want], group, idx=idx, member=member, ar=ar, dyn=dyn, amax=amax,
+                            max_amax=h2 and want == "max" and idx is None and amax is not None)
 
 
 def stack_max_gather(stack, feats, xyz, idx):
@@ -601,14 +635,15 @@ class FoldingNet(nn.Module):                            # PPPF_AE.py:50-80
 
 
 class H2Scales:
-    """The f16x2 scale bookkeeping of one packed PPPF_AE, rewritten by every forward on the device: amax = 6 slots of 8 floats that
-    receive a largest |value| (0 coordinates, 1 / 2 outputs of levels 1 / 2, 3 / 5 per-patch parts of mlp1 / mlp2, 4 coarse points),
-    dyn = 5 slots {s, 1 / s}, one per planes stack (levels 0..2, mlp1, mlp2): the power of two s <= 1 that normalises its input.
-    wsum = the largest absolute row sums of the two folding MLPs' per-point weights."""
+    """The f16x2 scale bookkeeping of one packed model, rewritten by every forward on the device: amax = n_amax slots of 8 floats that
+    receive a largest |value|, dyn = n_dyn slots {s, 1 / s}, one per planes stack: the power of two s <= 1 that normalises its input.
+    PPPF_AE (the defaults): amax 0 coordinates, 1 / 2 outputs of levels 1 / 2, 3 / 5 per-patch parts of mlp1 / mlp2, 4 coarse points;
+    dyn levels 0..2, mlp1, mlp2; wsum = the largest absolute row sums of the two folding MLPs' per-point weights.  PointCloudAE:
+    PointCloudAE._SLOTS."""
 
-    def __init__(self, device, wsum):
-        self.amax = torch.zeros(6 * 8, device=device, dtype=torch.float32)
-        self.dyn = torch.ones(5 * 2, device=device, dtype=torch.float32)
+    def __init__(self, device, wsum, n_amax=6, n_dyn=5):
+        self.amax = torch.zeros(n_amax * 8, device=device, dtype=torch.float32)
+        self.dyn = torch.ones(n_dyn * 2, device=device, dtype=torch.float32)
         self.wsum = wsum
 
     def __getitem__(self, name):                           # ._packed["h2"]["dyn"], as tests and bench.py read it
@@ -813,11 +848,25 @@ class PointNetSetAbstraction(nn.Module):                # pppe_pcd_ae.py:573-611
             last = out
         self.mlp_stack = nn.ModuleList(layers)
 
-    def run(self, stack, xyz, feats, start):
+    def run(self, stack, xyz, feats, start, h2=None):
+        """h2 = (H2Scales, amax slot of the offsets, amax slot of feats or None, dyn slot, amax slot of the output): the planes form in
+        f16x2 -- `stack` is then the stack whose first layer is centred_first_layer() and h2_prepare_stack has run on it.  The grouped
+        (B * S * K, 3 + C) rows never exist: the centred operand goes straight to planes, every layer runs on planes and the last one
+        reduces over the K neighbours and folds the level's largest output for the next level."""
         B, N, _ = xyz.shape
         S = self.npoint
         new_xyz = xyz if S == N else ops.index_points(xyz, ops.farthest_point_sample_batch(xyz, S, start))   # :593-597
         nn_ = ops.knn_points(new_xyz, xyz, self.K, patch_scale=1.0)                  # :599-600 (nn - centre) * 1
+        if h2 is not None:
+            sc, a_off, a_feat, d, a_out = h2
+            # s from the larger of the two input bounds; it has to exist before the first plane is written, so the offsets' maximum is
+            # taken from the (B, S, K, 3) rows here and not from the operand kernel's own fold
+            sc.absmax(nn_.knn, a_off)
+            sc.scale(d, a_off, a_feat, a2=1.0 if a_feat is not None else 0.0)
+            with stage("sa_stack_%d" % stack[-1].N):
+                pl, rows = group_planes_centred(nn_.knn, feats, nn_.idx, "f16x2", stack[0].h2["sig"], sc.dy(d))   # :599-606
+                y = run_planes(stack, pl, rows, "max", self.K, ar="f16x2", dyn=sc.dy(d), amax=sc.am(a_out))       # :607-610
+            return new_xyz, y.view(B, S, -1)
         x = cat_rows([nn_.knn, ops.index_points(feats, nn_.idx)] if feats is not None else [nn_.knn])   # :606 xyz first
         return new_xyz, group_max(stack.rows(x).view(B * S, self.K, -1)).view(B, S, -1)   # :610
 
@@ -862,6 +911,20 @@ class _PppeProbParams(nn.Module):                       # pppe_pcd_ae.py:751-772
 class PointCloudAE(_Packable):
     """pppe_pcd_ae.PointCloudAE.forward (pppe_pcd_ae.py:843-877), eval mode."""
 
+    # f16x2: every Conv / Linear stack of the forward on operand planes through run_planes (_forward_h2).  False = the rows path, which
+    # is also what the f32 and bf16x3 modes run (f16x2 then means bf16x3 rows: FoldedLinear.mode).  True = the planes path for every
+    # batch.  "auto" (the default) = whichever was measured faster for the batch (DESIGN 4.5): the planes path from h2_min_points input
+    # points (B * N) on -- below that the forward is bound by its launches and the rows path is a few percent ahead.
+    h2_stacks = "auto"
+    h2_min_points = 16 * 8192
+    # with h2_stacks: the three dense stacks after the encoder (gconv, coarse, expand; M = B rows) in f16x2 too; False leaves them on rows
+    h2_tails = True
+    # amax / dyn slots of the f16x2 forward (H2Scales).  Per set-abstraction stack: amax slot of its kNN offsets, amax slot of its input
+    # features, its dyn slot, amax slot of its output.  The two MSG branches normalise separately and fold their outputs into ONE slot,
+    # which so holds the larger of the two: the bound of the concatenated features level 1 reads.
+    _SLOTS = {"msg0": (0, None, 0, 2), "msg1": (1, None, 1, 2), "sa1": (3, 2, 2, 4), "sa2": (5, 4, 3, 6)}
+    _A_COARSE, _D_GCONV, _D_EXPAND, _N_AMAX, _N_DYN = 7, 4, 5, 8, 6
+
     def __init__(self, latent_dim=64, latent_bins=16, npoints=8192):
         super().__init__()
         self.encoder = PointNet2EncoderFull(latent_dim=latent_dim)
@@ -880,6 +943,66 @@ class PointCloudAE(_Packable):
             coarse=_fold_stack(self.decoder.fc_coarse, device), expand=_fold_stack(self.decoder.expansion_mlp, device))
         return self
 
+    def _ensure_h2(self, device):
+        """The f16x2 operands of the planes stacks, once per pack.  Every stack is bounded for a NORMALISED input, which _forward_h2
+        establishes per call from the data (a power of two s <= 1 per stack: biases times s, outputs times 1 / s):
+          * the four set-abstraction stacks, their first layers repacked for the features-first planes of group_planes_centred:
+            features (post-ReLU maxima) in [0, 1], offsets in [-1, 1];
+          * gconv on the global maximum, in [0, 1];  coarse on y_deq, in [0, q_max] as it stands (no s);  expand on [coarse | y_deq],
+            in [-1, 1] and [0, 1] after s from max|coarse| + q_max."""
+        pk = self._packed
+        if "h2" in pk:
+            return pk["h2"]
+        sa = self.encoder.sa_modules
+        mods = dict(msg0=sa[0].branches[0], msg1=sa[0].branches[1], sa1=sa[1], sa2=sa[2])
+        rows = dict(msg0=pk["msg"][0], msg1=pk["msg"][1], sa1=pk["sa1"], sa2=pk["sa2"])
+        for name, mod in mods.items():
+            first = mod.mlp_stack[0]
+            st = Stack([centred_first_layer(first[0], first[1], device)] + rows[name].layers[1:])
+            C = st[0].K - 3
+            h2_prepare_stack(st, np.concatenate([np.zeros(C), -np.ones(3)]), np.ones(C + 3))
+            pk[name + "_h2"] = st
+        d, n_c = self.latent_dim, pk["coarse"][-1].N
+        h2_prepare_stack(pk["gconv"], np.zeros(pk["gconv"][0].K), np.ones(pk["gconv"][0].K))
+        h2_prepare_stack(pk["coarse"], np.zeros(d), np.full(d, self.q_max))
+        h2_prepare_stack(pk["expand"], np.concatenate([-np.ones(n_c), np.zeros(d)]), np.ones(n_c + d))
+        pk["h2"] = H2Scales(device, None, self._N_AMAX, self._N_DYN)
+        return pk["h2"]
+
+    def _forward_h2(self, x, starts):
+        """forward() in the f16x2 arithmetic: the same selection kernels, every stack through run_planes."""
+        pk, sa, B = self._packed, self.encoder.sa_modules, x.shape[0]
+        sc = self._ensure_h2(x.device)
+        sc.reset()
+        outs, new_xyz = [], None
+        for i, (br, st) in enumerate(zip(sa[0].branches, starts[0])):               # :617-632 (last branch's centroids win)
+            new_xyz, f = br.run(pk["msg%d_h2" % i], x, None, st, h2=(sc,) + self._SLOTS["msg%d" % i])
+            outs.append(f)
+        feats = torch.cat(outs, dim=-1).contiguous()
+        xyz, feats = sa[1].run(pk["sa1_h2"], new_xyz, feats, starts[1], h2=(sc,) + self._SLOTS["sa1"])
+        xyz, feats = sa[2].run(pk["sa2_h2"], xyz, feats, starts[2], h2=(sc,) + self._SLOTS["sa2"])
+        cond = group_max(feats)                                                      # :682 global max
+        tails = self.h2_tails
+
+        def dense(name, f0, f1=None, dyn=None, amax=None):
+            """one dense stack on B rows: [f0 | f1] -> planes -> run_planes (rows)"""
+            if not tails:
+                return pk[name].rows(f0 if f1 is None else torch.cat([f0, f1], dim=1).contiguous())
+            pl, _ = group_planes(f0, f1, ar="f16x2", sig=pk[name][0].h2["sig"], dyn=dyn)
+            return run_planes(pk[name], pl, B, ar="f16x2", dyn=dyn, amax=amax)
+
+        if tails:
+            sc.scale(self._D_GCONV, self._SLOTS["sa2"][3])                          # max cond = the largest output of the last level
+        latent = dense("gconv", cond, dyn=sc.dy(self._D_GCONV))                      # :684
+        y_q, y_deq = torch.empty_like(latent), torch.empty_like(latent)
+        _lib.call("pccx_quantize_st", latent.data_ptr(), latent.numel(), float(self.q_min), float(self.q_max),
+                  int(self.latent_bins), y_q.data_ptr(), y_deq.data_ptr(), _stream())
+        c = dense("coarse", y_deq, amax=sc.am(self._A_COARSE))                       # :710; y_deq lies in [0, q_max]: no s
+        if tails:
+            sc.scale(self._D_EXPAND, self._A_COARSE, add=self.q_max, comb=0)         # |[coarse | y_deq]| <= max|coarse| + q_max
+        e = dense("expand", c, y_deq, dyn=sc.dy(self._D_EXPAND))                     # :711-712
+        return c.view(B, -1, 3), e.view(B, -1, 3), cond, y_q, latent
+
     def forward(self, x, starts):
         """x (B,N,3) on the GPU; starts = [[msg_branch0, msg_branch1], sa2, sa3], each (B,) FPS start
         indices (the reference draws them with torch.randint, pn_kit.py:321).
@@ -889,6 +1012,9 @@ class PointCloudAE(_Packable):
         pk = self._packed
         x = ops._f32c(x, "PointCloudAE")
         B = x.shape[0]
+        h2 = B * x.shape[1] >= self.h2_min_points if self.h2_stacks == "auto" else bool(self.h2_stacks)
+        if h2 and B > 0 and _arith() == "f16x2":
+            return self._forward_h2(x, starts)
         sa = self.encoder.sa_modules
         outs, new_xyz = [], None
         for br, stack, st in zip(sa[0].branches, pk["msg"], starts[0]):             # :617-632 (last branch's centroids win)
