@@ -357,6 +357,12 @@ PCCX_API int pccx_replicate_rows(const int32_t *rep, int64_t P, int row_floats, 
 /* pccx_knn for the queries with rep[b*M + m] == b*M + m only (rep over the (B, M) queries; NULL = all). */
 PCCX_API int pccx_knn_list(const float *q, int B, int M, const float *ref, int N, int K, float *dists, int64_t *idx, float *nn,
                            float patch_scale, const int32_t *rep, void *stream);
+/* pccx_knn for the queries uniq[0 .. *n_uniq) only (pccx_patch_groups over the (B, M) queries; both on the device, NULL = all): the
+ * workgroups walk the list instead of one being launched per query.  The list form covers the shapes pccx_knn_uniq_ok(N, K) accepts
+ * (host only, a pure function: N <= 8192, K <= 256). */
+PCCX_API int pccx_knn_uniq_ok(int N, int K);
+PCCX_API int pccx_knn_uniq(const float *q, int B, int M, const float *ref, int N, int K, float *dists, int64_t *idx, float *nn,
+                           float patch_scale, const int32_t *uniq, const int32_t *n_uniq, void *stream);
 PCCX_API int pccx_patch_knn16_list(const float *patches, int P, int K, void *nbr, const int32_t *uniq, const int32_t *n_uniq,
                                    void *stream);
 PCCX_API int pccx_ae_encode_h2_tables_list(const float *patches, int P, int K, const float *enc_blob, const float *h2_blob, int d,
@@ -368,12 +374,21 @@ PCCX_API int pccx_ae_decode_h2_list(const float *latent_q, int P, int d, int k, 
                                     float *workspace, float *patches_out, float scale, const float *centres,
                                     const float *nrm_center, const float *nrm_longest, int S, double margin, float *pc_out,
                                     const int32_t *uniq, const int32_t *n_uniq, void *stream);
+/* The same for a list much shorter than P (octree_mode "reference"): the head takes one listed tile per workgroup.  Same results. */
+PCCX_API int pccx_ae_decode_h2_short_list(const float *latent_q, int P, int d, int k, const float *dec_blob, const float *h2_blob,
+                                          float *workspace, float *patches_out, float scale, const float *centres,
+                                          const float *nrm_center, const float *nrm_longest, int S, double margin, float *pc_out,
+                                          const int32_t *uniq, const int32_t *n_uniq, void *stream);
 
 /* AE.ConditionalProbabilityModel.forward (AE.py:107-123) + pn_kit.pmf_to_cdf (pn_kit.py:452-461)
  * + torchac's float-CDF -> 16-bit conversion.  centres: (B,S,3), S % 16 == 0.  Any of the outputs
  * may be NULL: pmf (B,S,d,L) f32; cdf (B,S,d,L+1) f32; cdf_int (B,S,d,L+1) int32 holding uint16. */
 PCCX_API int pccx_prob_forward(const float *centres, int B, int S, int d, int L, const float *prob_blob,
                                float *pmf, float *cdf, int32_t *cdf_int, void *stream);
+/* The same outputs, bit for bit, for clouds whose centres repeat (octree_mode "reference": at most 8 distinct rows among 64): each
+ * distinct centre row of a cloud (compared bit for bit) is evaluated once and its tables are copied to the duplicates.  S <= 64. */
+PCCX_API int pccx_prob_forward_distinct(const float *centres, int B, int S, int d, int L, const float *prob_blob,
+                                        float *pmf, float *cdf, int32_t *cdf_int, void *stream);
 
 /* torchac.encode_float_cdf (compress.py:134-136) / decode_float_cdf (decompress.py:92-93) on the
  * integer CDFs of pccx_prob_forward.  One independent stream per cloud of nsym = S*d symbols.

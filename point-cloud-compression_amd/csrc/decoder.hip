@@ -21,14 +21,20 @@
 #include "plane_ring.h"
 
 // uniq / n_uniq (patch_groups.hip; null = every patch): slot `patch` of the tiles holds patch uniq[patch], *n_uniq slots are live;
-// `ntiles` stays the host's tile count of all P patches, the stride of the fragment arrays
+// `ntiles` stays the host's tile count of all P patches, the stride of the fragment arrays.
+// SPLIT (the listed form): one tile per workgroup instead of one per wave -- every wave recomputes the small first layer (16 MFMAs) and
+// takes four of the sixteen m-chunks of the 256 -> 1024 layer, whose 1024 weight fragments come from L2 one group at a time: with an
+// eighth of the patches left on the list, four times the waves are there to hide that latency.  Same arithmetic per column either way.
+// The grid stays the host's tile count (the list's length is on the device): workgroups past the last live tile read *n_uniq and
+// return -- 4096 launched for about 509 live at the headline shape, a few microseconds, where a persistent walk would serialise tiles.
+template <bool SPLIT>
 __global__ __launch_bounds__(256, 2) void dec_head_kernel(const float *__restrict__ latent_q, int P, int d, int ntiles,
                                                           const float *__restrict__ blob, f32x4 *__restrict__ h2p,
                                                           const int *__restrict__ uniq, const int *__restrict__ n_uniq)
 {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int g = lane >> 4, n = lane & 15;
-    const int tile = blockIdx.x * 4 + w;
+    const int tile = SPLIT ? blockIdx.x : blockIdx.x * 4 + w;
     if (uniq) P = *n_uniq;
     if (tile >= (P + 15) / 16) return;                            // whole wave exits
     const int patch = tile * 16 + n;
@@ -43,8 +49,9 @@ __global__ __launch_bounds__(256, 2) void dec_head_kernel(const float *__restric
 #pragma unroll
     for (int mt = 0; mt < 16; ++mt) a1[0][mt] = relu4(a1[0][mt]);
     const f32x4 *w2 = (const f32x4 *)(blob + DEC_H_W2);
+    const int mc0 = SPLIT ? 4 * __builtin_amdgcn_readfirstlane(w) : 0;
 #pragma unroll 1
-    for (int mc = 0; mc < 16; ++mc) {
+    for (int mc = mc0; mc < mc0 + (SPLIT ? 4 : 16); ++mc) {
         const f32x4 *w2c = opaque_uniform(w2) + (size_t)mc * 4 * 64;       // m-tiles 4mc..4mc+3
         f32x4 a2[1][4];
 #pragma unroll
@@ -56,10 +63,15 @@ __global__ __launch_bounds__(256, 2) void dec_head_kernel(const float *__restric
 }
 
 // the head for decoder_h2.hip (same kernel, same fp32 result; that file adds its own operand preparation)
+// per_tile: the one-tile-per-workgroup form, for a list much shorter than P (it recomputes the first layer in every wave: no gain, and
+// about 5 % more work, where most patches are listed)
 int pccx_dec_head_launch(const float *latent_q, int P, int d, int ntiles, const float *dec_blob, float *h2p, const int32_t *uniq,
-                         const int32_t *n_uniq, hipStream_t st)
+                         const int32_t *n_uniq, bool per_tile, hipStream_t st)
 {
-    hipLaunchKernelGGL(dec_head_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, st, latent_q, P, d, ntiles, dec_blob, (f32x4 *)h2p, uniq, n_uniq);
+    if (uniq && per_tile)
+        hipLaunchKernelGGL(dec_head_kernel<true>, dim3(ntiles), dim3(256), 0, st, latent_q, P, d, ntiles, dec_blob, (f32x4 *)h2p, uniq, n_uniq);
+    else
+        hipLaunchKernelGGL(dec_head_kernel<false>, dim3((ntiles + 3) / 4), dim3(256), 0, st, latent_q, P, d, ntiles, dec_blob, (f32x4 *)h2p, uniq, n_uniq);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }
@@ -377,7 +389,7 @@ extern "C" int pccx_ae_decode(const float *latent_q, int P, int d, int k, const 
     if (P == 0) return PCCX_OK;
     hipStream_t st = (hipStream_t)stream;
     const int ntiles = (P + 15) / 16;
-    hipLaunchKernelGGL(dec_head_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, st, latent_q, P, d, ntiles, dec_blob,
+    hipLaunchKernelGGL(dec_head_kernel<false>, dim3((ntiles + 3) / 4), dim3(256), 0, st, latent_q, P, d, ntiles, dec_blob,
                        (f32x4 *)workspace, (const int *)nullptr, (const int *)nullptr);
     PCCX_CHECK_LAUNCH();
     hipLaunchKernelGGL(dec_main_kernel, dim3(dec_grid(ntiles, k)), dim3(256), 0, st, (const f32x4 *)workspace, latent_q, P, d,
@@ -476,7 +488,7 @@ extern "C" int pccx_ae_decode_b3(const float *latent_q, int P, int d, int k, con
     const int ntiles = (P + 15) / 16;
     f32x4 *h2p = (f32x4 *)workspace;
     uint4 *h3 = (uint4 *)(workspace + (size_t)64 * ntiles * 64 * 4);
-    hipLaunchKernelGGL(dec_head_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, st, latent_q, P, d, ntiles, dec_blob, h2p, (const int *)nullptr, (const int *)nullptr);
+    hipLaunchKernelGGL(dec_head_kernel<false>, dim3((ntiles + 3) / 4), dim3(256), 0, st, latent_q, P, d, ntiles, dec_blob, h2p, (const int *)nullptr, (const int *)nullptr);
     PCCX_CHECK_LAUNCH();
     const size_t items = (size_t)32 * ntiles;
     hipLaunchKernelGGL(b3_split_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, (const f32x4 *)h2p, h3, 1, 64, ntiles,

@@ -16,7 +16,7 @@
 #include "plane_ring.h"
 
 int pccx_dec_head_launch(const float *latent_q, int P, int d, int ntiles, const float *dec_blob, float *h2p, const int32_t *uniq,
-                         const int32_t *n_uniq, hipStream_t st);   // decoder.hip
+                         const int32_t *n_uniq, bool per_tile, hipStream_t st);   // decoder.hip
 
 // one wave per tile of 16 patches: the patch scales, then the two fp16 planes of the head activation
 // h2p: [64 kt][ntiles][64 lanes] f32x4 (lane (g, n): channels 16 kt + 4 g + r of patch n); h3: [32 t][ntiles][2][64 lanes] uint4
@@ -237,9 +237,9 @@ extern "C" size_t pccx_ae_decode_h2_workspace_floats(int P)
 // uniq / n_uniq: null, or the representatives of pccx_patch_groups over (centre row, latent_q row) and their count (both on the device).
 // Head, preparation and main then run over those patches only, 16 of them per tile in list order; each result is written to its patch's
 // own place in patches_out / pc_out, and pccx_replicate_rows (k * 3 floats per row) fills the places of the copies.
-extern "C" int pccx_ae_decode_h2_list(const float *latent_q, int P, int d, int k, const float *dec_blob, const float *h2_blob, float *workspace,
-                                      float *patches_out, float scale, const float *centres, const float *nrm_center, const float *nrm_longest,
-                                      int S, double margin, float *pc_out, const int32_t *uniq, const int32_t *n_uniq, void *stream)
+static int dec_h2_list(const float *latent_q, int P, int d, int k, const float *dec_blob, const float *h2_blob, float *workspace,
+                       float *patches_out, float scale, const float *centres, const float *nrm_center, const float *nrm_longest,
+                       int S, double margin, float *pc_out, const int32_t *uniq, const int32_t *n_uniq, bool short_list, void *stream)
 {
     if (P == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
     PCCX_CHECK_ARG(latent_q && dec_blob && h2_blob && workspace, "pccx_ae_decode_h2: null pointer");
@@ -253,7 +253,7 @@ extern "C" int pccx_ae_decode_h2_list(const float *latent_q, int P, int d, int k
     float *h2p = workspace;
     uint4 *h3 = (uint4 *)(workspace + (size_t)64 * ntiles * 64 * 4);
     float *pscale = workspace + (size_t)128 * ntiles * 64 * 4;
-    const int rc = pccx_dec_head_launch(latent_q, P, d, ntiles, dec_blob, h2p, uniq, n_uniq, st);
+    const int rc = pccx_dec_head_launch(latent_q, P, d, ntiles, dec_blob, h2p, uniq, n_uniq, short_list, st);
     if (rc != PCCX_OK) return rc;
     hipLaunchKernelGGL(dec_h2_prep_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, st, (const f32x4 *)h2p, latent_q, P, d, ntiles, 32768.0f, h3, pscale, uniq, n_uniq);
     PCCX_CHECK_LAUNCH();
@@ -267,6 +267,24 @@ extern "C" int pccx_ae_decode_h2_list(const float *latent_q, int P, int d, int k
                            d, k, ntiles, h2_blob, patches_out, scale, centres, nrm_center, nrm_longest, S > 0 ? S : 1, (float)(1.0 - margin), pc_out, uniq, n_uniq);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
+}
+
+extern "C" int pccx_ae_decode_h2_list(const float *latent_q, int P, int d, int k, const float *dec_blob, const float *h2_blob, float *workspace,
+                                      float *patches_out, float scale, const float *centres, const float *nrm_center, const float *nrm_longest,
+                                      int S, double margin, float *pc_out, const int32_t *uniq, const int32_t *n_uniq, void *stream)
+{
+    return dec_h2_list(latent_q, P, d, k, dec_blob, h2_blob, workspace, patches_out, scale, centres, nrm_center, nrm_longest, S, margin, pc_out, uniq,
+                       n_uniq, false, stream);
+}
+
+// the same for a list much shorter than P (octree_mode "reference": about an eighth of the patches): the head takes one listed tile per
+// workgroup (decoder.hip: dec_head_kernel<true>).  Same results.
+extern "C" int pccx_ae_decode_h2_short_list(const float *latent_q, int P, int d, int k, const float *dec_blob, const float *h2_blob, float *workspace,
+                                            float *patches_out, float scale, const float *centres, const float *nrm_center, const float *nrm_longest,
+                                            int S, double margin, float *pc_out, const int32_t *uniq, const int32_t *n_uniq, void *stream)
+{
+    return dec_h2_list(latent_q, P, d, k, dec_blob, h2_blob, workspace, patches_out, scale, centres, nrm_center, nrm_longest, S, margin, pc_out, uniq,
+                       n_uniq, true, stream);
 }
 
 extern "C" int pccx_ae_decode_h2(const float *latent_q, int P, int d, int k, const float *dec_blob, const float *h2_blob, float *workspace,

@@ -171,6 +171,7 @@ __global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ q, i
 #define KNN_PPT 32
 #define KNN_BINS 2048
 #define KNN_CAPB 256
+#define KNN_LIST_GRID (256 * 8)      // the list-walking grid: 8 workgroups (two rounds of the four resident ones) for each of the MI355X's 256 CUs
 
 template <int X>
 __device__ __forceinline__ unsigned knn_xor_lane(unsigned v)             // value of lane (lane ^ X), X < 64
@@ -243,16 +244,13 @@ __device__ __forceinline__ void knn_level(const unsigned (&key)[KNN_PPT], int *h
     cnt = s_found[2];
 }
 
-__global__ __launch_bounds__(256, 4) void knn_fast_kernel(const float *__restrict__ q, int M, const float *__restrict__ ref,
-                                                       int N, int K, float *__restrict__ dists, int64_t *__restrict__ idx,
-                                                       float *__restrict__ nn, float patch_scale, const int *__restrict__ rep)
+// one query (m of cloud b) by the workgroup; the shared arrays come from the kernel
+__device__ __forceinline__ void knn_fast_query(const float *__restrict__ q, int M, const float *__restrict__ ref, int N, int K,
+                                               float *__restrict__ dists, int64_t *__restrict__ idx, float *__restrict__ nn, float patch_scale,
+                                               int m, int b, int tid, int *hist, unsigned long long *selA, unsigned long long *selB,
+                                               int *s_wsum, int *s_found, int *s_cnt)
 {
-    __shared__ int hist[KNN_BINS];
-    __shared__ unsigned long long selA[256], selB[KNN_CAPB];
-    __shared__ int s_wsum[4], s_found[3], s_cnt[2];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int m = blockIdx.x, b = blockIdx.y;
-    if (rep && rep[b * M + m] != b * M + m) return;                       // a copy of an earlier query of this cloud (patch_groups.hip): its rows stay unwritten
+    const int lane = tid & 63, w = tid >> 6;
     const float *rp = ref + (size_t)b * N * 3;
     const size_t qo = ((size_t)b * M + m) * 3;
     const float qx = q[qo], qy = q[qo + 1], qz = q[qo + 2];
@@ -376,10 +374,43 @@ __global__ __launch_bounds__(256, 4) void knn_fast_kernel(const float *__restric
     }
 }
 
+__global__ __launch_bounds__(256, 4) void knn_fast_kernel(const float *__restrict__ q, int M, const float *__restrict__ ref,
+                                                       int N, int K, float *__restrict__ dists, int64_t *__restrict__ idx,
+                                                       float *__restrict__ nn, float patch_scale, const int *__restrict__ rep)
+{
+    __shared__ int hist[KNN_BINS];
+    __shared__ unsigned long long selA[256], selB[KNN_CAPB];
+    __shared__ int s_wsum[4], s_found[3], s_cnt[2];
+    const int m = blockIdx.x, b = blockIdx.y;
+    if (rep && rep[b * M + m] != b * M + m) return;                       // a copy of an earlier query of this cloud (patch_groups.hip): its rows stay unwritten
+    knn_fast_query(q, M, ref, N, K, dists, idx, nn, patch_scale, m, b, threadIdx.x, hist, selA, selB, s_wsum, s_found, s_cnt);
+}
+
+// the same over the queries uniq[0 .. *n_uniq) (patch_groups.hip; both on the device): the workgroups of a one-dimensional grid walk the list
+__global__ __launch_bounds__(256, 4) void knn_fast_list_kernel(const float *__restrict__ q, int M, const float *__restrict__ ref,
+                                                            int N, int K, float *__restrict__ dists, int64_t *__restrict__ idx,
+                                                            float *__restrict__ nn, float patch_scale, const int *__restrict__ uniq,
+                                                            const int *__restrict__ n_uniq)
+{
+    __shared__ int hist[KNN_BINS];
+    __shared__ unsigned long long selA[256], selB[KNN_CAPB];
+    __shared__ int s_wsum[4], s_found[3], s_cnt[2];
+    const int nlist = *n_uniq;
+    for (int slot = blockIdx.x; slot < nlist; slot += gridDim.x) {
+        // the thread index is laundered per query: left visible, the 32 candidate offsets it determines are hoisted out of the loop and
+        // the kernel spills far more than it does now
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        const int p = uniq[slot];
+        knn_fast_query(q, M, ref, N, K, dists, idx, nn, patch_scale, p % M, p / M, tid, hist, selA, selB, s_wsum, s_found, s_cnt);
+        __syncthreads();                                                  // the shared arrays serve the next query of the list
+    }
+}
+
 // rep: null, or the (B * M) table of pccx_patch_groups over the queries -- only queries with rep[p] == p are computed, the output rows
 // of the others are left as they were (their results equal their representative's: same query, same cloud)
-extern "C" int pccx_knn_list(const float *q, int B, int M, const float *ref, int N, int K, float *dists, int64_t *idx,
-                             float *nn, float patch_scale, const int32_t *rep, void *stream)
+static int knn_launch(const float *q, int B, int M, const float *ref, int N, int K, float *dists, int64_t *idx, float *nn,
+                      float patch_scale, const int32_t *rep, const int32_t *uniq, const int32_t *n_uniq, void *stream)
 {
     if (B == 0 || M == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
     PCCX_CHECK_ARG(q && ref && (dists || idx || nn), "pccx_knn: null pointer (q, ref and at least one of dists / idx / nn are needed)");
@@ -392,20 +423,45 @@ extern "C" int pccx_knn_list(const float *q, int B, int M, const float *ref, int
     size_t shmem = (size_t)Kp * 8 + (size_t)N * 4 + (256 + 4 + 3 + 1) * 4;
     PCCX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if (N <= 256 * KNN_PPT && K <= 256)
-        hipLaunchKernelGGL(knn_fast_kernel, dim3(M, B), dim3(256), 0, (hipStream_t)stream, q, M, ref, N, K, dists, idx, nn,
-                           patch_scale, rep);
-    else
+    if (N <= 256 * KNN_PPT && K <= 256) {
+        // with a list: a one-dimensional grid sized from B M and capped -- the list's length stays on the device
+        const long long bm = (long long)B * M;
+        const dim3 grid = uniq ? dim3((unsigned)(bm < KNN_LIST_GRID ? bm : KNN_LIST_GRID)) : dim3(M, B);
+        if (uniq)
+            hipLaunchKernelGGL(knn_fast_list_kernel, grid, dim3(256), 0, (hipStream_t)stream, q, M, ref, N, K, dists, idx, nn, patch_scale, uniq, n_uniq);
+        else
+            hipLaunchKernelGGL(knn_fast_kernel, grid, dim3(256), 0, (hipStream_t)stream, q, M, ref, N, K, dists, idx, nn, patch_scale, rep);
+    } else
         hipLaunchKernelGGL(knn_kernel, dim3(M, B), dim3(256), shmem, (hipStream_t)stream, q, M, ref, N, K, Kp, dists, idx, nn,
                            patch_scale, rep);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }
 
+extern "C" int pccx_knn_list(const float *q, int B, int M, const float *ref, int N, int K, float *dists, int64_t *idx,
+                             float *nn, float patch_scale, const int32_t *rep, void *stream)
+{
+    return knn_launch(q, B, M, ref, N, K, dists, idx, nn, patch_scale, rep, nullptr, nullptr, stream);
+}
+
+// uniq / n_uniq: null, or the representatives of pccx_patch_groups over the (B, M) queries and their count (both on the device): the
+// fast kernel (N <= 8192, K <= 256) walks that list; the radix-select kernel skips the other queries through `rep` as pccx_knn_list does,
+// so it is handed the table only through that entry point and refuses a list here
+extern "C" int pccx_knn_uniq_ok(int N, int K) { return N >= 1 && N <= 256 * KNN_PPT && K >= 1 && K <= 256 && K <= N; }
+
+extern "C" int pccx_knn_uniq(const float *q, int B, int M, const float *ref, int N, int K, float *dists, int64_t *idx, float *nn,
+                             float patch_scale, const int32_t *uniq, const int32_t *n_uniq, void *stream)
+{
+    PCCX_CHECK_ARG(!uniq == !n_uniq, "pccx_knn_uniq: uniq and n_uniq come together");
+    PCCX_CHECK_ARG(!uniq || pccx_knn_uniq_ok(N, K), "pccx_knn_uniq: the list form needs N <= %d and K <= 256 (N=%d K=%d); use pccx_knn_list",
+                   256 * KNN_PPT, N, K);
+    return knn_launch(q, B, M, ref, N, K, dists, idx, nn, patch_scale, nullptr, uniq, n_uniq, stream);
+}
+
 extern "C" int pccx_knn(const float *q, int B, int M, const float *ref, int N, int K, float *dists, int64_t *idx,
                         float *nn, float patch_scale, void *stream)
 {
-    return pccx_knn_list(q, B, M, ref, N, K, dists, idx, nn, patch_scale, nullptr, stream);
+    return knn_launch(q, B, M, ref, N, K, dists, idx, nn, patch_scale, nullptr, nullptr, nullptr, stream);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -170,6 +170,266 @@ __global__ __launch_bounds__(256, 2) void prob_forward_kernel(const float *__res
     ws.drain();                                           // no DMA may land after the workgroup retires
 }
 
+// ---- the table stage of prob_forward_distinct_kernel: a wave copies the rows of every centre of its cloud from the centre's slot.
+// rows = the wave's [16][128] floats (pmf, later the clamped cumsum, of the tile's slots), slots = centre -> slot.  The lanes share out
+// (centre, W consecutive words of its row): a centre's row is contiguous in the output, so W = 4 is one 16-byte store per lane
+// (row length a multiple of 4 and the array 16-byte aligned; W = 1 otherwise).
+__device__ __forceinline__ void prob_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int W>
+__device__ __forceinline__ void prob_store_pmf(const float *rows, const int *slots, int nslots, int t, int lane, size_t row0, int rl,
+                                               float *__restrict__ pmf)
+{
+    const int per = rl / W;
+    for (int it = lane; it < nslots * per; it += 64) {
+        const int c = it / per, j = (it % per) * W, sl = slots[c];
+        if ((sl >> 4) != t) continue;
+        const float *src = rows + (sl & 15) * 128 + j;
+        float *dst = pmf + (row0 + c) * (size_t)rl + j;
+        if constexpr (W == 4) *(f32x4 *)dst = *(const f32x4 *)src;
+        else *dst = *src;
+    }
+}
+
+template <int W>
+__device__ __forceinline__ void prob_store_cdf(const float *rows, const int *slots, int nslots, int t, int lane, size_t row0, int d, int L,
+                                               float *__restrict__ cdf, int32_t *__restrict__ cdf_int)
+{
+    const int Lp = L + 1, rl = d * Lp, per = rl / W;
+    for (int it = lane; it < nslots * per; it += 64) {
+        const int c = it / per, j = (it % per) * W, sl = slots[c];
+        if ((sl >> 4) != t) continue;
+        float cv[W];
+        int ci[W];
+#pragma unroll
+        for (int q = 0; q < W; ++q) {
+            const int i = (j + q) / Lp, l = (j + q) % Lp;                          // level 0 of a row is the leading zero
+            cv[q] = l ? rows[(sl & 15) * 128 + i * L + l - 1] : 0.f;
+            // torchac: round(cdf * (2^16 - (Lp-1))) + arange(Lp), kept to 16 bits
+            ci[q] = l ? ((int)rintf(cv[q] * (float)(65536 - (Lp - 1))) + l) & 0xFFFF : 0;
+        }
+        const size_t o = (row0 + c) * (size_t)rl + j;
+        if constexpr (W == 4) {
+            if (cdf) *(f32x4 *)(cdf + o) = f32x4{cv[0], cv[1], cv[2], cv[3]};
+            if (cdf_int) *(int4 *)(cdf_int + o) = make_int4(ci[0], ci[1], ci[2], ci[3]);
+        } else {
+            if (cdf) cdf[o] = cv[0];
+            if (cdf_int) cdf_int[o] = ci[0];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// The same function for clouds whose centres repeat (octree_mode "reference": at most 8 distinct rows among a cloud's 64).  A column of
+// an MFMA tile depends on nothing but its own input column, and pass 1's maximum is the same over the distinct centres as over all of
+// them, so every distinct centre row is evaluated once and its tables are copied to the duplicates: bit for bit prob_forward_kernel's
+// outputs.
+// Workgroup = FOUR clouds, one per wave (a wave past the batch walks the last cloud and writes nothing: the ring's barriers need it).
+//   distinct: lane c holds centre c (S <= 64); rows are compared bit for bit, the representative is the first equal row and its slot its
+//             rank among the representatives; slot -> centre and centre -> slot go to LDS.  Slots past the last one read centre 0.
+//   pass 1 : as above on tiles of 16 slots, all of the wave's own
+//   pass 1b: once per workgroup -- column n of the B operand carries cloud (n & 3)'s feature, a quarter of the 512 rows per wave
+//   pass 2 : tiles of 16 slots; the loop count is the workgroup's largest (a wave with fewer tiles walks its last one again)
+//   tables : softmax once per (slot, latent dim), in place over the logits, then the pmf rows of every centre of the tile's slots are
+//            copied out; the cumsum + clamp again in place, then the cdf / cdf_int rows (the integer CDF is a function of the clamped
+//            value and the level alone).  One expf pair per distinct (centre, dim, level) instead of per centre.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256, 2) void prob_forward_distinct_kernel(const float *__restrict__ centres, int B, int S, int d, int L,
+                                                                       const float *__restrict__ blob, float *__restrict__ pmf,
+                                                                       float *__restrict__ cdf, int32_t *__restrict__ cdf_int)
+{
+    __shared__ __attribute__((aligned(16))) f32x4 swt[4 * PRB_WS_CHUNK * 64];   // 32 KiB weight ring, four chunks deep
+    __shared__ __attribute__((aligned(16))) float sfeat[4][256];
+    __shared__ __attribute__((aligned(16))) float su[4][512];
+    __shared__ __attribute__((aligned(16))) float slog[4][16][128];
+    __shared__ int slot_of[4][64], cen_of[4][64], s_nt[4];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int g = lane >> 4, n = lane & 15;
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    const int bw = blockIdx.x * 4 + wu;
+    const bool live = bw < B;
+    const size_t b = live ? bw : B - 1;
+    const float *cp = centres + b * (size_t)S * 3;
+    WStreamT<PRB_WS_CHUNK, 4, 4> ws{blob + PRB_STREAM, swt, PRB_STREAM_CHUNKS, lane, wu, true};
+    ws.prologue();                                        // the first chunks of model_mlp arrive while model_pn runs
+
+    // ---- the distinct centres of this wave's cloud
+    int nt;
+    {
+        const bool valid = lane < S;
+        const int cl = valid ? lane : S - 1;
+        const unsigned kx = __float_as_uint(cp[3 * cl]), ky = __float_as_uint(cp[3 * cl + 1]), kz = __float_as_uint(cp[3 * cl + 2]);
+        int rep = cl;
+        for (int j = S - 1; j >= 0; --j) {                // descending: the first equal row is the one that stays
+            const unsigned jx = __builtin_amdgcn_readlane(kx, j), jy = __builtin_amdgcn_readlane(ky, j), jz = __builtin_amdgcn_readlane(kz, j);
+            if (jx == kx && jy == ky && jz == kz) rep = j;
+        }
+        const unsigned long long reps = __ballot(valid && rep == lane);
+        const int rank = __popcll(reps & ((1ull << lane) - 1ull));
+        const int slot = __shfl(rank, rep);
+        // slot -> centre in ONE store per lane, so no order between stores is relied on: lane s < n_distinct takes the s-th set bit of
+        // the representatives' mask (slots are ranks, so that lane is the slot's centre), the other slots read centre 0
+        {
+            unsigned long long m = reps;
+            const int nd = __popcll(reps);
+            for (int i = 0; i < (lane < nd ? lane : 0); ++i) m &= m - 1ull;
+            cen_of[w][lane] = lane < nd ? __ffsll((long long)m) - 1 : 0;
+        }
+        if (valid) slot_of[w][lane] = slot;
+        nt = __builtin_amdgcn_readfirstlane((__popcll(reps) + 15) >> 4);
+        if (lane == 0) s_nt[w] = nt;
+    }
+    __syncthreads();
+
+    // ---- pass 1: model_pn (AE.py:96,112) over the wave's own slots
+    {
+        f32x4 run[16];
+#pragma unroll
+        for (int mt = 0; mt < 16; ++mt) run[mt][0] = run[mt][1] = run[mt][2] = run[mt][3] = -INFINITY;
+        for (int tile = 0; tile < nt; ++tile) {
+            const float *bl = opaque_uniform(blob);
+            const int c = cen_of[w][tile * 16 + n];
+            f32x4 in[1][1];
+            in[0][0][0] = g == 0 ? cp[3 * c] : 0.f;
+            in[0][0][1] = g == 0 ? cp[3 * c + 1] : 0.f;
+            in[0][0][2] = g == 0 ? cp[3 * c + 2] : 0.f;
+            in[0][0][3] = 0.f;
+            f32x4 a0[1][4];
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) a0[0][mt] = *(const f32x4 *)(bl + PRB_P_B0 + 16 * mt + 4 * g);
+            dense_acc<1, 4, 1, 4>((const f32x4 *)(bl + PRB_P_W0), lane, in, a0);
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) a0[0][mt] = relu4(a0[0][mt]);
+            f32x4 a1[1][8];
+#pragma unroll
+            for (int mt = 0; mt < 8; ++mt) a1[0][mt] = *(const f32x4 *)(bl + PRB_P_B1 + 16 * mt + 4 * g);
+            dense_acc<4, 8, 1, 8>((const f32x4 *)(bl + PRB_P_W1), lane, a0, a1);
+#pragma unroll
+            for (int mt = 0; mt < 8; ++mt) a1[0][mt] = relu4(a1[0][mt]);
+            f32x4 a2[1][16];
+#pragma unroll
+            for (int mt = 0; mt < 16; ++mt) a2[0][mt] = *(const f32x4 *)(bl + PRB_P_B2 + 16 * mt + 4 * g);
+            dense_acc<8, 16, 1, 16>((const f32x4 *)(bl + PRB_P_W2), lane, a1, a2);
+#pragma unroll
+            for (int mt = 0; mt < 16; ++mt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) run[mt][r] = fmaxf(run[mt][r], fmaxf(row16_max(a2[0][mt][r]), 0.f));
+        }
+        if (n == 0)
+#pragma unroll
+            for (int mt = 0; mt < 16; ++mt) *(f32x4 *)(&sfeat[w][16 * mt + 4 * g]) = run[mt];
+    }
+    __syncthreads();
+    const int ntmax = max(max(s_nt[0], s_nt[1]), max(s_nt[2], s_nt[3]));
+
+    // ---- pass 1b: u = b0 + W0[:, feature channels] feat for the four clouds at once: column n is cloud n & 3, rows 128 w .. 128 w + 127
+    {
+        const float *bl = opaque_uniform(blob);
+        f32x4 fin[1][16];
+#pragma unroll
+        for (int kt = 0; kt < 16; ++kt) fin[0][kt] = *(const f32x4 *)(&sfeat[n & 3][16 * kt + 4 * g]);
+        f32x4 u[1][8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) u[0][m] = *(const f32x4 *)(bl + PRB_M_B0 + 16 * (8 * wu + m) + 4 * g);
+        dense_acc<16, 8, 1, 32>((const f32x4 *)(bl + PRB_M_W0), lane, fin, u, 0, 8 * wu);
+        if (n < 4)
+#pragma unroll
+            for (int m = 0; m < 8; ++m) *(f32x4 *)(&su[n][16 * (8 * wu + m) + 4 * g]) = u[0][m];
+    }
+    __syncthreads();
+
+    // ---- pass 2: model_mlp (AE.py:97-105,115-118) on tiles of slots, then the tables of every centre
+    const int Lp = L + 1;
+    for (int t = 0; t < ntmax; ++t) {
+        const bool act = live && t < nt;                  // wave-uniform
+        {
+            const float *bl = opaque_uniform(blob);
+            ws.g = bl + PRB_STREAM;
+            // lane indices from a laundered lane id, as in prob_forward_kernel: nothing is carried through the wide layers' accumulators
+            int lane2 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            asm volatile("" : "+v"(lane2));
+            const int g = lane2 >> 4, n = lane2 & 15;
+            ws.lane = lane2;
+            const int c = cen_of[wu][(t < nt ? t : nt - 1) * 16 + n];
+            int f = 0;
+            f32x4 a0[1][32];
+#pragma unroll
+            for (int mt = 0; mt < 32; ++mt) a0[0][mt] = *(const f32x4 *)(&su[wu][16 * mt + 4 * g]);   // bias + the feature k-tiles (pass 1b)
+            {
+                f32x4 in[1][1];
+                in[0][0][0] = g == 0 ? cp[3 * c] : 0.f;
+                in[0][0][1] = g == 0 ? cp[3 * c + 1] : 0.f;
+                in[0][0][2] = g == 0 ? cp[3 * c + 2] : 0.f;
+                in[0][0][3] = 0.f;
+                dense_acc_stream<1, 32, 1>(ws, f, in, a0);                                              // the xyz k-tile, last as before
+            }
+#pragma unroll
+            for (int mt = 0; mt < 32; ++mt) a0[0][mt] = relu4(a0[0][mt]);
+            f32x4 a2[1][8];
+#pragma unroll
+            for (int mt = 0; mt < 8; ++mt) a2[0][mt] = *(const f32x4 *)(bl + PRB_M_B2 + 16 * mt + 4 * g);
+#pragma clang loop unroll(full)
+            for (int mp = 0; mp < 16; ++mp) {
+                f32x4 a1[1][2];
+#pragma unroll
+                for (int m = 0; m < 2; ++m) a1[0][m] = *(const f32x4 *)(bl + PRB_M_B1 + 16 * (2 * mp + m) + 4 * g);
+                dense_acc_stream<32, 2, 1>(ws, f, a0, a1);
+#pragma unroll
+                for (int m = 0; m < 2; ++m) a1[0][m] = relu4(a1[0][m]);
+                dense_acc_stream<2, 8, 1>(ws, f, a1, a2);
+            }
+            if (t < nt)
+#pragma unroll
+                for (int mt = 0; mt < 8; ++mt) *(f32x4 *)(&slog[wu][n][16 * mt + 4 * g]) = a2[0][mt];
+        }
+        // From here to the end of the tile a wave touches its own slog / slot_of only: LDS operations of one wave complete in order, so
+        // a wave-local fence (prob_wave_sync) orders the phases and the four clouds of the workgroup do not wait for each other.
+        prob_wave_sync();
+        // softmax, one thread per (slot, latent dim) of the tile, in place: the L logits of the pair become its pmf
+        const int nslots = S < 64 ? S : 64;               // slot_of / cen_of entries of this cloud
+        if (act)
+            for (int e = lane; e < 16 * d; e += 64) {
+                float *lg = &slog[wu][e / d][(e % d) * L];      // output.view(B,S,d,L): channel i*L + l
+                float mx = -INFINITY;
+                for (int l = 0; l < L; ++l) mx = fmaxf(mx, lg[l]);
+                float sum = 0.f;
+                for (int l = 0; l < L; ++l) sum += expf(lg[l] - mx);
+                for (int l = 0; l < L; ++l) lg[l] = expf(lg[l] - mx) / sum;
+            }
+        prob_wave_sync();
+        if (act && pmf) {
+            if ((d * L) % 4 == 0 && ((uintptr_t)pmf & 15) == 0) prob_store_pmf<4>(&slog[wu][0][0], slot_of[wu], nslots, t, lane, b * S, d * L, pmf);
+            else prob_store_pmf<1>(&slog[wu][0][0], slot_of[wu], nslots, t, lane, b * S, d * L, pmf);
+        }
+        if (cdf || cdf_int) {
+            prob_wave_sync();
+            if (act)
+                for (int e = lane; e < 16 * d; e += 64) {
+                    float *lg = &slog[wu][e / d][(e % d) * L];
+                    float run_c = 0.f;
+                    for (int l = 0; l < L; ++l) {
+                        run_c = run_c + lg[l];                                     // cumsum (pn_kit.py:453)
+                        lg[l] = fminf(run_c, 1.0f);                                // clamp(max=1) (pn_kit.py:460)
+                    }
+                }
+            prob_wave_sync();
+            if (act) {
+                if ((d * Lp) % 4 == 0 && (((uintptr_t)cdf | (uintptr_t)cdf_int) & 15) == 0)
+                    prob_store_cdf<4>(&slog[wu][0][0], slot_of[wu], nslots, t, lane, b * S, d, L, cdf, cdf_int);
+                else
+                    prob_store_cdf<1>(&slog[wu][0][0], slot_of[wu], nslots, t, lane, b * S, d, L, cdf, cdf_int);
+            }
+        }
+        prob_wave_sync();
+    }
+    ws.drain();                                           // no DMA may land after the workgroup retires
+}
+
 extern "C" int pccx_prob_forward(const float *centres, int B, int S, int d, int L, const float *prob_blob, float *pmf,
                                  float *cdf, int32_t *cdf_int, void *stream)
 {
@@ -180,6 +440,20 @@ extern "C" int pccx_prob_forward(const float *centres, int B, int S, int d, int 
     PCCX_CHECK_ARG(d >= 1 && d <= 16 && L >= 1 && L <= 15 && d * L <= 128, "pccx_prob_forward: unsupported d=%d L=%d", d, L);
     hipLaunchKernelGGL(prob_forward_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, centres, S, d, L, prob_blob, pmf, cdf,
                        cdf_int);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+extern "C" int pccx_prob_forward_distinct(const float *centres, int B, int S, int d, int L, const float *prob_blob, float *pmf,
+                                          float *cdf, int32_t *cdf_int, void *stream)
+{
+    if (B == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
+    PCCX_CHECK_ARG(centres && prob_blob, "pccx_prob_forward_distinct: null pointer");
+    PCCX_CHECK_ARG(pmf || cdf || cdf_int, "pccx_prob_forward_distinct: no output requested");
+    PCCX_CHECK_ARG(B >= 0 && S >= 16 && S % 16 == 0 && S <= 64, "pccx_prob_forward_distinct: need S %% 16 == 0, S <= 64 (S=%d)", S);
+    PCCX_CHECK_ARG(d >= 1 && d <= 16 && L >= 1 && L <= 15 && d * L <= 128, "pccx_prob_forward_distinct: unsupported d=%d L=%d", d, L);
+    hipLaunchKernelGGL(prob_forward_distinct_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, centres, B, S, d, L, prob_blob,
+                       pmf, cdf, cdf_int);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }

@@ -190,6 +190,12 @@ class Codec:
         if ae.K != K or ae.k != self.k:
             raise ValueError("AE was built for a different K / k")
 
+    def _distinct(self):
+        """Whether the centres of a cloud repeat (at most 8 distinct among 64): then the probability model runs its distinct-centre form,
+        the kNN patching walks the list and the decoder head takes one listed tile per workgroup.  In "full" mode the lists hold nearly every
+        patch, where those forms cost more than they save, and the kernels take the lists as before."""
+        return self.octree_mode == "reference" and self.group_duplicates
+
     def compress(self, pc, start_idx, keep_extras=False):
         """pc (B,N,3) f32 on the GPU; start_idx (B,) FPS start per cloud (the reference draws it
         from torch.randint, pn_kit.py:321)."""
@@ -218,11 +224,11 @@ class Codec:
         with stage("knn_patches"):
             nn = ops.knn_points(rec, pcn, self.K, patch_scale=scale,                 # compress.py:105-108 (KNN_Patching keeps the
                                 return_dists=False, return_idx=keep_extras,          # patches; the indices only for diagnostics)
-                                rep=None if keep_extras or groups is None else groups.rep)
+                                **({} if keep_extras or groups is None else {"groups": groups} if self._distinct() else {"rep": groups.rep}))
         patches = nn.knn.view(B * S, self.K, 3)
         raw, latent, q = self.ae.encode(patches, sa_matmul=self.sa_matmul, pn_matmul=self.pn_matmul, groups=groups)                      # compress.py:113-127
         with stage("prob"):
-            cdf_int = self.prob.run(rec, ("cdf_int",))["cdf_int"]                    # compress.py:131-134
+            cdf_int = self.prob.run(rec, ("cdf_int",), distinct=self._distinct())["cdf_int"]                    # compress.py:131-134
         with stage("range_encode"):
             models.range_encode(cdf_int, q.view(B, S * d), L, out=comp.p_bytes, nb=comp.p_nbytes)   # compress.py:135-136
         comp.c[:, :3].copy_(center)                                                  # compress.py:149-152
@@ -246,7 +252,7 @@ class Codec:
         cdf_int = getattr(comp, "_cdf_int", None) if reuse_cdf else None
         if cdf_int is None or cdf_int.shape[0] != B or cdf_int.shape[1] != S:
             with stage("prob"):
-                cdf_int = self.prob.run(rec, ("cdf_int",))["cdf_int"]                     # decompress.py:88-92
+                cdf_int = self.prob.run(rec, ("cdf_int",), distinct=self._distinct())["cdf_int"]                     # decompress.py:88-92
         with stage("range_decode"):
             q = models.range_decode(cdf_int, comp.p_bytes, comp.p_nbytes, L)              # decompress.py:93
         N = S * self.k                                                                    # decompress.py:106
@@ -254,7 +260,7 @@ class Codec:
         with stage("ae_decode"):
             return self.ae.decode(q.view(B * S, d), rec.view(B * S, 3), comp.c[:, :3].contiguous(),
                                   comp.c[:, 3].contiguous(), S=S, scale=scale, margin=self.margin,
-                                  matmul=self.decoder_matmul, group=self.group_duplicates)
+                                  matmul=self.decoder_matmul, group=self.group_duplicates, short_list=self._distinct())
 
 
 def d1_psnr(orig, recon, search=None, index=None):

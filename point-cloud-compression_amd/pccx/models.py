@@ -449,13 +449,15 @@ class AE(nn.Module):
             outs.append(self.inv_mlp(mlp_in).transpose(2, 1).contiguous())                         # :101-102
         return torch.cat(outs) if outs else torch.empty(0, self.k, 3, device=q.device)
 
-    def decode(self, latent_q, centres=None, center=None, longest=None, S=None, scale=None, margin=0.01, matmul=None, group=False):
+    def decode(self, latent_q, centres=None, center=None, longest=None, S=None, scale=None, margin=0.01, matmul=None, group=False, short_list=False):
         """latent_q (BS,d) -> decoded patches (BS,k,3) (AE.py:48-53).  With centres/center/longest/S/scale
         it returns instead the reassembled, denormalised cloud (B,S*k,3) of decompress.py:104-116.
         matmul="bf16x3" / "f16x2" evaluate the matrix products as fp32 products of three bf16 / two exactly scaled fp16 pieces
         per operand on the matrix cores (fp32-level error, not bit-identical to "f32"); None = pccx.DEFAULT_MATMUL.
         group=True (reassembling form, "f16x2"): patches of a cloud with the same (centre row, latent_q row) decode to the same 3 k floats, so
-        the decoder runs once per distinct pair (ops.patch_groups) and the copies are filled from it; the other modes decode every patch."""
+        the decoder runs once per distinct pair (ops.patch_groups) and the copies are filled from it; the other modes decode every patch.
+        short_list=True (with group): the caller expects far fewer distinct pairs than patches (octree_mode "reference"), and the head runs in
+        its one-tile-per-workgroup form; same result."""
         matmul = matmul or _pccx_default_matmul()
         q = _f32c(latent_q, "AE.decode")
         P = q.shape[0]
@@ -489,6 +491,8 @@ class AE(nn.Module):
             lists = (groups.uniq.data_ptr(), groups.n_uniq.data_ptr()) if groups is not None else (None, None)
         # patches_out, then the reassembling arguments, then pc_out: one of the two destinations is null
         dest = (None, *form, result.data_ptr()) if reassemble else (result.data_ptr(), *form, None)
+        if groups is not None and short_list:
+            fn = "pccx_ae_decode_h2_short_list"
         _lib.call(fn, q.data_ptr(), P, self.d, self.k, dec.data_ptr(), *extra, ws.data_ptr(), *dest, *lists, _stream())
         if groups is not None:
             replicate_rows(groups, result)
@@ -537,8 +541,10 @@ class ConditionalProbabilityModel(nn.Module):
         self._blob = blob.to(device)
         return self
 
-    def run(self, sampled_xyz, want=("pmf",)):
-        """sampled_xyz (B,S,3) -> dict with any of pmf (B,S,d,L), cdf (B,S,d,L+1), cdf_int (int32)."""
+    def run(self, sampled_xyz, want=("pmf",), distinct=False):
+        """sampled_xyz (B,S,3) -> dict with any of pmf (B,S,d,L), cdf (B,S,d,L+1), cdf_int (int32).
+        distinct=True (clouds whose centres repeat, octree_mode "reference"): the fused kernel that evaluates each distinct centre of a
+        cloud once, for S <= 64 -- the same outputs bit for bit; other shapes take the usual path."""
         x = _f32c(sampled_xyz, "ConditionalProbabilityModel")
         B, S, _ = x.shape
         if not self.fused_ok(S):
@@ -546,7 +552,8 @@ class ConditionalProbabilityModel(nn.Module):
         if self._blob is None or self._blob.device != x.device:
             self.pack(x.device)
         r, ptrs = self._outputs(want, B, S, x.device)
-        _lib.call("pccx_prob_forward", x.data_ptr(), B, S, self.d, self.L, self._blob.data_ptr(), *ptrs, _stream())
+        fn = "pccx_prob_forward_distinct" if distinct and S <= 64 else "pccx_prob_forward"
+        _lib.call(fn, x.data_ptr(), B, S, self.d, self.L, self._blob.data_ptr(), *ptrs, _stream())
         return r
 
     def _outputs(self, want, B, S, device):

@@ -165,11 +165,12 @@ def replicate_rows(groups, *arrays):
         _lib.call("pccx_replicate_rows", groups.rep.data_ptr(), P, arrays[0].numel() // max(P, 1), *ptrs, _stream())
 
 
-def knn_points(p1, p2, K, return_nn=True, patch_scale=0.0, return_dists=True, return_idx=True, rep=None):
+def knn_points(p1, p2, K, return_nn=True, patch_scale=0.0, return_dists=True, return_idx=True, rep=None, groups=None):
     """pytorch3d.ops.knn_points (compress.py:71, pn_kit.py:190).  With patch_scale != 0 the third
     field holds (nn - p1) * patch_scale, i.e. compress.py:72 and :108 fused.  return_dists / return_idx = False leave that field None
     and its bytes unwritten (KNN_Patching, compress.py:70-74, keeps the gathered points only).
-    rep: Groups.rep over the (B, M) queries -- only the representatives are searched, the rows of the other queries stay unwritten."""
+    rep: Groups.rep over the (B, M) queries -- only the representatives are searched, the rows of the other queries stay unwritten.
+    groups: the Groups themselves -- the same, with the workgroups walking groups.uniq instead of one being launched per query."""
     p1, p2 = _f32c(p1, "knn_points.p1"), _f32c(p2, "knn_points.p2")
     B, M, _ = p1.shape
     N = p2.shape[1]
@@ -179,6 +180,14 @@ def knn_points(p1, p2, K, return_nn=True, patch_scale=0.0, return_dists=True, re
     ptr = lambda t: t.data_ptr() if t is not None else None
     if rep is not None and (rep.dtype != torch.int32 or rep.numel() != B * M or not rep.is_cuda or not rep.is_contiguous()):
         raise _lib.PccxError("knn_points: rep must be the dense int32 (B*M) table of patch_groups over the queries")
+    if groups is not None:
+        if rep is not None or groups.rep.numel() != B * M:
+            raise _lib.PccxError("knn_points: groups must be the patch_groups of the (B, M) queries, given without rep")
+        if _lib.load().pccx_knn_uniq_ok(N, int(K)):
+            _lib.call("pccx_knn_uniq", p1.data_ptr(), B, M, p2.data_ptr(), N, int(K), ptr(dists), ptr(idx), ptr(nn), float(patch_scale),
+                      groups.uniq.data_ptr(), groups.n_uniq.data_ptr(), _stream())
+            return KNN(dists, idx, nn)
+        rep = groups.rep                       # the radix-select kernel of the larger shapes skips by the table
     _lib.call("pccx_knn_list", p1.data_ptr(), B, M, p2.data_ptr(), N, int(K), ptr(dists), ptr(idx), ptr(nn), float(patch_scale), ptr(rep), _stream())
     return KNN(dists, idx, nn)
 
