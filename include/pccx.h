@@ -130,6 +130,9 @@ PCCX_API int pccx_grid_dims(int N, float ex, float ey, float ez, int32_t *dims, 
 PCCX_API size_t pccx_grid_index_workspace_bytes(int B, int N);
 PCCX_API size_t pccx_grid_query_workspace_bytes(int B, int M);
 PCCX_API int pccx_grid_index_build(const float *Y, int B, int N, void *workspace, void *stream);
+/* The same index with about `target` >= 2 points per cell instead of 2 (same workspace size, queried by the same entries with the same
+ * results): coarser cells for pccx_grid_knn_wide, whose K neighbours span hundreds of the default cells. */
+PCCX_API int pccx_grid_index_build_target(const float *Y, int B, int N, int target, void *workspace, void *stream);
 /* pccx_nn_dist(X, Y) through the index of Y (B,Q,3): d2 (B,P) f32, nn (B,P) int32 or NULL.  query_workspace:
  * pccx_grid_query_workspace_bytes(B, P) bytes of scratch, 16-byte aligned.  Stands in for the KD-tree's 1-NN of eval.py:73-81. */
 PCCX_API int pccx_grid_nn(const float *X, int B, int P, int Q, const void *index, void *query_workspace, float *d2, int32_t *nn,
@@ -138,6 +141,18 @@ PCCX_API int pccx_grid_nn(const float *X, int B, int P, int Q, const void *index
  * (distance, index).  Stands in for search_knn_vector_3d(knn=30) of eval.py:59-60 and knn_points of eval.py:132 at room size. */
 PCCX_API int pccx_grid_knn(const float *q, int B, int M, int N, int K, const void *index, void *query_workspace, float *dists,
                            int64_t *idx, void *stream);
+/* pccx_knn_list(q, ref) through the index of ref (B,N,3) for the wide K of the codec's patch search, 1 <= K <= min(N, 1024)
+ * (KNN_Patching, compress.py:70-74, and the patches of compress.py:105-108): what lets a cloud past pccx_knn's 32768 points be cut into
+ * patches as ONE cloud.  One workgroup per query keeps its candidates in LDS.  dists (B,M,K) f32, idx (B,M,K) int64 and nn (B,M,K,3)
+ * are each optional (at least one); nn holds ref[idx], or (ref[idx] - q) * patch_scale when patch_scale != 0, read from the index's
+ * own copy of the points.  rep: NULL or the (B * M) table of pccx_patch_groups over the queries -- only queries with rep[p] == p are
+ * searched, the rows of the others stay unwritten.  Results are bit for bit those of pccx_knn, ascending by (distance bits, index).
+ * query_workspace: pccx_grid_knn_wide_workspace_bytes(B, N) bytes (N: the points per cloud of the INDEX), 16-byte aligned; host only,
+ * 0 for an empty batch.  K <= 32 is served too (pccx_grid_knn, one wave per query, is the faster kernel there but has no nn and no
+ * rep).  B <= 65535, B * M and B * N < 2^31. */
+PCCX_API size_t pccx_grid_knn_wide_workspace_bytes(int B, int N);
+PCCX_API int pccx_grid_knn_wide(const float *q, int B, int M, int N, int K, const void *index, void *query_workspace, float *dists,
+                                int64_t *idx, float *nn, float patch_scale, const int32_t *rep, void *stream);
 
 /* chamfer_distance's value from the two pccx_nn_dist passes dxy (B,P), dyx (B,Q) (pytorch3d defaults: point and batch mean, both
  * directions summed; AE.py:67): out[0] = batch mean of (mean_p dxy + mean_q dyx), accumulated in double */

@@ -76,5 +76,8 @@ def add_codec_flags(parser):
     parser.add_argument('--octree-mode', choices=['reference', 'full'], default='reference',
                         help="'reference' reproduces octree_np.decode as written (8 bits consumed, S=64); "
                              "'full' is the level-by-level decode.")
+    parser.add_argument('--knn-search', choices=['auto', 'brute', 'grid'], default='auto',
+                        help="Patch search of compress.py: 'brute' = the all-pairs kernels (clouds of up to 32768 points), 'grid' = the "
+                             "exact grid index (any size, same patches), 'auto' = brute up to 32768 points and the grid above.")
     parser.add_argument('--batch', type=int, default=256, help='Clouds per launch sequence.')
     parser.add_argument('--seed', type=int, default=11, help='Seed of the per-file FPS start index.')

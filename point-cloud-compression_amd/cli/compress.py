@@ -27,7 +27,7 @@ def main():
     files = sorted(glob(args.input_glob, recursive=True))
     rank, world = _common.setup_ranks(args)
     ae, prob = _common.load_models(args)
-    cd = codec.Codec(ae, prob, K=args.K, ALPHA=args.ALPHA, N0=args.N0, octree_mode=args.octree_mode)
+    cd = codec.Codec(ae, prob, K=args.K, ALPHA=args.ALPHA, N0=args.N0, octree_mode=args.octree_mode, knn_search=args.knn_search)
     mine = set(dist.shard_indices(len(files), rank, world))                                      # file i -> rank i mod world
     times, todo, bits, points = [], [t for t in enumerate(files) if t[0] in mine], 0, 0
     with torch.no_grad():

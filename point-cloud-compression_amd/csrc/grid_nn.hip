@@ -12,6 +12,8 @@
 // that order, so neighbouring waves read the same cells from cache.  The wave walks the query's cell, then the shell of cells at
 // Chebyshev distance 1, 2, ... around it; the 64 lanes read 64 consecutive points of a run of cells (coalesced: the points lie in
 // cell order) and the best K (distance, index) pairs live one per lane in registers (K <= 32; no LDS, no scratch).
+// Query with a wide K (pccx_grid_knn_wide, K <= 1024: the codec's patches): one WORKGROUP per query and the candidates in LDS -- the
+// comment above grid_wide_kernel at the end of this file.
 //
 // Why the results are exact:
 //   * Same arithmetic.  Every distance is pccx_sqdist(query, point), the operation sequence of nn_dist_kernel and knn_kernel, and
@@ -67,15 +69,14 @@ __host__ __device__ static inline int grid_axis_cells(float e, float emax, int g
 
 // Largest g <= GRID_MAX_AXIS whose grid has at most the budget's cells.  Division and floor are correctly rounded and monotone, so
 // every axis count is non-decreasing in g and the search is well defined; an axis of zero extent gets one cell, a cloud of identical
-// points one cell in all (cell side 1: never used to separate anything).
-__host__ __device__ static inline void grid_dims(long long N, float ex, float ey, float ez, int *G, float *cell)
+// points one cell in all (cell side 1: never used to separate anything).  budget: the cells a cloud may have, >= 1.
+__host__ __device__ static inline void grid_dims_budget(long long budget, float ex, float ey, float ez, int *G, float *cell)
 {
     const float e[3] = {grid_clean_extent(ex), grid_clean_extent(ey), grid_clean_extent(ez)};
     const float emax = fmaxf(fmaxf(e[0], e[1]), e[2]);
     G[0] = G[1] = G[2] = 1;
     *cell = 1.f;
     if (!(emax > 0.f)) return;
-    const long long budget = grid_cell_budget(N);
     int lo = 1, hi = GRID_MAX_AXIS;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -85,6 +86,11 @@ __host__ __device__ static inline void grid_dims(long long N, float ex, float ey
     }
     for (int a = 0; a < 3; ++a) G[a] = grid_axis_cells(e[a], emax, lo);
     *cell = emax / (float)lo;
+}
+
+__host__ __device__ static inline void grid_dims(long long N, float ex, float ey, float ez, int *G, float *cell)
+{
+    grid_dims_budget(grid_cell_budget(N), ex, ey, ez, G, cell);
 }
 
 extern "C" int pccx_grid_dims(int N, float ex, float ey, float ez, int32_t *dims, float *cell)
@@ -196,7 +202,7 @@ __global__ __launch_bounds__(256) void grid_bbox_kernel(const float *__restrict_
     }
 }
 
-__global__ void grid_params_kernel(int *__restrict__ params, int B, int N)
+__global__ void grid_params_kernel(int *__restrict__ params, int B, long long budget)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
@@ -205,7 +211,7 @@ __global__ void grid_params_kernel(int *__restrict__ params, int B, int N)
     for (int a = 0; a < 3; ++a) e[a] = __fsub_rn(grid_ordered_float(w[3 + a]), grid_ordered_float(w[a]));
     int G[3];
     float cell;
-    grid_dims(N, e[0], e[1], e[2], G, &cell);
+    grid_dims_budget(budget, e[0], e[1], e[2], G, &cell);
     w[6] = __float_as_int(cell);
     w[7] = __float_as_int(__fdiv_rn(1.f, cell));
     w[8] = G[0]; w[9] = G[1]; w[10] = G[2];
@@ -288,11 +294,13 @@ static inline unsigned grid_blocks(long long n, long long cap)
     return (unsigned)(b < 1 ? 1 : b);
 }
 
-extern "C" int pccx_grid_index_build(const float *Y, int B, int N, void *workspace, void *stream)
+// budget: the cells per cloud, 1 <= budget <= grid_cell_budget(N) -- the layout (and its key stride S) is always that of the default
+// target, so an index with coarser cells is queried exactly like any other: the grid itself is read from its parameters
+static int grid_build(const char *who, const float *Y, int B, int N, long long budget, void *workspace, void *stream)
 {
-    PCCX_CHECK_ARG(Y && workspace && ((uintptr_t)workspace & 15) == 0, "pccx_grid_index_build: null or misaligned pointer");
-    PCCX_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "pccx_grid_index_build: bad shape B=%d N=%d (1 <= B <= 65535, N >= 1)", B, N);
-    PCCX_CHECK_ARG((long long)B * N < (1ll << 31), "pccx_grid_index_build: B * N = %lld must stay below 2^31", (long long)B * N);
+    PCCX_CHECK_ARG(Y && workspace && ((uintptr_t)workspace & 15) == 0, "%s: null or misaligned pointer", who);
+    PCCX_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1, "%s: bad shape B=%d N=%d (1 <= B <= 65535, N >= 1)", who, B, N);
+    PCCX_CHECK_ARG((long long)B * N < (1ll << 31), "%s: B * N = %lld must stay below 2^31", who, (long long)B * N);
     const GridLayout L = grid_layout(B, N);
     char *ws = (char *)workspace;
     int *params = (int *)(ws + L.params), *cstart = (int *)(ws + L.cstart), *sidx = (int *)(ws + L.sidx);
@@ -302,7 +310,7 @@ extern "C" int pccx_grid_index_build(const float *Y, int B, int N, void *workspa
     const long long total = (long long)B * N;
     hipLaunchKernelGGL(grid_bbox_init_kernel, dim3((B * GRID_PARAM_WORDS + 255) / 256), dim3(256), 0, st, params, B);
     hipLaunchKernelGGL(grid_bbox_kernel, dim3(grid_blocks(N, B > 1 ? 8 : 512), B), dim3(256), 0, st, Y, N, params);
-    hipLaunchKernelGGL(grid_params_kernel, dim3((B + 63) / 64), dim3(64), 0, st, params, B, N);
+    hipLaunchKernelGGL(grid_params_kernel, dim3((B + 63) / 64), dim3(64), 0, st, params, B, budget);
     hipLaunchKernelGGL(grid_keys_kernel, dim3(grid_blocks(N, 2048), B), dim3(256), 0, st, Y, N, (const int *)params, L.S, keys);
     PCCX_CHECK_LAUNCH();
     const int rc = pccx_sort_keys_u64((int64_t *)keys, total, grid_key_bits(B, L.S), (int64_t *)order, ws + L.sort, stream);
@@ -312,6 +320,20 @@ extern "C" int pccx_grid_index_build(const float *Y, int B, int N, void *workspa
     hipLaunchKernelGGL(grid_cell_start_kernel, dim3(grid_blocks(entries, 4096)), dim3(256), 0, st, (const long long *)keys, total, entries, cstart);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
+}
+
+extern "C" int pccx_grid_index_build(const float *Y, int B, int N, void *workspace, void *stream)
+{
+    return grid_build("pccx_grid_index_build", Y, B, N, grid_cell_budget(N), workspace, stream);
+}
+
+// the same index with about `target` points per cell instead of GRID_TARGET: coarser cells for searches with a wide K
+extern "C" int pccx_grid_index_build_target(const float *Y, int B, int N, int target, void *workspace, void *stream)
+{
+    PCCX_CHECK_ARG(target >= GRID_TARGET && N >= 1, "pccx_grid_index_build_target: target=%d points per cell (at least %d: the index's layout), N=%d",
+                   target, GRID_TARGET, N);
+    const long long budget = N / target < 1 ? 1 : N / target, most = grid_cell_budget(N);
+    return grid_build("pccx_grid_index_build_target", Y, B, N, budget < most ? budget : most, workspace, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -372,6 +394,29 @@ __device__ __forceinline__ void grid_scan_run(const float *__restrict__ sxyz, co
     }
 }
 
+// Squared lower bound on the distance from query q (cell c) to any point outside the cube of cells [c - r, c + r]: the nearest face of
+// that cube that still has cells behind it, from the query's true coordinates, shrunk as the file header says.  +inf when no face has.
+// The one statement of the stop rule's bound: both walks (one wave per query, one workgroup per query) end on it.
+__device__ __forceinline__ float grid_face_bound2(const GridParams &g, const float (&q)[3], const int (&c)[3], int r)
+{
+    float bound = INFINITY;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float rel = __fsub_rn(q[a], g.lo[a]);
+        const float slack = GRID_SLACK * (fabsf(rel) + (float)g.G[a] * g.cell);
+        if (c[a] - r > 0) {
+            const float gap = rel - (float)(c[a] - r) * g.cell - slack;
+            bound = gap < bound ? gap : bound;
+        }
+        if (c[a] + r + 1 < g.G[a]) {
+            const float gap = (float)(c[a] + r + 1) * g.cell - rel - slack;
+            bound = gap < bound ? gap : bound;
+        }
+    }
+    bound = bound > 0.f ? bound : 0.f;
+    return bound * bound * 0.9999f;
+}
+
 template <bool KNN>
 __global__ __launch_bounds__(256) void grid_walk_kernel(const float *__restrict__ X, int B, int M, int Q, const int *__restrict__ params,
                                                         const int *__restrict__ cstart, long long S, const float *__restrict__ sxyz,
@@ -412,23 +457,7 @@ __global__ __launch_bounds__(256) void grid_walk_kernel(const float *__restrict_
         // every cell visited?  (integers only: this is what ends the loop when no distance ever does)
         if (c[0] - r <= 0 && c[0] + r >= g.G[0] - 1 && c[1] - r <= 0 && c[1] + r >= g.G[1] - 1 && c[2] - r <= 0 && c[2] + r >= g.G[2] - 1) break;
         if (!KNN) kth = grid_wave_min64(mine);
-        // the nearest face of the visited cube that still has cells behind it, from the query's true coordinates
-        float bound = INFINITY;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float rel = __fsub_rn(q[a], g.lo[a]);
-            const float slack = GRID_SLACK * (fabsf(rel) + (float)g.G[a] * g.cell);
-            if (c[a] - r > 0) {
-                const float gap = rel - (float)(c[a] - r) * g.cell - slack;
-                bound = gap < bound ? gap : bound;
-            }
-            if (c[a] + r + 1 < g.G[a]) {
-                const float gap = (float)(c[a] + r + 1) * g.cell - rel - slack;
-                bound = gap < bound ? gap : bound;
-            }
-        }
-        bound = bound > 0.f ? bound : 0.f;
-        const float bound2 = bound * bound * 0.9999f;
+        const float bound2 = grid_face_bound2(g, q, c, r);
         if (__uint_as_float((unsigned)(kth >> 32)) < bound2) break;       // strict: see "same tie rule" above
     }
     if (KNN) {
@@ -487,4 +516,228 @@ extern "C" int pccx_grid_knn(const float *q, int B, int M, int N, int K, const v
                              void *stream)
 {
     return grid_query("pccx_grid_knn", true, q, B, M, N, index, query_workspace, K, dists, idx, nullptr, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// the wide walk: one workgroup per query, K <= 1024 (the codec's patch search, compress.py:70-74,105-108, on clouds past the 32768
+// points pccx_knn keeps in LDS).  Meant for K > GRID_KMAX; smaller K are served too, for the nn and rep arguments the narrow walk lacks.
+//
+// The K best no longer fit one per lane, so they live in LDS: `buf` collects every scanned point whose key is below a threshold
+// `thr` (~0 until K points are held), and whenever it may fill up a bitonic sort of its entries keeps the K smallest and lowers thr to
+// the K-th.  Nothing below the final K-th key is ever dropped: an entry is refused or cut only when K keys below it are already held.
+// The three points of the argument at the top of this file carry over unchanged: (1) distances are pccx_sqdist; (2) keys are
+// (distance bits, original index) and all distinct, so the K smallest are one well-defined set whatever the visiting order; (3) after
+// every ring the buffer is sorted when it holds K or more, thr IS the K-th best, and the walk ends only when its distance is
+// STRICTLY below grid_face_bound2 -- or when the integer test says that every cell has been visited.
+//
+// All 256 threads walk the same loops (every barrier is reached by all of them):
+//   ring r -> its columns in batches of 128 (two run slots each: a side column's cells z0..z1, or an inner column's bottom and top
+//   cell) -> a block scan of the runs' lengths -> the batch's points 256 at a time, each thread finding its point's run by binary
+//   search in the scanned offsets: every lane has a point however short the runs are.
+// Appending is ballot + mbcnt per wave and one LDS atomic per wave.  `ub`, an upper bound of the count that every thread keeps in a
+// register (+256 per step), says when the exact count has to be read and, if fewer than 256 places are left, the buffer compacted; a
+// full buffer is thus never written to.  Every loop is bounded by integers: rings by rmax, batches by the column count, steps by the
+// batch's point count, the sort by its fixed network.  One cell holding the whole cloud is one long run: N / 256 steps.
+// ------------------------------------------------------------------------------------------
+#define GRID_WIDE_KMAX 1024
+#define GRID_WIDE_CAP 2048                 // keys of LDS per workgroup: 16 KiB, >= K + 256 for every K
+
+extern "C" size_t pccx_grid_knn_wide_workspace_bytes(int B, int N)
+{
+    if (B <= 0 || N <= 0) return 0;
+    return grid_align((size_t)B * (size_t)N * 4);
+}
+
+// inv[cloud * N + original index] = position in the cell-ordered copy (position p belongs to cloud p / N: the keys sort by cloud first)
+__global__ __launch_bounds__(256) void grid_inverse_kernel(const int *__restrict__ sidx, int N, long long total, int *__restrict__ inv)
+{
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long long)gridDim.x * blockDim.x)
+        inv[p / N * N + sidx[p]] = (int)p;
+}
+
+// Ascending bitonic sort of buf[0 .. n) (n a power of two, 2 <= n <= GRID_WIDE_CAP) by the workgroup; ends with a barrier.
+__device__ __forceinline__ void grid_wide_sort(unsigned long long *buf, int n, int tid)
+{
+    for (int size = 2; size <= n; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = tid; t < (n >> 1); t += 256) {
+                const int i = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), l = i | stride;
+                const unsigned long long a = buf[i], b = buf[l];
+                if ((a > b) == ((i & size) == 0)) { buf[i] = b; buf[l] = a; }
+            }
+            __syncthreads();
+        }
+}
+
+// Sort the c entries of buf and keep the K smallest.  Called by all threads with the same c, after a barrier behind the last append.
+// Returns the count kept; thr becomes the K-th key once K are held.
+__device__ __forceinline__ int grid_wide_compact(unsigned long long *buf, int *s_count, int c, int K, int tid, unsigned long long &thr)
+{
+    int n = 2;
+    while (n < c) n <<= 1;                                    // c <= GRID_WIDE_CAP, a power of two
+    for (int t = c + tid; t < n; t += 256) buf[t] = ~0ull;
+    __syncthreads();
+    grid_wide_sort(buf, n, tid);
+    if (c >= K) thr = buf[K - 1];
+    if (c > K && tid == 0) *s_count = K;
+    __syncthreads();                                          // nobody appends before everybody has read thr and the count is set
+    return c > K ? K : c;
+}
+
+__global__ __launch_bounds__(256) void grid_wide_kernel(const float *__restrict__ X, int B, int M, int N, const int *__restrict__ params,
+                                                        const int *__restrict__ cstart, long long S, const float *__restrict__ sxyz,
+                                                        const int *__restrict__ sidx, const int *__restrict__ inv, int K,
+                                                        const int *__restrict__ rep, float *__restrict__ dists, int64_t *__restrict__ idx64,
+                                                        float *__restrict__ nn, float patch_scale)
+{
+    __shared__ unsigned long long buf[GRID_WIDE_CAP];
+    __shared__ int s_off[256], s_p0[256], s_wsum[4], s_count;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const long long qi = blockIdx.x;
+    if (rep && rep[qi] != (int)qi) return;                    // a copy of an earlier query (patch_groups.hip): the whole workgroup leaves
+    const int b = (int)(qi / M);
+    const GridParams g = grid_load_params(params, b);
+    const float q[3] = {X[3 * qi], X[3 * qi + 1], X[3 * qi + 2]};
+    int c[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) c[a] = grid_cell(q[a], g.lo[a], g.inv, g.G[a]);
+    const int *cs = cstart + (size_t)b * S;
+    const int rmax = max(max(g.G[0], g.G[1]), g.G[2]) - 1;
+    const int cap = K <= 256 ? GRID_WIDE_CAP / 2 : GRID_WIDE_CAP;     // small K: compact sooner, sort less
+
+    if (tid == 0) s_count = 0;
+    __syncthreads();
+    unsigned long long thr = ~0ull;
+    int ub = 0;                                               // >= the count, the same in every thread
+    int kept = -1;                                            // the count the last compaction left: while the count equals it, buf is sorted
+    for (int r = 0; r <= rmax; ++r) {
+        const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.G[0] - 1);
+        const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.G[1] - 1);
+        const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.G[2] - 1);
+        const int ny = y1 - y0 + 1, ncol = (x1 - x0 + 1) * ny;
+        for (int n0 = 0; n0 < ncol; n0 += 128) {
+            // ---- this thread's run: slot (tid & 1) of column n0 + (tid >> 1)
+            const int n = n0 + (tid >> 1);
+            int p0 = 0, len = 0;
+            if (n < ncol) {
+                const int ix = x0 + n / ny, iy = y0 + n % ny;
+                const int col = (ix * g.G[1] + iy) * g.G[2];
+                int za = 0, zb = -1;                          // cells za .. zb of the column; none when zb < za
+                if (abs(ix - c[0]) == r || abs(iy - c[1]) == r) {
+                    if ((tid & 1) == 0) { za = z0; zb = z1; } // a column on the shell's side: one contiguous run of the sorted points
+                } else if ((tid & 1) == 0) {                  // inside the shell's outline (r > 0 here): its bottom and its top cell
+                    if (c[2] - r >= 0) za = zb = c[2] - r;
+                } else if (c[2] + r < g.G[2])
+                    za = zb = c[2] + r;
+                if (zb >= za) {
+                    p0 = cs[col + za];
+                    len = cs[col + zb + 1] - p0;
+                    len = len > 0 ? len : 0;
+                }
+            }
+            // ---- exclusive scan of the lengths over the workgroup
+            int incl = len;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int up = __shfl_up(incl, o);
+                if (lane >= o) incl += up;
+            }
+            __syncthreads();                                  // the previous batch's steps have read s_off / s_p0 / s_wsum
+            if (lane == 63) s_wsum[w] = incl;
+            __syncthreads();
+            int before = 0, T = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { before += k < w ? s_wsum[k] : 0; T += s_wsum[k]; }
+            s_off[tid] = before + incl - len;
+            s_p0[tid] = p0;
+            __syncthreads();
+            // ---- the batch's T points, 256 per step
+            for (int base = 0; base < T; base += 256) {
+                if (ub + 256 > cap) {                         // the buffer may lack room for this step: read the count, compact if it does
+                    __syncthreads();
+                    const int cnt = s_count;
+                    __syncthreads();
+                    ub = cnt;
+                    if (cnt + 256 > cap) ub = kept = grid_wide_compact(buf, &s_count, cnt, K, tid, thr);
+                }
+                const int j = base + tid;
+                bool take = false;
+                unsigned long long key = ~0ull;
+                if (j < T) {
+                    int t = 0;                                // the last run starting at or before j: the one that holds point j
+#pragma unroll
+                    for (int s = 128; s > 0; s >>= 1) t += s_off[t + s] <= j ? s : 0;
+                    const size_t p = (size_t)(s_p0[t] + (j - s_off[t]));
+                    const float d = pccx_sqdist(q[0], q[1], q[2], sxyz[3 * p], sxyz[3 * p + 1], sxyz[3 * p + 2]);
+                    key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)sidx[p];
+                    take = key < thr;
+                }
+                const unsigned long long bal = __ballot(take);
+                if (bal) {                                    // wave-uniform
+                    int at = 0;
+                    if (lane == 0) at = atomicAdd(&s_count, __popcll(bal));
+                    at = __shfl(at, 0) + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+                    if (take) buf[at] = key;                  // at < count <= ub + 256 <= cap
+                }
+                ub += 256;
+            }
+        }
+        // every cell visited?  (integers only: this is what ends the loop when no distance ever does)
+        if (c[0] - r <= 0 && c[0] + r >= g.G[0] - 1 && c[1] - r <= 0 && c[1] + r >= g.G[1] - 1 && c[2] - r <= 0 && c[2] + r >= g.G[2] - 1) break;
+        __syncthreads();
+        const int cnt = s_count;
+        __syncthreads();
+        ub = cnt;
+        if (cnt >= K) {
+            if (cnt != kept) ub = kept = grid_wide_compact(buf, &s_count, cnt, K, tid, thr);      // thr = the K-th best of all visited
+            if (__uint_as_float((unsigned)(thr >> 32)) < grid_face_bound2(g, q, c, r)) break;     // strict: see "same tie rule" above
+        }
+    }
+    __syncthreads();
+    const int cnt = s_count;
+    __syncthreads();
+    if (cnt != kept) grid_wide_compact(buf, &s_count, cnt, K, tid, thr);
+    // every cell was visited or K keys lie below the bound: buf[0 .. K) is the answer, ascending (K <= N <= the points visited)
+    for (int k = tid; k < K; k += 256) {
+        const unsigned long long v = buf[k];
+        const int i = (int)(unsigned)v;
+        const size_t o = (size_t)qi * K + k;
+        if (dists) dists[o] = __uint_as_float((unsigned)(v >> 32));
+        if (idx64) idx64[o] = (int64_t)i;
+        if (nn) {
+            const size_t p = (size_t)inv[(size_t)b * N + min(max(i, 0), N - 1)];      // the same floats as ref[b][i]
+            float x = sxyz[3 * p], y = sxyz[3 * p + 1], z = sxyz[3 * p + 2];
+            if (patch_scale != 0.f) {
+                // grouped_xyz -= centre (compress.py:72); x_patches * (N/N0)^(1/3) (compress.py:108)
+                x = __fmul_rn(__fsub_rn(x, q[0]), patch_scale);
+                y = __fmul_rn(__fsub_rn(y, q[1]), patch_scale);
+                z = __fmul_rn(__fsub_rn(z, q[2]), patch_scale);
+            }
+            nn[3 * o] = x; nn[3 * o + 1] = y; nn[3 * o + 2] = z;
+        }
+    }
+}
+
+extern "C" int pccx_grid_knn_wide(const float *q, int B, int M, int N, int K, const void *index, void *query_workspace, float *dists,
+                                  int64_t *idx, float *nn, float patch_scale, const int32_t *rep, void *stream)
+{
+    const char *who = "pccx_grid_knn_wide";
+    PCCX_CHECK_ARG(q && index && query_workspace, "%s: null pointer", who);
+    PCCX_CHECK_ARG(dists || idx || nn, "%s: at least one of dists / idx / nn is needed", who);
+    PCCX_CHECK_ARG((((uintptr_t)index | (uintptr_t)query_workspace) & 15) == 0, "%s: the index and the query workspace must be 16-byte aligned", who);
+    PCCX_CHECK_ARG(B >= 1 && B <= 65535 && M >= 1 && N >= 1, "%s: bad shape B=%d queries=%d N=%d (1 <= B <= 65535, both clouds non-empty)", who, B, M, N);
+    PCCX_CHECK_ARG((long long)B * M < (1ll << 31) && (long long)B * N < (1ll << 31), "%s: B * points must stay below 2^31", who);
+    PCCX_CHECK_ARG(K >= 1 && K <= GRID_WIDE_KMAX && K <= N, "%s: need 1 <= K <= min(N,%d), got K=%d N=%d", who, GRID_WIDE_KMAX, K, N);
+    const GridLayout L = grid_layout(B, N);
+    const char *ws = (const char *)index;
+    const int *params = (const int *)(ws + L.params), *cstart = (const int *)(ws + L.cstart), *sidx = (const int *)(ws + L.sidx);
+    const float *sxyz = (const float *)(ws + L.sxyz);
+    int *inv = (int *)query_workspace;
+    hipStream_t st = (hipStream_t)stream;
+    const long long total = (long long)B * N;
+    if (nn) hipLaunchKernelGGL(grid_inverse_kernel, dim3(grid_blocks(total, 4096)), dim3(256), 0, st, sidx, N, total, inv);
+    hipLaunchKernelGGL(grid_wide_kernel, dim3((unsigned)((long long)B * M)), dim3(256), 0, st, q, B, M, N, params, cstart, L.S, sxyz, sidx,
+                       (const int *)inv, K, (const int *)rep, dists, idx, nn, patch_scale);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
 }

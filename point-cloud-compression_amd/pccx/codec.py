@@ -165,16 +165,23 @@ def stream_sizes(directory, names, threads=0):
     return ss[:len(names)], ps[:len(names)]
 
 
+KNN_BRUTE_MAX_N = 32768        # pccx_knn / pccx_knn_list / pccx_knn_uniq keep a cloud's keys in LDS (csrc/knn.hip)
+OCTREE_MAX_S = 1024            # centres per cloud pccx_octree_encode, pccx_patch_groups and the decoder take
+
+
 class Codec:
     def __init__(self, ae, prob, K=256, ALPHA=2, N0=1024, octree_mode="reference", margin=0.01, matmul=None,
-                 decoder_matmul=None, sa_matmul=None, pn_matmul=None, group_duplicates=True):
+                 decoder_matmul=None, sa_matmul=None, pn_matmul=None, group_duplicates=True, knn_search="auto"):
         """matmul: how the three transforms (SetAbstraction, PointNet, decoder) form their fp32 products --
         "f32" = v_mfma_f32_16x16x4_f32 (bit-for-bit a k-ordered fmaf chain), "bf16x3" = each fp32 operand split exactly into
         three bf16 pieces, six products per pair on the bf16 matrix cores, fp32 accumulate (fp32-level error, 2.6x the
         rate).  None = pccx.DEFAULT_MATMUL.  The per-stage arguments override it.
         group_duplicates: transform each distinct patch of a cloud once and copy the result to its duplicates (ops.patch_groups; in
         octree_mode "reference" a cloud has at most 8 distinct centres among its 64).  Same bytes, same
-        reconstruction either way; False computes every patch."""
+        reconstruction either way; False computes every patch.
+        knn_search: how compress finds the K points of a patch (compress.py:105-108) -- "brute" = the all-pairs kernels, which keep a
+        cloud's keys in LDS and stop at KNN_BRUTE_MAX_N = 32768 points; "grid" = ops.GridIndex.knn_wide, the same patches bit for bit at any
+        size; "auto" = brute wherever it can run and the grid above (the hard limit, not a tuned crossover: DESIGN.md section 4.5)."""
         from . import DEFAULT_MATMUL
         matmul = matmul or DEFAULT_MATMUL
         self.ae, self.prob = ae, prob
@@ -187,6 +194,9 @@ class Codec:
         self.octree_mode = octree_mode
         self.group_duplicates = bool(group_duplicates)
         self.margin = margin
+        if knn_search not in ("auto", "brute", "grid"):
+            raise ValueError(f"knn_search must be 'auto', 'brute' or 'grid', got {knn_search!r}")
+        self.knn_search = knn_search
         if ae.K != K or ae.k != self.k:
             raise ValueError("AE was built for a different K / k")
 
@@ -201,9 +211,13 @@ class Codec:
         from torch.randint, pn_kit.py:321)."""
         B, N, _ = pc.shape
         d, L = self.ae.d, self.ae.L
+        S = int(N * self.ALPHA // self.K)                                            # compress.py:93
+        if S > OCTREE_MAX_S:
+            raise ValueError(f"a cloud of {N} points gives S={S} patches; the octree coder takes at most {OCTREE_MAX_S}, which is "
+                             f"{OCTREE_MAX_S}*K/ALPHA = {OCTREE_MAX_S * self.K // self.ALPHA} points at K={self.K}, ALPHA={self.ALPHA}. "
+                             f"Larger clouds go through pccx.large.compress_large (blocks of points).")
         with stage("normalize"):
             pcn, center, longest = ops.normalize(pc, self.margin)                    # compress.py:90
-        S = int(N * self.ALPHA // self.K)                                            # compress.py:93
         if self.octree_mode == "reference" and S != 64:
             raise ValueError(f"octree_mode='reference' reproduces octree_np.decode's hard-coded S=64 "
                              f"(octree_np.py:100; compress.py:102 asserts); got S={S}. Use octree_mode='full'.")
@@ -224,6 +238,7 @@ class Codec:
         with stage("knn_patches"):
             nn = ops.knn_points(rec, pcn, self.K, patch_scale=scale,                 # compress.py:105-108 (KNN_Patching keeps the
                                 return_dists=False, return_idx=keep_extras,          # patches; the indices only for diagnostics)
+                                search="grid" if self.knn_search == "grid" or (self.knn_search == "auto" and N > KNN_BRUTE_MAX_N) else None,
                                 **({} if keep_extras or groups is None else {"groups": groups} if self._distinct() else {"rep": groups.rep}))
         patches = nn.knn.view(B * S, self.K, 3)
         raw, latent, q = self.ae.encode(patches, sa_matmul=self.sa_matmul, pn_matmul=self.pn_matmul, groups=groups)                      # compress.py:113-127

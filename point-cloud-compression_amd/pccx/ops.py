@@ -165,12 +165,16 @@ def replicate_rows(groups, *arrays):
         _lib.call("pccx_replicate_rows", groups.rep.data_ptr(), P, arrays[0].numel() // max(P, 1), *ptrs, _stream())
 
 
-def knn_points(p1, p2, K, return_nn=True, patch_scale=0.0, return_dists=True, return_idx=True, rep=None, groups=None):
+def knn_points(p1, p2, K, return_nn=True, patch_scale=0.0, return_dists=True, return_idx=True, rep=None, groups=None, search=None, index=None):
     """pytorch3d.ops.knn_points (compress.py:71, pn_kit.py:190).  With patch_scale != 0 the third
     field holds (nn - p1) * patch_scale, i.e. compress.py:72 and :108 fused.  return_dists / return_idx = False leave that field None
     and its bytes unwritten (KNN_Patching, compress.py:70-74, keeps the gathered points only).
     rep: Groups.rep over the (B, M) queries -- only the representatives are searched, the rows of the other queries stay unwritten.
-    groups: the Groups themselves -- the same, with the workgroups walking groups.uniq instead of one being launched per query."""
+    groups: the Groups themselves -- the same, with the workgroups walking groups.uniq instead of one being launched per query.
+    search="grid": the same results through a GridIndex of p2 (``index``: one the caller already built over p2), which has no limit
+    on p2's size where the all-pairs kernels stop at 32768 points; groups= then counts as its rep table."""
+    if _search(search, "knn_points"):
+        return _knn_points_grid(p1, p2, int(K), return_nn, patch_scale, return_dists, return_idx, rep, groups, index)
     p1, p2 = _f32c(p1, "knn_points.p1"), _f32c(p2, "knn_points.p2")
     B, M, _ = p1.shape
     N = p2.shape[1]
@@ -215,6 +219,9 @@ def ball_query(p1, p2, K, radius, method="auto", extent=1.0):
     return KNN(dists, idx, None)
 
 
+GRID_WIDE_TARGET = None      # points per cell of the index knn_points(search="grid") builds for knn_wide; None = the library's 2
+
+
 def _search(search, who):
     """search=None / "brute": the all-pairs kernels; "grid": through a GridIndex.  Anything else is an error."""
     if search is None or search == "brute":
@@ -225,12 +232,13 @@ def _search(search, who):
 
 
 class GridIndex:
-    """Exact grid index over the reference clouds y (B,Q,3) (csrc/grid_nn.hip): built once, queried any number of times.  .nn and
-    .knn return what nn_dist and knn_points return for the same clouds, bit for bit (same fp32 distances, ties to the lower index);
+    """Exact grid index over the reference clouds y (B,Q,3) (csrc/grid_nn.hip): built once, queried any number of times.  .nn,
+    .knn and .knn_wide return what nn_dist and knn_points return for the same clouds, bit for bit (same fp32 distances, ties to the lower index);
     they stand in for open3d's KDTreeFlann.search_knn_vector_3d (eval.py:55-81) at sizes where the all-pairs scans cost P * Q pairs.
     The index keeps its own copy of the points in cell order, so y need not stay alive."""
 
-    def __init__(self, y):
+    def __init__(self, y, target=None):
+        """target: points per cell aimed at (>= 2); None = the library's 2, chosen for K <= 32 (pccx_grid_index_build_target)."""
         y = _f32c(y, "GridIndex.y")
         if y.dim() != 3 or y.shape[2] != 3:
             raise _lib.PccxError(f"GridIndex: expected (B,Q,3), got {tuple(y.shape)}")
@@ -238,12 +246,17 @@ class GridIndex:
         self.device = y.device
         self.ws = torch.empty(max(int(_lib.load().pccx_grid_index_workspace_bytes(self.B, self.Q)), 16), device=y.device, dtype=torch.uint8)
         with stage("grid_index"):
-            _lib.call("pccx_grid_index_build", y.data_ptr(), self.B, self.Q, self.ws.data_ptr(), _stream())
+            if target is None:
+                _lib.call("pccx_grid_index_build", y.data_ptr(), self.B, self.Q, self.ws.data_ptr(), _stream())
+            else:
+                _lib.call("pccx_grid_index_build_target", y.data_ptr(), self.B, self.Q, int(target), self.ws.data_ptr(), _stream())
 
-    def _queries(self, x, who):
+    def _queries(self, x, who, workspace=True):
         x = _f32c(x, who)
         if x.dim() != 3 or x.shape[2] != 3 or x.shape[0] != self.B or x.device != self.device:
             raise _lib.PccxError(f"{who}: expected ({self.B},P,3) on {self.device}, got {tuple(x.shape)} on {x.device}")
+        if not workspace:
+            return x, None
         qws = torch.empty(max(int(_lib.load().pccx_grid_query_workspace_bytes(self.B, int(x.shape[1]))), 16), device=x.device, dtype=torch.uint8)
         return x, qws
 
@@ -268,6 +281,44 @@ class GridIndex:
             _lib.call("pccx_grid_knn", x.data_ptr(), self.B, M, self.Q, int(K), self.ws.data_ptr(), qws.data_ptr(), dists.data_ptr(),
                       idx.data_ptr(), _stream())
         return KNN(dists, idx, None)
+
+    def knn_wide(self, x, K, return_nn=False, patch_scale=0.0, return_dists=True, return_idx=True, rep=None):
+        """knn_points(x, y, K, ...) through the index for K <= min(Q, 1024), the codec's patch search (compress.py:70-74,105-108; K <= 32
+        is served too, where .knn is the faster kernel but returns neither the points nor takes rep):
+        KNN(dists, idx, knn), each field None unless asked for; with patch_scale != 0 knn holds (y[idx] - x) * patch_scale.  rep:
+        Groups.rep over the (B, M) queries -- only the representatives are searched, the rows of the others stay unwritten."""
+        x, _ = self._queries(x, "GridIndex.knn_wide", workspace=False)
+        M, K = int(x.shape[1]), int(K)
+        if rep is not None and (rep.dtype != torch.int32 or rep.numel() != self.B * M or not rep.is_cuda or not rep.is_contiguous()):
+            raise _lib.PccxError("GridIndex.knn_wide: rep must be the dense int32 (B*M) table of patch_groups over the queries")
+        if not (return_dists or return_idx or return_nn):
+            raise _lib.PccxError("GridIndex.knn_wide: at least one of dists / idx / nn must be asked for")
+        if not 1 <= K <= min(self.Q, 1024):
+            raise _lib.PccxError(f"GridIndex.knn_wide: need 1 <= K <= min(Q,1024), got K={K} Q={self.Q}")
+        qws = torch.empty(max(int(_lib.load().pccx_grid_knn_wide_workspace_bytes(self.B, self.Q)), 16), device=x.device, dtype=torch.uint8)
+        dists = torch.empty(self.B, M, K, device=x.device, dtype=torch.float32) if return_dists else None
+        idx = torch.empty(self.B, M, K, device=x.device, dtype=torch.int64) if return_idx else None
+        nn = torch.empty(self.B, M, K, 3, device=x.device, dtype=torch.float32) if return_nn else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with stage("grid_knn_wide"):
+            _lib.call("pccx_grid_knn_wide", x.data_ptr(), self.B, M, self.Q, K, self.ws.data_ptr(), qws.data_ptr(), ptr(dists), ptr(idx),
+                      ptr(nn), float(patch_scale), ptr(rep), _stream())
+        return KNN(dists, idx, nn)
+
+
+def _knn_points_grid(p1, p2, K, return_nn, patch_scale, return_dists, return_idx, rep, groups, index):
+    """knn_points(search="grid"): GridIndex.knn where it serves the request (K <= 32, dists and idx only, every query), knn_wide otherwise."""
+    if groups is not None:
+        if rep is not None:
+            raise _lib.PccxError("knn_points: groups must be given without rep")
+        rep = groups.rep
+    narrow = K <= 32 and not return_nn and rep is None
+    if index is None:
+        index = GridIndex(p2, None if narrow else GRID_WIDE_TARGET)
+    if narrow:
+        r = index.knn(p1, K)
+        return KNN(r.dists if return_dists else None, r.idx if return_idx else None, None)
+    return index.knn_wide(p1, K, return_nn=return_nn, patch_scale=patch_scale, return_dists=return_dists, return_idx=return_idx, rep=rep)
 
 
 def nn_dist(x, y, return_idx=False, search=None):
