@@ -202,7 +202,21 @@ PCCX_API int pccx_octree_encode(const float *centres, int B, int S, int N, doubl
  *          consumed; output padded to 64 points);  S_out must be 64.
  * mode 1 = "full": level-by-level decode (the build's extension), descending-Morton order; the
  *          first min(count,S_out) points are written, the rest repeat the last point.
- * bytes: (B,stride) uint8; nbytes: (B) int32; out: (B,S_out,3) f32; count: (B) int32 decoded points. */
+ * bytes: (B,stride) uint8; nbytes: (B) int32; out: (B,S_out,3) f32; count: (B) int32 decoded points.
+ *
+ * Streams nobody encoded.  Every byte string decodes to something defined or is refused; nothing past a row is read or written.
+ * nbytes is clamped to [0, stride] (mode 0 only tells "<= 0" from the rest: it reads byte 0 alone).
+ * mode 0: nbytes <= 0 gives the single point (0.5,0.5,0.5), count 1.  Otherwise the eight bits of byte 0, MSB first, are the children
+ *   111..000 of the root: count = popcount(byte 0) points in {0.25,0.75}^3, padded to 64 with the last one, all zeros when count = 0.
+ *   This is octree_np.decode of byte_array_to_binary_array(bytes) for all 256 values of byte 0, whatever follows it.
+ * mode 1: the stream is the 8*(nbytes-1) + 1 bits the encoder packs: nbytes-1 whole bytes MSB first, then ONE bit, the lowest bit of
+ *   the last byte (pn_kit.py:465-466 right-aligns a final partial group; the other seven bits of that byte are not read, so a stream
+ *   cut at a byte boundary reads its last byte as that one bit).  Bit 0 is the root; level l+1 is the next 8*popcount(level l) bits
+ *   and is taken only when all of them are inside the stream, so trailing bits that do not fill a level are ignored.  An empty
+ *   stream, a root bit of 0 or an all-zero level give count 0 and out = 0.  Otherwise count = popcount of the last level taken, and
+ *   min(count,S_out) leaves are written followed by copies of the last one; S_out < count writes the first S_out only.
+ *   count = -1 refuses the stream and leaves its out row untouched: a level of more than 2048 occupied cells, or a whole level
+ *   present below level 16 (the encoder never writes either: S <= 1024 and DEPTH <= 16).  A deeper stream is NOT cut at level 16. */
 PCCX_API int pccx_octree_decode(const uint8_t *bytes, int stride, const int32_t *nbytes, int B,
                                 int mode, int S_out, float *out, int32_t *count, void *stream);
 
@@ -408,7 +422,21 @@ PCCX_API int pccx_prob_forward_distinct(const float *centres, int B, int S, int 
 /* torchac.encode_float_cdf (compress.py:134-136) / decode_float_cdf (decompress.py:92-93) on the
  * integer CDFs of pccx_prob_forward.  One independent stream per cloud of nsym = S*d symbols.
  * latent_q: (B,nsym) f32 integer-valued in [-(L/2), L/2]; out: (B,cap) bytes; nbytes: (B) int32
- * (negative = capacity exceeded, |value| bytes were needed). */
+ * (negative = capacity exceeded, |value| bytes were needed).
+ *
+ * cdf_int rows hold L+1 entries, entry 0 = 0, entry L standing for 2^16 whatever it stores; the coder is defined for rows that give
+ * every one of the L symbols a width of at least 1 (entry l+1 > entry l, entry L-1 < 2^16).
+ * Encode: the symbol is (int)latent_q + L/2 clamped to [0, L-1].  Row b of out receives the first min(|nbytes[b]|, cap) bytes of the
+ *   stream and nothing else: bytes from there to the end of the row keep what they held, and on overflow the cap bytes written are
+ *   the prefix of the full stream.
+ * Decode: nbytes[b] is clamped to [0, stride], and bits past the stream read as zero, as torchac reads them.  Any byte string
+ *   therefore decodes, a truncated or empty one included, to nsym symbols in [0, L-1]: low <= value <= high holds after every
+ *   symbol, so no stream is refused and none is "corrupt" to this layer.  Symbol for symbol the result is what the bit-at-a-time
+ *   coder gives on the same bytes, and encoding it again yields a stream that decodes to the same symbols.
+ * Each direction has two kernels with identical results, chosen by pccx_range_coder_form (0 = one wave per cloud, staged in LDS;
+ * 1 = one lane per cloud from global memory): encode takes 0 while nsym*8 + round4(cap) <= 60 KiB, decode while
+ * round4(nsym*(L+1)*2) + round4(stride) + nsym <= 60 KiB and 2 <= L <= 63.  The query takes cap for decode = 0, stride otherwise. */
+PCCX_API int pccx_range_coder_form(int decode, int nsym, int L, int cap_or_stride);
 PCCX_API int pccx_range_encode(const int32_t *cdf_int, const float *latent_q, int B, int nsym, int L,
                                uint8_t *out, int cap, int32_t *nbytes, void *stream);
 PCCX_API int pccx_range_decode(const int32_t *cdf_int, const uint8_t *in, int stride,

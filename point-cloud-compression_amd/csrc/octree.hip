@@ -252,6 +252,8 @@ __global__ __launch_bounds__(256) void octree_decode_full_kernel(const uint8_t *
         __syncthreads();
         parents = base; pos += n; cur ^= 1; ++depth;
     }
+    // a stream that holds one more whole level below OCT_MAX_DEPTH is refused, not cut (block-uniform: parents, pos, depth are)
+    if (depth == OCT_MAX_DEPTH && parents > 0 && pos + 8 * parents <= nbits) bad = 1;
     if (bad) {
         if (tid == 0 && count) count[b] = -1;
         return;

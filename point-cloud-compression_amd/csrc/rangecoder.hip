@@ -340,14 +340,31 @@ __global__ __launch_bounds__(64) void range_decode_wave_kernel(const int32_t *__
     for (int i = lane; i < nsym; i += 64) latent_q[(size_t)b * nsym + i] = (float)((int)ssym[i] - sym_offset);
 }
 
+// LDS images of the two wave kernels: (c_low, c_high) per symbol + the output words; the 16-bit tables + the stream words +
+// one byte per decoded symbol.
+static size_t rc_encode_lds(int nsym, int cap) { return (size_t)nsym * 8 + (size_t)((cap + 3) / 4) * 4; }
+static size_t rc_decode_lds(int nsym, int L, int stride)
+{
+    return (((size_t)nsym * (L + 1) * 2 + 3) & ~(size_t)3) + (size_t)((stride + 3) / 4) * 4 + (size_t)nsym;
+}
+
+// The one statement of which kernel a call runs: 0 = one wave per cloud (its LDS image fits RC_MAX_LDS_BYTES; the wave decoder also
+// needs the L+1 table entries of a symbol on the 64 lanes and a search mask of at least one bit, 2 <= L <= 63), 1 = one lane per cloud.
+extern "C" int pccx_range_coder_form(int decode, int nsym, int L, int cap_or_stride)
+{
+    if (nsym < 0 || L < 1 || cap_or_stride < 0) return 1;
+    if (decode) return rc_decode_lds(nsym, L, cap_or_stride) <= RC_MAX_LDS_BYTES && L >= 2 && L + 1 <= 64 ? 0 : 1;
+    return rc_encode_lds(nsym, cap_or_stride) <= RC_MAX_LDS_BYTES ? 0 : 1;
+}
+
 extern "C" int pccx_range_encode(const int32_t *cdf_int, const float *latent_q, int B, int nsym, int L, uint8_t *out, int cap,
                                  int32_t *nbytes, void *stream)
 {
     if (B == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
     PCCX_CHECK_ARG(cdf_int && latent_q && out && nbytes, "pccx_range_encode: null pointer");
     PCCX_CHECK_ARG(B >= 0 && nsym >= 0 && L >= 1 && cap >= 8, "pccx_range_encode: bad shape");
-    const size_t lds = (size_t)nsym * 8 + (size_t)((cap + 3) / 4) * 4;
-    if (lds <= RC_MAX_LDS_BYTES) {
+    const size_t lds = rc_encode_lds(nsym, cap);
+    if (pccx_range_coder_form(0, nsym, L, cap) == 0) {
         hipLaunchKernelGGL(range_encode_wave_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, cdf_int, latent_q, nsym, L + 1,
                            L / 2, out, cap, nbytes);
         PCCX_CHECK_LAUNCH();
@@ -365,8 +382,8 @@ extern "C" int pccx_range_decode(const int32_t *cdf_int, const uint8_t *in, int 
     if (B == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
     PCCX_CHECK_ARG(cdf_int && in && nbytes && latent_q, "pccx_range_decode: null pointer");
     PCCX_CHECK_ARG(B >= 0 && nsym >= 0 && L >= 1 && stride >= 1, "pccx_range_decode: bad shape");
-    const size_t lds = (((size_t)nsym * (L + 1) * 2 + 3) & ~(size_t)3) + (size_t)((stride + 3) / 4) * 4 + (size_t)nsym;
-    if (lds <= RC_MAX_LDS_BYTES && L >= 2 && L + 1 <= 64) {
+    const size_t lds = rc_decode_lds(nsym, L, stride);
+    if (pccx_range_coder_form(1, nsym, L, stride) == 0) {
         hipLaunchKernelGGL(range_decode_wave_kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, cdf_int, in, stride, nbytes, nsym,
                            L + 1, L / 2, latent_q);
         PCCX_CHECK_LAUNCH();

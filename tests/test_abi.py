@@ -42,6 +42,7 @@ def test_derived_signatures():
     assert sig["pccx_sort_keys_workspace_bytes"] == (C.c_size_t, [i64])
     assert sig["pccx_normalize"] == (i, [P, i, i, dbl, P, P, P, P])
     assert sig["pccx_write_streams_host"] == (i, [P, i, i, i, s, s, P, i])
+    assert sig["pccx_range_coder_form"] == (i, [i, i, i, i])
     assert sig["pccx_replicate_rows"] == (i, [P, i64, i, P, P, P, P])
     assert sig["pccx_ae_decode_h2_list"] == (i, [P, i, i, i, P, P, P, P, f, P, P, P, i, dbl, P, P, P, P])
     assert _lib.parse_header("/* PCCX_API int pccx_a(int); */\nPCCX_API size_t pccx_b(void); // PCCX_API int pccx_c(int);\n") == {
@@ -65,6 +66,26 @@ def test_version_and_error_string():
     # argument validation happens on the host, before any HIP call
     rc = lib.pccx_octree_encode(None, 1, 64, 8192, 0.25, None, None, None, None, None, None)
     assert rc == -1 and b"null pointer" in lib.pccx_last_error()
+
+
+def test_range_coder_form_query_states_the_lds_budget():
+    """pccx_range_coder_form is host arithmetic (no GPU): 0 = one wave per cloud while the kernel's LDS image fits 60 KiB -- encode
+    nsym*8 + round4(cap), decode round4(nsym*(L+1)*2) + round4(stride) + nsym and 2 <= L <= 63 -- else 1 = one lane per cloud."""
+    form = _lib.load().pccx_range_coder_form
+    r4 = lambda v: (v + 3) // 4 * 4
+    for nsym in (0, 1, 77, 1024, 4352, 6000, 7679, 7680, 16384):
+        for cap in (8, 9, 2 * nsym + 16, 61440 - 8 * nsym - 4, 61440 - 8 * nsym - 3, 61440 - 8 * nsym, 61440 - 8 * nsym + 1, 61440):
+            if cap >= 0:
+                assert form(0, nsym, 7, cap) == (0 if nsym * 8 + r4(cap) <= 61440 else 1), (nsym, cap)
+        for L in (1, 2, 7, 63, 64, 200):
+            fixed = r4(nsym * (L + 1) * 2) + nsym
+            for stride in (1, 5, 61440 - fixed - 3, 61440 - fixed, 61440 - fixed + 1, 61440):
+                if stride >= 0:
+                    assert form(1, nsym, L, stride) == (0 if fixed + r4(stride) <= 61440 and 2 <= L <= 63 else 1), (nsym, L, stride)
+    # the shapes the codec runs: 64 patches of d = 16 take the wave kernels, the whole-cloud codec's 1024 patches the one-lane ones
+    assert form(0, 1024, 7, 2 * 1024 + 16) == 0 and form(1, 1024, 7, 2 * 1024 + 16) == 0
+    assert form(0, 16384, 7, 2 * 16384 + 16) == 1 and form(1, 16384, 7, 2 * 16384 + 16) == 1
+    assert form(0, 383 * 16, 7, 2 * 383 * 16 + 16) == 0 and form(0, 384 * 16, 7, 2 * 384 * 16 + 16) == 1
 
 
 def test_model_limits_name_the_reference_flags():
