@@ -57,6 +57,18 @@ PCCX_API int pccx_denormalize(const float *pc, int B, int N, double margin, cons
 PCCX_API int pccx_fps(const float *xyz, int B, int N, int npoint, const int32_t *start_idx,
                       int64_t *idx_out, float *workspace, void *stream);
 
+/* The same indices, bit for bit, with every cloud shared by G workgroups of 1024 threads (one cooperative launch of B * G
+ * workgroups; each keeps its share of the cloud and of the running minima in registers, the winners of a round meet in `workspace`
+ * through agent-scope atomics and a bounded grid barrier over the cloud's G workgroups).  ceil(N / 16384) <= G <= 64, so
+ * N <= 1048576, and B * G must not exceed the device's compute-unit count (all workgroups have to be resident): PCCX_ERR_ARG
+ * otherwise, before anything is launched.  workspace: pccx_fps_coop_workspace_bytes(B, npoint) bytes on the device, cleared by the
+ * entry itself; per cloud (npoint + 2) 64-bit words, word 1 of them the STATUS word: non-zero after the launch when a barrier wait
+ * ran out of its bound (about a second) and the cloud's workgroups gave up -- idx_out of that cloud is then incomplete.  Not for
+ * stream capture (the caller reads the status words). */
+PCCX_API size_t pccx_fps_coop_workspace_bytes(int B, int npoint);
+PCCX_API int pccx_fps_coop(const float *xyz, int B, int N, int npoint, const int32_t *start_idx, int64_t *idx_out, int G,
+                           void *workspace, void *stream);
+
 /* 63-bit Morton keys over the bounding box [lo, lo+extent]^3 (lo_host: 3 floats on the HOST), used to
  * cut clouds larger than one block into spatially compact 8192-point blocks (BASELINE configs[3]).
  * xyz: (n,3) f32; keys: (n) int64. */
@@ -195,6 +207,11 @@ PCCX_API int pccx_octree_bits_capacity(int S);
 PCCX_API int pccx_octree_encode(const float *centres, int B, int S, int N, double min_bpp,
                                 uint8_t *bits, int32_t *nbits, int32_t *depth, uint8_t *bytes,
                                 int32_t *nbytes, void *stream);
+/* The same outputs, bit for bit, for 1 <= S <= 8192 centres: 1024 threads with up to 8 sorted keys each (the sort runs over up to
+ * 8192 keys in 64 KB of LDS).  pccx_octree_encode keeps its own kernel and its limit. */
+PCCX_API int pccx_octree_encode_wide(const float *centres, int B, int S, int N, double min_bpp,
+                                     uint8_t *bits, int32_t *nbits, int32_t *depth, uint8_t *bytes,
+                                     int32_t *nbytes, void *stream);
 
 /* pn_kit.decode_sampled_np -> octree_np.decode (octree_np.py:47-112) from the packed stream
  * (decompress.py:80-83 unpacks with pn_kit.byte_array_to_binary_array first).
@@ -216,7 +233,10 @@ PCCX_API int pccx_octree_encode(const float *centres, int B, int S, int N, doubl
  *   stream, a root bit of 0 or an all-zero level give count 0 and out = 0.  Otherwise count = popcount of the last level taken, and
  *   min(count,S_out) leaves are written followed by copies of the last one; S_out < count writes the first S_out only.
  *   count = -1 refuses the stream and leaves its out row untouched: a level of more than 2048 occupied cells, or a whole level
- *   present below level 16 (the encoder never writes either: S <= 1024 and DEPTH <= 16).  A deeper stream is NOT cut at level 16. */
+ *   present below level 16 (the encoder never writes either: S <= 1024 and DEPTH <= 16).  A deeper stream is NOT cut at level 16.
+ *   With S_out > 1024 the wide kernel decodes (1024 threads, 8192 codes per level in 128 KB of LDS): the same rules with the refusal
+ *   at a level of more than 8192 occupied cells, for the streams of pccx_octree_encode_wide.
+ * mode 2 = mode 1 through the wide kernel whatever S_out (the same points and counts wherever mode 1's kernel accepts the stream). */
 PCCX_API int pccx_octree_decode(const uint8_t *bytes, int stride, const int32_t *nbytes, int B,
                                 int mode, int S_out, float *out, int32_t *count, void *stream);
 
@@ -382,6 +402,10 @@ PCCX_API int pccx_ae_decode_h2(const float *latent_q, int P, int d, int k, const
 PCCX_API size_t pccx_patch_groups_workspace_ints(int B);
 PCCX_API int pccx_patch_groups(const float *keys_a, int floats_a, const float *keys_b, int floats_b, int B, int S, int32_t *rep,
                                int32_t *uniq, int32_t *n_uniq, int32_t *workspace, void *stream);
+/* The same tables for 1 <= S <= 8192 patches per cloud: an open-addressing table in LDS in place of the all-earlier-rows compare
+ * (csrc/patch_groups.hip).  Same arguments and workspace. */
+PCCX_API int pccx_patch_groups_wide(const float *keys_a, int floats_a, const float *keys_b, int floats_b, int B, int S, int32_t *rep,
+                                    int32_t *uniq, int32_t *n_uniq, int32_t *workspace, void *stream);
 PCCX_API int pccx_replicate_rows(const int32_t *rep, int64_t P, int row_floats, float *a0, float *a1, float *a2, void *stream);
 /* pccx_knn for the queries with rep[b*M + m] == b*M + m only (rep over the (B, M) queries; NULL = all). */
 PCCX_API int pccx_knn_list(const float *q, int B, int M, const float *ref, int N, int K, float *dists, int64_t *idx, float *nn,

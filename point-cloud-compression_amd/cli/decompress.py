@@ -33,7 +33,7 @@ def main():
     rank, world = _common.setup_ranks(args)
     names = [names[i] for i in dist.shard_indices(len(names), rank, world)]                      # file i -> rank i mod world
     ae, prob = _common.load_models(args)
-    cd = codec.Codec(ae, prob, K=args.K, ALPHA=args.ALPHA, N0=args.N0, octree_mode=args.octree_mode)
+    cd = codec.Codec(ae, prob, K=args.K, ALPHA=args.ALPHA, N0=args.N0, octree_mode=args.octree_mode, max_centres=codec.OCTREE_WIDE_MAX_S)
     times = []
     with torch.no_grad():
         for b0 in range(0, len(names), args.batch):
@@ -45,7 +45,7 @@ def main():
             up = codec.Compressed.read_files(args.compressed_path, chunk, device=args.device)
             s_b, s_n, p_b, p_n, c = up.s_bytes, up.s_nbytes, up.p_bytes, up.p_nbytes, up.c
             # number of centres each stream holds (decompress.py:85 takes S from the decoded array)
-            _, count = ops.octree_decode(s_b, s_n, args.octree_mode, 64 if args.octree_mode == 'reference' else 1)
+            _, count = ops.octree_decode(s_b, s_n, args.octree_mode, 64 if args.octree_mode == 'reference' else 1, wide=args.octree_mode == 'full')   # up to 8192 centres
             count = count.cpu().numpy()
             if (count < 0).any():
                 raise PccxError("corrupt .s.bin stream(s): " + ", ".join(n for n, k_ in zip(chunk, count) if k_ < 0))

@@ -444,6 +444,160 @@ extern "C" int pccx_fps(const float *xyz, int B, int N, int npoint, const int32_
 }
 
 // ------------------------------------------------------------------------------------------
+// pccx_fps_coop: ONE cloud's farthest point sampling on G workgroups (a cooperative launch of B * G workgroups of 1024 threads).
+//
+// Workgroup g of a cloud owns the 1024-point rows g, g + G, g + 2G, ... (point i = tid + 1024 * row), PPT rows per thread in registers
+// with their running minima, the arithmetic of fps_kernel to the operation.  A round: every workgroup reduces its own winner to one
+// 64-bit argmax_key (DPP, then 16 wave keys through LDS), lane 0 merges it into the round's word of the workspace by an agent-scope
+// atomic max and then -- only after the max has RETURNED -- adds 1 to the cloud's arrival counter.  The counter is monotonic (never
+// reset inside the launch): round s is complete at G * (s + 1).  Lane 0 polls it (relaxed agent-scope loads, s_sleep between them),
+// reads the round's word by an agent-scope load, hands it to its workgroup through LDS behind a workgroup barrier, and every thread
+// reads the winner's coordinates from xyz, which nobody writes during the launch.
+//
+// Exactness: keys of distinct points are distinct (the index is part of the key), max is associative and commutative, and the key
+// order is torch.max's rule (larger distance, then lower index), so the merged winner is the one fps_kernel picks whatever G, the
+// partition or the arrival order: the indices are bit-identical to pccx_fps.
+//
+// Every spin is bounded.  A poll that outlasts FPS_COOP_SPIN_BOUND sets the cloud's status word; the pollers of that cloud look at
+// the word while they wait, every workgroup reads it after the barrier, and all of them leave the round loop.  The caller reads the
+// word after the launch.  Workspace per cloud, 64-bit words: [0] arrival counter, [1] status, [2 + s] the key of round s; the entry
+// clears it with a kernel ahead of the launch.
+// ------------------------------------------------------------------------------------------
+#define FPS_COOP_MAX_G 64
+#define FPS_COOP_SPIN_BOUND (1u << 20)     // polls of >= 1 us each (an L2 round trip and an s_sleep): of the order of a second
+
+template <int PPT>
+__global__ __launch_bounds__(1024) void fps_coop_kernel(const float *__restrict__ xyz, int N, int npoint,
+                                                        const int32_t *__restrict__ start, int64_t *__restrict__ out, int G,
+                                                        unsigned long long *ws)
+{
+    __shared__ unsigned long long part_k[16];                 // wave winners (argmax_key)
+    __shared__ unsigned long long s_win[2];                   // the round's global winner, the cloud's status word
+    const int b = blockIdx.x / G, g = blockIdx.x - b * G, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const float *p = xyz + (size_t)b * N * 3;
+    unsigned long long *cw = ws + (size_t)b * ((size_t)npoint + 2);
+    unsigned *counter = (unsigned *)cw, *status = (unsigned *)(cw + 1);
+    unsigned long long *slots = cw + 2;
+
+    constexpr int PP = PPT / 2;
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    f32x2 px[PP], py[PP], pz[PP], md[PP];
+#pragma unroll
+    for (int j = 0; j < PP; ++j)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const long long i = tid + 1024ll * (g + (long long)G * (2 * j + e));
+            if (i < N) {
+                px[j][e] = p[3 * i]; py[j][e] = p[3 * i + 1]; pz[j][e] = p[3 * i + 2];
+                md[j][e] = 1e10f;              // distance = ones * 1e10 (:320)
+            } else {
+                px[j][e] = py[j][e] = pz[j][e] = 0.f;
+                md[j][e] = -INFINITY;          // never selected
+            }
+        }
+
+    int far = start ? start[b] : 0;
+    if (far < 0 || far >= N) far = 0;
+    for (int s = 0; s < npoint; ++s) {
+        if (g == 0 && tid == 0) out[(size_t)b * npoint + s] = far;   // centroids[:, i] = farthest (:324)
+        if (s + 1 == npoint) break;                                   // the last centroid needs no successor
+        const float cx = p[3 * (size_t)far], cy = p[3 * (size_t)far + 1], cz = p[3 * (size_t)far + 2];
+        float best = -INFINITY;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int j = 0; j < PP; ++j) {
+            const f32x2 dx = px[j] - cx, dy = py[j] - cy, dz = pz[j] - cz;   // (:326): (x - c)^2 summed x, y, z
+            f32x2 d = dx * dx;
+            d = d + dy * dy;
+            d = d + dz * dz;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                md[j][e] = fminf(md[j][e], d[e]);                             // (:327-328)
+                const bool up = md[j][e] > best;                              // ascending index, strict '>'
+                best = up ? md[j][e] : best;
+                bi = up ? tid + 1024 * (g + G * (2 * j + e)) : bi;
+            }
+        }
+        const unsigned long long wk = wave_argmax_key(argmax_key(best, bi));
+        if (lane == 0) part_k[w] = wk;
+        __syncthreads();
+        if (w == 0) {
+            const unsigned long long vk = row16_argmax_key(part_k[lane & 15]);   // this workgroup's winner, in every lane
+            if (lane == 0) {
+                const unsigned long long old = __hip_atomic_fetch_max(slots + s, vk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                asm volatile("s_waitcnt vmcnt(0)" ::"v"(old) : "memory");        // the max has returned: only now the arrival
+                __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const unsigned target = (unsigned)G * (unsigned)(s + 1);
+                unsigned st = 0u;
+                for (unsigned spins = 0;; ++spins) {
+                    if (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= target) break;
+                    if ((spins & 31u) == 31u) st = __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (spins >= FPS_COOP_SPIN_BOUND) {
+                        __hip_atomic_fetch_or(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        st = 1u;
+                    }
+                    if (st) break;
+                    __builtin_amdgcn_s_sleep(2);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // no instruction: keeps the loads below behind the poll
+                if (!st) st = __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                s_win[0] = __hip_atomic_load(slots + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                s_win[1] = st;
+            }
+        }
+        __syncthreads();
+        if (s_win[1]) break;                                          // the same word in every thread of the workgroup
+        far = __builtin_amdgcn_readfirstlane(argmax_key_index(s_win[0]));
+        if (far < 0 || far >= N) far = 0;                             // cannot happen with a cleared workspace; never index out of the cloud
+    }
+}
+
+template <int PPT>
+static int launch_fps_coop(const float *xyz, int B, int N, int npoint, const int32_t *start, int64_t *out, int G,
+                           unsigned long long *ws, hipStream_t st)
+{
+    void *args[] = {(void *)&xyz, (void *)&N, (void *)&npoint, (void *)&start, (void *)&out, (void *)&G, (void *)&ws};
+    PCCX_CHECK_HIP(hipLaunchCooperativeKernel((const void *)fps_coop_kernel<PPT>, dim3((unsigned)(B * G)), dim3(1024), args, 0, st));
+    return PCCX_OK;
+}
+
+extern "C" size_t pccx_fps_coop_workspace_bytes(int B, int npoint)
+{
+    if (B <= 0 || npoint < 0) return 0;
+    return ((size_t)B * ((size_t)npoint + 2) * 8 + 15) & ~(size_t)15;
+}
+
+extern "C" int pccx_fps_coop(const float *xyz, int B, int N, int npoint, const int32_t *start_idx, int64_t *idx_out, int G,
+                             void *workspace, void *stream)
+{
+    if (B == 0 || npoint == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
+    PCCX_CHECK_ARG(xyz && idx_out && workspace, "pccx_fps_coop: null pointer");
+    PCCX_CHECK_ARG(B >= 0 && N >= 1 && npoint >= 0, "pccx_fps_coop: bad shape B=%d N=%d npoint=%d", B, N, npoint);
+    const int gmin = (int)(((long long)N + 16383) / 16384);
+    PCCX_CHECK_ARG(G >= 1 && G <= FPS_COOP_MAX_G && G >= gmin,
+                   "pccx_fps_coop: N=%d points need %d <= G <= %d workgroups per cloud (16384 points each at the most), got G=%d", N,
+                   gmin, FPS_COOP_MAX_G, G);
+    int dev = 0, cus = 0, coop = 0;
+    PCCX_CHECK_HIP(hipGetDevice(&dev));
+    PCCX_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    PCCX_CHECK_HIP(hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev));
+    PCCX_CHECK_ARG(coop, "pccx_fps_coop: the device does not support cooperative launches");
+    PCCX_CHECK_ARG((long long)B * G <= cus,
+                   "pccx_fps_coop: B*G = %d*%d workgroups must all be resident, one per compute unit, and the device has %d: split the batch",
+                   B, G, cus);
+    hipStream_t st = (hipStream_t)stream;
+    PCCX_CHECK_HIP(pccx_zero_async(workspace, (size_t)B * ((size_t)npoint + 2) * 8, st));   // exactly the words of these B clouds
+    unsigned long long *ws = (unsigned long long *)workspace;
+    const int ppt = (int)(((long long)N + 1024ll * G - 1) / (1024ll * G));
+    if (ppt <= 2) return launch_fps_coop<2>(xyz, B, N, npoint, start_idx, idx_out, G, ws, st);
+    if (ppt <= 4) return launch_fps_coop<4>(xyz, B, N, npoint, start_idx, idx_out, G, ws, st);
+    if (ppt <= 6) return launch_fps_coop<6>(xyz, B, N, npoint, start_idx, idx_out, G, ws, st);
+    if (ppt <= 8) return launch_fps_coop<8>(xyz, B, N, npoint, start_idx, idx_out, G, ws, st);
+    if (ppt <= 12) return launch_fps_coop<12>(xyz, B, N, npoint, start_idx, idx_out, G, ws, st);
+    return launch_fps_coop<16>(xyz, B, N, npoint, start_idx, idx_out, G, ws, st);
+}
+
+// ------------------------------------------------------------------------------------------
 // Morton keys for block-partitioning large clouds (BASELINE configs[3]: S3DIS rooms chunked into
 // 8192-point blocks so that S = N*ALPHA/K stays 64).  21 bits per axis over the cloud's bounding box.
 // ------------------------------------------------------------------------------------------

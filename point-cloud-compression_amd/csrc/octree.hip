@@ -172,6 +172,182 @@ extern "C" int pccx_octree_encode(const float *centres, int B, int S, int N, dou
 }
 
 // ------------------------------------------------------------------------------------------
+// pccx_octree_encode_wide: the same stream for up to 8192 centres.  1024 threads, E = T / 1024 <= 8 keys per thread (T = the power of two
+// >= S, at least 1024): the bitonic sort runs over T keys in dynamic LDS (64 KB at 8192), after it thread t owns the sorted keys
+// t*E .. t*E + E-1 in registers, and the block scan of the level loop carries E flags per thread (a running count inside the thread, a
+// wave scan of the thread sums, 16 wave totals through LDS).  Same closed form, same outputs as octree_encode_kernel.
+// ------------------------------------------------------------------------------------------
+#define OCT_WIDE_MAX_S 8192
+
+// Exclusive block scan of one count per thread (1024 threads); *total gets the block sum.  Two barriers.  s_w: int[17] scratch.
+__device__ __forceinline__ int block_scan_count(int c, int *s_w, int *total)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int v = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(v, o);
+        if (lane >= o) v += t;
+    }
+    if (lane == 63) s_w[w] = v;
+    __syncthreads();
+    int base = 0, tot = 0;
+    for (int k = 0; k < 16; ++k) {
+        const int x = s_w[k];
+        if (k < w) base += x;
+        tot += x;
+    }
+    __syncthreads();
+    *total = tot;
+    return base + v - c;
+}
+
+template <int E>
+__global__ __launch_bounds__(1024) void octree_encode_wide_kernel(const float *__restrict__ centres, int S, int N, double min_bpp,
+                                                                  uint8_t *__restrict__ bits_all, int cap,
+                                                                  int32_t *__restrict__ nbits_out, int32_t *__restrict__ depth_out,
+                                                                  uint8_t *__restrict__ bytes_all, int bytes_stride,
+                                                                  int32_t *__restrict__ nbytes_out)
+{
+    extern __shared__ unsigned long long keys[];     // [T]
+    __shared__ int s_w[17];
+    constexpr int T = 1024 * E;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    uint8_t *bits = bits_all + (size_t)b * cap;
+
+#pragma unroll 1
+    for (int e = 0; e < E; ++e) {
+        const int i = tid + 1024 * e;
+        unsigned long long k = ~0ull;
+        if (i < S) {
+            const float *p = centres + ((size_t)b * S + i) * 3;
+            k = (spread3(quant16(p[0])) << 2) | (spread3(quant16(p[1])) << 1) | spread3(quant16(p[2]));
+        }
+        keys[i] = k;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int size = 2; size <= T; size <<= 1) {
+#pragma unroll 1
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int q = tid; q < (T >> 1); q += 1024) {
+                const int lo = 2 * q - (q & (stride - 1)), hi = lo + stride;
+                const bool up = ((lo & size) == 0);
+                const unsigned long long a = keys[lo], c = keys[hi];
+                if ((a > c) == up) { keys[lo] = c; keys[hi] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    // This thread's sorted positions: first .. first + E-1.  A key opens a new level-D cell when it differs from its predecessor in the
+    // bits above 3*(16-D), i.e. from the level 16 - msb(key ^ prev) / 3 on: one small integer per key stands for the two 64-bit
+    // compares per level of octree_encode_kernel (lvl_all: among all centres, the uniqueness test; lvl_in: among those inside the unit
+    // cube, the stream; 99 = never).
+    const int first = tid * E;
+    unsigned long long key[E];
+    int lvl_all[E], lvl_in[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) key[e] = keys[first + e];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const unsigned long long prev = e > 0 ? key[e - 1] : (first > 0 ? keys[first - 1] : 0ull);
+        const bool valid = first + e < S;
+        const bool in = valid && (key[e] >> 48) == 0x7000ull;               // all three q in [0, 2^16)
+        const bool prev_in = first + e > 0 && (prev >> 48) == 0x7000ull;
+        const unsigned long long x = key[e] ^ prev;
+        const int lvl = x ? 16 - (63 - __clzll((long long)x)) / 3 : 99;
+        lvl_all[e] = !valid ? 99 : (first + e == 0 ? 0 : lvl);
+        lvl_in[e] = !in ? 99 : (!prev_in ? 0 : lvl);
+    }
+
+    // cells are counted, not stored: a thread keeps the number of level-(D-1) cells opened before its first key (base_prev) and
+    // recounts its own E flags where it needs a key's parent cell
+    int c = 0, total;
+#pragma unroll
+    for (int e = 0; e < E; ++e) c += lvl_in[e] <= 0 ? 1 : 0;           // in && !prev_in
+    int base_prev = block_scan_count(c, s_w, &total);
+    int occ_prev = total;
+    int sum_occ = 0;
+    int accepted = 0, final_bits = 1, final_depth = 17;
+    if (tid == 0) bits[0] = occ_prev ? 1 : 0;                           // root bit
+#pragma unroll 1
+    for (int D = 1; D <= OCT_MAX_DEPTH; ++D) {
+        const int sh = 3 * (16 - D);
+        int occ_all, occ_in;
+        c = 0;
+#pragma unroll
+        for (int e = 0; e < E; ++e) c += D >= lvl_all[e] ? 1 : 0;
+        block_scan_count(c, s_w, &occ_all);
+        c = 0;
+#pragma unroll
+        for (int e = 0; e < E; ++e) c += D >= lvl_in[e] ? 1 : 0;
+        const int base_in = block_scan_count(c, s_w, &occ_in);
+        const int off = 1 + 8 * sum_occ;                 // first bit of level D
+        const int nb = occ_prev ? off + 8 * occ_prev : 1;
+        if (!accepted) {
+            if (occ_prev) {
+                for (int j = tid; j < 8 * occ_prev; j += 1024) bits[off + j] = 0;
+                __syncthreads();
+                int parent = base_prev;                  // level-(D-1) cells opened up to and including this key
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    parent += D - 1 >= lvl_in[e] ? 1 : 0;
+                    if (D >= lvl_in[e]) bits[off + 8 * (occ_prev - parent) + (7 - (int)((key[e] >> sh) & 7ull))] = 1;
+                }
+            }
+            final_bits = nb;
+            if ((double)nb / (double)N > min_bpp && occ_all == S) { accepted = 1; final_depth = D; }
+        }
+        sum_occ += occ_prev;
+        occ_prev = occ_in;
+        base_prev = base_in;
+    }
+    __syncthreads();
+    // pack (pn_kit.py:463-467): MSB-first; a final partial group is right-aligned in its byte.
+    const int nby = (final_bits + 7) >> 3;
+    uint8_t *bytes = bytes_all + (size_t)b * bytes_stride;
+    for (int j = tid; j < nby; j += 1024) {
+        int lo = 8 * j, hi = lo + 8 < final_bits ? lo + 8 : final_bits;
+        unsigned v = 0;
+        for (int t = lo; t < hi; ++t) v = (v << 1) | bits[t];
+        bytes[j] = (uint8_t)v;
+    }
+    if (tid == 0) {
+        nbits_out[b] = final_bits;
+        depth_out[b] = final_depth;
+        nbytes_out[b] = nby;
+    }
+}
+
+template <int E>
+static int launch_octree_encode_wide(const float *centres, int B, int S, int N, double min_bpp, uint8_t *bits, int cap, int32_t *nbits,
+                                     int32_t *depth, uint8_t *bytes, int32_t *nbytes, hipStream_t st)
+{
+    const size_t lds = (size_t)1024 * E * 8;
+    PCCX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&octree_encode_wide_kernel<E>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds));
+    hipLaunchKernelGGL(octree_encode_wide_kernel<E>, dim3(B), dim3(1024), lds, st, centres, S, N, min_bpp, bits, cap, nbits, depth, bytes,
+                       (cap + 7) / 8, nbytes);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+extern "C" int pccx_octree_encode_wide(const float *centres, int B, int S, int N, double min_bpp, uint8_t *bits, int32_t *nbits,
+                                       int32_t *depth, uint8_t *bytes, int32_t *nbytes, void *stream)
+{
+    if (B == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
+    PCCX_CHECK_ARG(centres && bits && nbits && depth && bytes && nbytes, "pccx_octree_encode_wide: null pointer");
+    PCCX_CHECK_ARG(B >= 0 && S >= 1 && S <= OCT_WIDE_MAX_S && N >= 1, "pccx_octree_encode_wide: need 1 <= S <= %d, N >= 1 (S=%d N=%d)",
+                   OCT_WIDE_MAX_S, S, N);
+    const int cap = pccx_octree_bits_capacity(S);
+    hipStream_t st = (hipStream_t)stream;
+    if (S <= 1024) return launch_octree_encode_wide<1>(centres, B, S, N, min_bpp, bits, cap, nbits, depth, bytes, nbytes, st);
+    if (S <= 2048) return launch_octree_encode_wide<2>(centres, B, S, N, min_bpp, bits, cap, nbits, depth, bytes, nbytes, st);
+    if (S <= 4096) return launch_octree_encode_wide<4>(centres, B, S, N, min_bpp, bits, cap, nbits, depth, bytes, nbytes, st);
+    return launch_octree_encode_wide<8>(centres, B, S, N, min_bpp, bits, cap, nbits, depth, bytes, nbytes, st);
+}
+
+// ------------------------------------------------------------------------------------------
 // decode
 // ------------------------------------------------------------------------------------------
 // mode 0: octree_np.decode AS WRITTEN (octree_np.py:47-112).  Line :61 overwrites the stream with
@@ -222,33 +398,33 @@ __device__ __forceinline__ int stream_bit(const uint8_t *bytes, int nb, int pos)
     return (bytes[pos >> 3] >> (7 - (pos & 7))) & 1;
 }
 
-__global__ __launch_bounds__(256) void octree_decode_full_kernel(const uint8_t *__restrict__ bytes_all, int stride,
-                                                                 const int32_t *__restrict__ nbytes, int S_out,
-                                                                 float *__restrict__ out, int32_t *__restrict__ count)
+// One body for both forms: THREADS threads, CAP codes per level in each of the two buffers codes[0 .. CAP) and codes[CAP .. 2 CAP).
+template <int THREADS, int CAP>
+__device__ __forceinline__ void octree_decode_full_body(const uint8_t *__restrict__ bytes_all, int stride, const int32_t *__restrict__ nbytes,
+                                                        int S_out, float *__restrict__ out, int32_t *__restrict__ count,
+                                                        unsigned long long *codes, int *s_w)
 {
-    __shared__ unsigned long long codes[2][OCT_DEC_CAP];
-    __shared__ int s_w[17];
     const int b = blockIdx.x, tid = threadIdx.x;
     const uint8_t *bytes = bytes_all + (size_t)b * stride;
     const int nb = min(max(nbytes[b], 0), stride);     // never read past the row, whatever the caller's count says
     float *o = out + (size_t)b * S_out * 3;
     const int nbits = nb >= 1 ? 8 * (nb - 1) + 1 : 0;
     int parents = (nbits >= 1 && stream_bit(bytes, nb, 0)) ? 1 : 0;
-    if (tid == 0) codes[0][0] = 0ull;
+    if (tid == 0) codes[0] = 0ull;
     __syncthreads();
     int cur = 0, depth = 0, pos = 1, bad = 0;
     while (parents > 0 && pos + 8 * parents <= nbits && depth < OCT_MAX_DEPTH) {
         const int n = 8 * parents;
         int base = 0;
-        for (int j0 = 0; j0 < n; j0 += 256) {
+        for (int j0 = 0; j0 < n; j0 += THREADS) {
             const int j = j0 + tid;
             const bool f = j < n && stream_bit(bytes, nb, pos + j);
             int tot;
-            const int r = base + block_scan_flag(f, s_w, 4, &tot) - 1;
-            if (f && r < OCT_DEC_CAP) codes[cur ^ 1][r] = codes[cur][j >> 3] * 8ull + (unsigned long long)(7 - (j & 7));
+            const int r = base + block_scan_flag(f, s_w, THREADS / 64, &tot) - 1;
+            if (f && r < CAP) codes[(cur ^ 1) * CAP + r] = codes[cur * CAP + (j >> 3)] * 8ull + (unsigned long long)(7 - (j & 7));
             base += tot;
         }
-        if (base > OCT_DEC_CAP) { bad = 1; break; }
+        if (base > CAP) { bad = 1; break; }
         __syncthreads();
         parents = base; pos += n; cur ^= 1; ++depth;
     }
@@ -260,10 +436,10 @@ __global__ __launch_bounds__(256) void octree_decode_full_kernel(const uint8_t *
     }
     if (tid == 0 && count) count[b] = parents;
     const float cell = __uint_as_float((unsigned)(127 - depth) << 23);          // 2^-depth
-    for (int i = tid; i < S_out; i += 256) {
+    for (int i = tid; i < S_out; i += THREADS) {
         float x = 0.f, y = 0.f, z = 0.f;
         if (parents > 0) {
-            const unsigned long long c = codes[cur][i < parents ? i : parents - 1];
+            const unsigned long long c = codes[cur * CAP + (i < parents ? i : parents - 1)];
             x = ((float)compact3(c >> 2) + 0.5f) * cell;
             y = ((float)compact3(c >> 1) + 0.5f) * cell;
             z = ((float)compact3(c) + 0.5f) * cell;
@@ -272,18 +448,44 @@ __global__ __launch_bounds__(256) void octree_decode_full_kernel(const uint8_t *
     }
 }
 
+__global__ __launch_bounds__(256) void octree_decode_full_kernel(const uint8_t *__restrict__ bytes_all, int stride,
+                                                                 const int32_t *__restrict__ nbytes, int S_out,
+                                                                 float *__restrict__ out, int32_t *__restrict__ count)
+{
+    __shared__ unsigned long long codes[2][OCT_DEC_CAP];
+    __shared__ int s_w[17];
+    octree_decode_full_body<256, OCT_DEC_CAP>(bytes_all, stride, nbytes, S_out, out, count, &codes[0][0], s_w);
+}
+
+// S_out up to 8192: 8192 codes per level, the two buffers are 128 KB of dynamic LDS -- one workgroup per CU, and one workgroup per cloud.
+#define OCT_DEC_WIDE_CAP 8192
+__global__ __launch_bounds__(1024) void octree_decode_full_wide_kernel(const uint8_t *__restrict__ bytes_all, int stride,
+                                                                       const int32_t *__restrict__ nbytes, int S_out,
+                                                                       float *__restrict__ out, int32_t *__restrict__ count)
+{
+    extern __shared__ unsigned long long wide_codes[];   // [2][OCT_DEC_WIDE_CAP]
+    __shared__ int s_w[17];
+    octree_decode_full_body<1024, OCT_DEC_WIDE_CAP>(bytes_all, stride, nbytes, S_out, out, count, wide_codes, s_w);
+}
+
 extern "C" int pccx_octree_decode(const uint8_t *bytes, int stride, const int32_t *nbytes, int B, int mode, int S_out,
                                   float *out, int32_t *count, void *stream)
 {
     if (B == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
     PCCX_CHECK_ARG(bytes && nbytes && out, "pccx_octree_decode: null pointer");
     PCCX_CHECK_ARG(B >= 0 && stride >= 1 && S_out >= 1, "pccx_octree_decode: bad shape");
-    PCCX_CHECK_ARG(mode == 0 || mode == 1, "pccx_octree_decode: mode must be 0 (reference) or 1 (full)");
+    PCCX_CHECK_ARG(mode == 0 || mode == 1 || mode == 2, "pccx_octree_decode: mode must be 0 (reference), 1 (full) or 2 (full, the wide kernel)");
     if (mode == 0) {
         PCCX_CHECK_ARG(S_out == 64, "pccx_octree_decode: reference mode always yields 64 points (octree_np.py:100), S_out=%d",
                        S_out);
         hipLaunchKernelGGL(octree_decode_reference_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, bytes, stride,
                            nbytes, B, out, count);
+    } else if (mode == 2 || S_out > 1024) {
+        const size_t lds = (size_t)2 * OCT_DEC_WIDE_CAP * 8;
+        PCCX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&octree_decode_full_wide_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(octree_decode_full_wide_kernel, dim3(B), dim3(1024), lds, (hipStream_t)stream, bytes, stride, nbytes, S_out,
+                           out, count);
     } else {
         hipLaunchKernelGGL(octree_decode_full_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, bytes, stride, nbytes, S_out,
                            out, count);

@@ -134,6 +134,88 @@ extern "C" int pccx_patch_groups(const float *keys_a, int floats_a, const float 
     return PCCX_OK;
 }
 
+// pccx_patch_groups_wide: up to 8192 patches per cloud.  The all-earlier-rows compare of patch_groups_rep_kernel is O(S^2 / threads) --
+// about 130 000 dependent LDS reads per thread of a 256-thread workgroup at S = 8192 with nearly every centre distinct (octree_mode
+// "full"), milliseconds per cloud -- so the wide form keeps an open-addressing table in LDS instead: 16384 slots, each holding the
+// LOWEST row index of the key class that owns it (-1 = empty).  A row probes linearly from its hash: an empty slot is claimed by
+// compare-and-swap, a slot whose row equals it bit for bit takes the row's index by atomic min, anything else moves on.  Slots are
+// never emptied and a class's rows all walk the same probe sequence, so a class owns exactly one slot and after the barrier that
+// slot holds its first row: rep.  Equality is decided on the rows themselves, as in the narrow form; the hash only picks the start.
+#define PG_WIDE_MAX_S 8192
+#define PG_WIDE_SLOTS 16384
+
+__global__ __launch_bounds__(1024) void patch_groups_rep_wide_kernel(PgKeys k, int S, int *__restrict__ rep, int *__restrict__ cnt)
+{
+    __shared__ int table[PG_WIDE_SLOTS];
+    __shared__ int s_cnt;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const size_t base = (size_t)b * S;
+    for (int i = tid; i < PG_WIDE_SLOTS; i += 1024) table[i] = -1;
+    if (tid == 0) s_cnt = 0;
+    __syncthreads();
+    int slot_of[PG_WIDE_MAX_S / 1024];
+#pragma unroll
+    for (int e = 0; e < PG_WIDE_MAX_S / 1024; ++e) {
+        const int i = tid + 1024 * e;
+        slot_of[e] = -1;
+        if (i < S) {
+            unsigned h = 2166136261u;
+            for (int c = 0; c < k.fa; ++c) h = (h ^ k.a[(base + i) * k.fa + c]) * 16777619u;
+            for (int c = 0; c < k.fb; ++c) h = (h ^ k.b[(base + i) * k.fb + c]) * 16777619u;
+            int slot = (int)((h ^ (h >> 15)) & (PG_WIDE_SLOTS - 1));
+            for (int probes = 0; probes < PG_WIDE_SLOTS; ++probes) {               // at most S <= 8192 slots are ever taken: an empty one is met
+                int cur = ((volatile int *)table)[slot];
+                if (cur < 0) cur = atomicCAS(&table[slot], -1, i);
+                if (cur < 0) { slot_of[e] = slot; break; }                         // claimed: this row opens its class
+                if (pg_rows_equal(k, base + i, base + cur)) {
+                    atomicMin(&table[slot], i);
+                    slot_of[e] = slot;
+                    break;
+                }
+                slot = (slot + 1) & (PG_WIDE_SLOTS - 1);
+            }
+        }
+    }
+    __syncthreads();
+    int mine = 0;
+#pragma unroll
+    for (int e = 0; e < PG_WIDE_MAX_S / 1024; ++e) {
+        const int i = tid + 1024 * e;
+        if (i < S) {
+            const int r = slot_of[e] >= 0 ? table[slot_of[e]] : i;
+            rep[base + i] = (int)(base + r);
+            mine += r == i ? 1 : 0;
+        }
+    }
+    if (mine) atomicAdd(&s_cnt, mine);
+    __syncthreads();
+    if (tid == 0) cnt[b] = s_cnt;
+}
+
+extern "C" int pccx_patch_groups_wide(const float *keys_a, int floats_a, const float *keys_b, int floats_b, int B, int S, int32_t *rep,
+                                      int32_t *uniq, int32_t *n_uniq, int32_t *workspace, void *stream)
+{
+    PCCX_CHECK_ARG(n_uniq, "pccx_patch_groups_wide: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    PCCX_CHECK_ARG(B >= 0 && S >= 1 && S <= PG_WIDE_MAX_S, "pccx_patch_groups_wide: need B >= 0 and 1 <= S <= %d (B=%d S=%d)", PG_WIDE_MAX_S, B, S);
+    PCCX_CHECK_ARG((size_t)B * (size_t)S <= 0x7FFFFFFFull, "pccx_patch_groups_wide: B * S does not fit an int32 patch index");
+    if (B == 0) {
+        PCCX_CHECK_HIP(pccx_zero_async(n_uniq, 4, st));
+        return PCCX_OK;
+    }
+    PCCX_CHECK_ARG(keys_a && rep && uniq && workspace, "pccx_patch_groups_wide: null pointer");
+    PCCX_CHECK_ARG(floats_a >= 1 && floats_b >= 0 && (floats_b == 0 || keys_b), "pccx_patch_groups_wide: bad key widths %d, %d", floats_a, floats_b);
+    const PgKeys k{(const unsigned *)keys_a, floats_b ? (const unsigned *)keys_b : nullptr, floats_a, floats_b};
+    int *cnt = workspace, *off = workspace + B;
+    hipLaunchKernelGGL(patch_groups_rep_wide_kernel, dim3(B), dim3(1024), 0, st, k, S, rep, cnt);
+    PCCX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(patch_groups_scan_kernel, dim3(1), dim3(1024), 0, st, (const int *)cnt, B, off, n_uniq);
+    PCCX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(patch_groups_compact_kernel, dim3(B), dim3(256), 0, st, (const int *)rep, S, (const int *)off, uniq);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
 // rows p with rep[p] != p of up to three (P, row_floats) arrays are overwritten with row rep[p] of the same array.  Representatives'
 // rows are only read, so the copy is in place.  T = uint4 when rows are whole 16-byte units, else float.
 template <typename T>

@@ -166,12 +166,14 @@ def stream_sizes(directory, names, threads=0):
 
 
 KNN_BRUTE_MAX_N = 32768        # pccx_knn / pccx_knn_list / pccx_knn_uniq keep a cloud's keys in LDS (csrc/knn.hip)
-OCTREE_MAX_S = 1024            # centres per cloud pccx_octree_encode, pccx_patch_groups and the decoder take
+OCTREE_MAX_S = 1024            # centres per cloud pccx_octree_encode, pccx_patch_groups and the narrow full decode take
+OCTREE_WIDE_MAX_S = 8192       # ... and their wide forms (pccx_octree_encode_wide, pccx_octree_decode above 1024, pccx_patch_groups_wide)
 
 
 class Codec:
     def __init__(self, ae, prob, K=256, ALPHA=2, N0=1024, octree_mode="reference", margin=0.01, matmul=None,
-                 decoder_matmul=None, sa_matmul=None, pn_matmul=None, group_duplicates=True, knn_search="auto"):
+                 decoder_matmul=None, sa_matmul=None, pn_matmul=None, group_duplicates=True, knn_search="auto",
+                 max_centres=OCTREE_MAX_S):
         """matmul: how the three transforms (SetAbstraction, PointNet, decoder) form their fp32 products --
         "f32" = v_mfma_f32_16x16x4_f32 (bit-for-bit a k-ordered fmaf chain), "bf16x3" = each fp32 operand split exactly into
         three bf16 pieces, six products per pair on the bf16 matrix cores, fp32 accumulate (fp32-level error, 2.6x the
@@ -181,7 +183,10 @@ class Codec:
         reconstruction either way; False computes every patch.
         knn_search: how compress finds the K points of a patch (compress.py:105-108) -- "brute" = the all-pairs kernels, which keep a
         cloud's keys in LDS and stop at KNN_BRUTE_MAX_N = 32768 points; "grid" = ops.GridIndex.knn_wide, the same patches bit for bit at any
-        size; "auto" = brute wherever it can run and the grid above (the hard limit, not a tuned crossover: DESIGN.md section 4.5)."""
+        size; "auto" = brute wherever it can run and the grid above (the hard limit, not a tuned crossover: DESIGN.md section 4.5).
+        max_centres: the most patch centres S = N*ALPHA/K a cloud may have, 1 .. OCTREE_WIDE_MAX_S = 8192.  Up to OCTREE_MAX_S = 1024 (the
+        default) everything runs as before; above it the octree coder, the full decode and the patch grouping take their wide forms and
+        the farthest point sampling its cooperative form (ops.farthest_point_sample_batch(workgroups="auto")) -- 1048576 points at K = 256."""
         from . import DEFAULT_MATMUL
         matmul = matmul or DEFAULT_MATMUL
         self.ae, self.prob = ae, prob
@@ -197,6 +202,9 @@ class Codec:
         if knn_search not in ("auto", "brute", "grid"):
             raise ValueError(f"knn_search must be 'auto', 'brute' or 'grid', got {knn_search!r}")
         self.knn_search = knn_search
+        if isinstance(max_centres, bool) or not isinstance(max_centres, int) or not 1 <= max_centres <= OCTREE_WIDE_MAX_S:
+            raise ValueError(f"max_centres must be an int in 1..{OCTREE_WIDE_MAX_S} (the wide octree coder's limit), got {max_centres!r}")
+        self.max_centres = max_centres
         if ae.K != K or ae.k != self.k:
             raise ValueError("AE was built for a different K / k")
 
@@ -206,23 +214,29 @@ class Codec:
         patch, where those forms cost more than they save, and the kernels take the lists as before."""
         return self.octree_mode == "reference" and self.group_duplicates
 
+    def _check_centres(self, S, what):
+        """S above max_centres: refused on the host, before anything is launched, with the limit in points and the way out."""
+        m = self.max_centres
+        if S > m:
+            raise ValueError(f"{what}; the octree coder takes at most {m}, which is "
+                             f"{m}*K/ALPHA = {m * self.K // self.ALPHA} points at K={self.K}, ALPHA={self.ALPHA}. "
+                             f"Larger clouds go through pccx.large.compress_large (blocks of points).")
+
     def compress(self, pc, start_idx, keep_extras=False):
         """pc (B,N,3) f32 on the GPU; start_idx (B,) FPS start per cloud (the reference draws it
         from torch.randint, pn_kit.py:321)."""
         B, N, _ = pc.shape
         d, L = self.ae.d, self.ae.L
         S = int(N * self.ALPHA // self.K)                                            # compress.py:93
-        if S > OCTREE_MAX_S:
-            raise ValueError(f"a cloud of {N} points gives S={S} patches; the octree coder takes at most {OCTREE_MAX_S}, which is "
-                             f"{OCTREE_MAX_S}*K/ALPHA = {OCTREE_MAX_S * self.K // self.ALPHA} points at K={self.K}, ALPHA={self.ALPHA}. "
-                             f"Larger clouds go through pccx.large.compress_large (blocks of points).")
+        self._check_centres(S, f"a cloud of {N} points gives S={S} patches")
         with stage("normalize"):
             pcn, center, longest = ops.normalize(pc, self.margin)                    # compress.py:90
         if self.octree_mode == "reference" and S != 64:
             raise ValueError(f"octree_mode='reference' reproduces octree_np.decode's hard-coded S=64 "
                              f"(octree_np.py:100; compress.py:102 asserts); got S={S}. Use octree_mode='full'.")
         with stage("fps"):
-            fps_idx = ops.farthest_point_sample_batch(pcn, S, start_idx)             # compress.py:96
+            fps_idx = ops.farthest_point_sample_batch(pcn, S, start_idx,             # compress.py:96
+                                                      workgroups="auto" if self.max_centres > OCTREE_MAX_S else None)
         with stage("gather"):
             sampled = ops.index_points(pcn, fps_idx)
         comp = Compressed.alloc(B, (ops.octree_bits_capacity(S) + 7) // 8, models.range_cap(S * d), N, pc.device)
@@ -262,6 +276,7 @@ class Codec:
         Compressed built by from_packed / read_files) the table is always recomputed, as decompress.py does."""
         B = comp.s_bytes.shape[0]
         d, L = self.ae.d, self.ae.L
+        self._check_centres(int(S), f"decompress(S={S})")
         with stage("octree_decode"):
             rec, cnt = ops.octree_decode(comp.s_bytes, comp.s_nbytes, self.octree_mode, S)    # decompress.py:80-85
         cdf_int = getattr(comp, "_cdf_int", None) if reuse_cdf else None

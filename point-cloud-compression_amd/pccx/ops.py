@@ -98,17 +98,95 @@ def denormalize(pc, center, longest, margin=0.01):
     return out
 
 
-def farthest_point_sample_batch(xyz, npoint, start_idx=None):
+FPS_COOP_POINTS_PER_WORKGROUP = 16384     # 1024 threads x 16 points in registers (csrc/geometry.hip, fps_coop_kernel)
+FPS_COOP_MAX_WORKGROUPS = 64              # per cloud: the flat barrier of pccx_fps_coop is sized for that many arrivals
+FPS_COOP_SPREAD = 2                       # "auto" aims at this many times the least G, i.e. 8 points per thread
+
+
+def fps_coop_workgroups(N, B, n_cus):
+    """Workgroups per cloud G that "auto" hands to pccx_fps_coop for B clouds of N points on a device of n_cus compute units.
+    Never below ceil(N / 16384) (a thread holds at most 16 points) nor above 64 or n_cus; FPS_COOP_SPREAD times the least G
+    where the whole batch is then resident at once (B * G <= n_cus), less -- down to the least G -- where that keeps it resident.
+    A batch that does not fit even at the least G is run in sub-batches of n_cus // G clouds by the caller."""
+    N, B, n_cus = int(N), int(B), int(n_cus)
+    if N < 1 or B < 0 or n_cus < 1:
+        raise ValueError(f"fps_coop_workgroups: need N >= 1, B >= 0, n_cus >= 1, got N={N} B={B} n_cus={n_cus}")
+    least = -(-N // FPS_COOP_POINTS_PER_WORKGROUP)
+    most = min(FPS_COOP_MAX_WORKGROUPS, n_cus)
+    if least > most:
+        raise ValueError(f"fps_coop_workgroups: a cloud of {N} points needs {least} workgroups of {FPS_COOP_POINTS_PER_WORKGROUP} points; "
+                         f"at most {most} can share a cloud on {n_cus} compute units")
+    G = min(FPS_COOP_SPREAD * least, most)
+    if B * G > n_cus:
+        G = max(least, min(G, n_cus // max(B, 1)))
+    return G
+
+
+def fps_auto_workgroups(N, npoint, B, n_cus):
+    """What workgroups="auto" does: G for pccx_fps_coop, or None for pccx_fps.  Cooperative wherever npoint > 1024 (a whole room: the
+    single workgroup would take seconds), and for N > 16384 -- where pccx_fps keeps its running minima in global memory -- when the whole
+    batch is resident in one launch: measured 4.3x to 8.3x faster at 65536 and 131072 points, B = 1, in each of three alternating rounds
+    (DESIGN.md 4.5).  Up to 16384 points pccx_fps holds the cloud in registers on one CU and stays."""
+    if B < 1 or npoint < 1:
+        return None
+    if npoint > 1024:
+        return fps_coop_workgroups(N, B, n_cus)
+    if N > FPS_COOP_POINTS_PER_WORKGROUP and -(-N // FPS_COOP_POINTS_PER_WORKGROUP) <= min(FPS_COOP_MAX_WORKGROUPS, n_cus):
+        G = fps_coop_workgroups(N, B, n_cus)
+        return G if B * G <= n_cus else None
+    return None
+
+
+def _n_cus(device):
+    return int(torch.cuda.get_device_properties(device).multi_processor_count)
+
+
+def _fps_coop(xyz, npoint, start, out, G, workspace):
+    """pccx_fps_coop over sub-batches of n_cus // G clouds; raises when a cloud's status word reports an expired barrier wait."""
+    B, N, _ = xyz.shape
+    lib = _lib.load()
+    G = int(G)
+    per = max(1, _n_cus(xyz.device) // max(G, 1))            # clouds per launch: B * G workgroups must all be resident (the entry checks G itself)
+    need = int(lib.pccx_fps_coop_workspace_bytes(B, int(npoint)))
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), device=xyz.device, dtype=torch.uint8)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.device != xyz.device or workspace.dtype != torch.uint8 or not workspace.is_contiguous()
+          or workspace.numel() < need or workspace.data_ptr() % 16):
+        raise _lib.PccxError(f"farthest_point_sample_batch: workspace must be a dense 16-byte aligned uint8 tensor of at least {need} bytes on {xyz.device}")
+    row = (int(npoint) + 2) * 8
+    for b0 in range(0, B, per):
+        nb = min(per, B - b0)
+        _lib.call("pccx_fps_coop", xyz[b0:].data_ptr(), nb, N, int(npoint), start[b0:].data_ptr() if start is not None else None,
+                  out[b0:].data_ptr(), G, workspace[b0 * row:].data_ptr(), _stream())
+    if B and npoint:
+        status = workspace[:B * row].view(torch.int64).view(B, int(npoint) + 2)[:, 1]
+        bad = torch.nonzero(status).flatten().tolist()            # the one read-back of this path (it is eager, never captured)
+        if bad:
+            raise _lib.PccxError(f"pccx_fps_coop: the workgroups of clouds {bad} gave up a barrier wait that outlasted its bound; their indices are incomplete")
+    return out
+
+
+def farthest_point_sample_batch(xyz, npoint, start_idx=None, workgroups=None, workspace=None):
     """pn_kit.farthest_point_sample_batch (pn_kit.py:309-330).  ``start_idx`` (B,) replaces the
-    reference's torch.randint draw (:321); None draws it the same way the reference does."""
+    reference's torch.randint draw (:321); None draws it the same way the reference does.
+    workgroups: None = pccx_fps, one workgroup per cloud; an int G = pccx_fps_coop with G workgroups per cloud (the same indices, bit
+    for bit; ceil(N / 16384) <= G <= 64; a batch with B * G above the device's compute units runs in sub-batches); "auto" =
+    fps_auto_workgroups' choice: the cooperative form where npoint > 1024 and for resident batches above 16384 points.  workspace: for the cooperative
+    form, a uint8 tensor of pccx_fps_coop_workspace_bytes(B, npoint) to use instead of a fresh one (the entry clears it itself)."""
     xyz = _f32c(xyz, "farthest_point_sample_batch")
     B, N, _ = xyz.shape
+    if isinstance(workgroups, str):
+        if workgroups != "auto":
+            raise ValueError(f"farthest_point_sample_batch: workgroups must be None, 'auto' or an int, got {workgroups!r}")
+        workgroups = fps_auto_workgroups(N, int(npoint), B, _n_cus(xyz.device))
     if start_idx is None:
         start_idx = torch.randint(0, N, (B,), dtype=torch.long)
     # start_idx == "zero": every cloud starts from its point 0 (pytorch3d's sample_farthest_points); the kernel takes a null table for
     # that, so nothing is uploaded (a pageable upload blocks the calling thread behind everything queued on its stream)
     start = None if isinstance(start_idx, str) and start_idx == "zero" else torch.as_tensor(start_idx).to(device=xyz.device, dtype=torch.int32).contiguous()
     out = torch.empty(B, npoint, device=xyz.device, dtype=torch.int64)
+    if workgroups is not None:
+        return _fps_coop(xyz, npoint, start, out, workgroups, workspace)
     work = torch.empty(B * N, device=xyz.device, dtype=torch.float32) if N > 16384 else None
     _lib.call("pccx_fps", xyz.data_ptr(), B, N, int(npoint), start.data_ptr() if start is not None else None, out.data_ptr(),
               work.data_ptr() if work is not None else None, _stream())
@@ -138,18 +216,23 @@ def knn_gather(x, idx):
     return index_points(x, idx)
 
 
-def patch_groups(keys_a, keys_b=None):
+PATCH_GROUPS_MAX_S = 1024          # pccx_patch_groups, pccx_octree_encode and the narrow full decode; above it the *_wide forms, to 8192
+WIDE_MAX_S = 8192
+
+
+def patch_groups(keys_a, keys_b=None, wide=False):
     """Which patches of a batch repeat an earlier patch of their own cloud (csrc/patch_groups.hip).  keys_a (B,S,fa) f32 and optionally
     keys_b (B,S,fb) f32: the key row of patch (b, i) is the fa + fb words of the two rows, compared bit for bit.  In octree_mode
     "reference" the decoded centres take at most 8 distinct values per cloud (octree_np.py:47-112 consumes one byte of the stream), so
-    the transforms run on about an eighth of the patches and the results are copied (replicate_rows).  Returns Groups, all on the device."""
+    the transforms run on about an eighth of the patches and the results are copied (replicate_rows).  Returns Groups, all on the device.
+    S > 1024 (to 8192), or wide=True at any S, takes pccx_patch_groups_wide: the same tables through a hash table in LDS."""
     a = _f32c(keys_a, "patch_groups.keys_a")
     B, S, fa = a.shape
     b = _f32c(keys_b.reshape(B, S, -1), "patch_groups.keys_b") if keys_b is not None else None
     buf = torch.empty(2 * B * S + 1 + _lib.load().pccx_patch_groups_workspace_ints(B), device=a.device, dtype=torch.int32)
     g = Groups(buf[:B * S], buf[B * S:2 * B * S], buf[2 * B * S:2 * B * S + 1])
     with stage("patch_groups"):
-        _lib.call("pccx_patch_groups", a.data_ptr(), fa, b.data_ptr() if b is not None else None, b.shape[2] if b is not None else 0, B, S,
+        _lib.call("pccx_patch_groups_wide" if wide or S > PATCH_GROUPS_MAX_S else "pccx_patch_groups", a.data_ptr(), fa, b.data_ptr() if b is not None else None, b.shape[2] if b is not None else 0, B, S,
                   g.rep.data_ptr(), g.uniq.data_ptr(), g.n_uniq.data_ptr(), buf[2 * B * S + 1:].data_ptr(), _stream())
     return g
 
@@ -463,11 +546,12 @@ def octree_bits_capacity(S):
     return int(_lib.load().pccx_octree_bits_capacity(int(S)))
 
 
-def octree_encode(centres, N, min_bpp, out_bytes=None, out_nbytes=None):
+def octree_encode(centres, N, min_bpp, out_bytes=None, out_nbytes=None, wide=False):
     """pn_kit.encode_sampled_np (pn_kit.py:380-401) + binary_array_to_byte_array (:463-467),
     batched on the GPU.  centres (B,S,3).  Returns dict of device tensors:
     bits (B,cap) u8 one byte per bit, nbits (B), depth (B), bytes (B,stride) u8, nbytes (B).
-    out_bytes / out_nbytes: caller-provided dense destinations of that shape (codec.Compressed's packed buffer)."""
+    out_bytes / out_nbytes: caller-provided dense destinations of that shape (codec.Compressed's packed buffer).
+    S > 1024 (to 8192), or wide=True at any S, takes pccx_octree_encode_wide: the same outputs."""
     centres = _f32c(centres, "octree_encode")
     B, S, _ = centres.shape
     cap = octree_bits_capacity(S)
@@ -483,15 +567,16 @@ def octree_encode(centres, N, min_bpp, out_bytes=None, out_nbytes=None):
              nbits=torch.empty(B, device=dev, dtype=torch.int32),
              depth=torch.empty(B, device=dev, dtype=torch.int32),
              bytes=out_bytes, nbytes=out_nbytes)
-    _lib.call("pccx_octree_encode", centres.data_ptr(), B, S, int(N), float(min_bpp), r["bits"].data_ptr(),
+    _lib.call("pccx_octree_encode_wide" if wide or S > PATCH_GROUPS_MAX_S else "pccx_octree_encode", centres.data_ptr(), B, S, int(N), float(min_bpp), r["bits"].data_ptr(),
               r["nbits"].data_ptr(), r["depth"].data_ptr(), r["bytes"].data_ptr(), r["nbytes"].data_ptr(), _stream())
     return r
 
 
-def octree_decode(bytes_, nbytes, mode="reference", S_out=64):
+def octree_decode(bytes_, nbytes, mode="reference", S_out=64, wide=False):
     """pn_kit.decode_sampled_np (pn_kit.py:424-431) from packed streams.  mode 'reference' is
     bug-compatible with octree_np.decode as written; 'full' is the level-by-level decode.
-    bytes_ (B,stride) u8, nbytes (B) i32 -> (points (B,S_out,3), count (B))."""
+    bytes_ (B,stride) u8, nbytes (B) i32 -> (points (B,S_out,3), count (B)).
+    'full' with S_out > 1024, or wide=True, decodes with the wide kernel: up to 8192 cells per level where the narrow one stops at 2048."""
     _dev(bytes_, "octree_decode")
     bytes_ = bytes_.contiguous()
     B, stride = bytes_.shape
@@ -499,5 +584,5 @@ def octree_decode(bytes_, nbytes, mode="reference", S_out=64):
     out = torch.empty(B, S_out, 3, device=bytes_.device, dtype=torch.float32)
     count = torch.empty(B, device=bytes_.device, dtype=torch.int32)
     _lib.call("pccx_octree_decode", bytes_.data_ptr(), stride, nbytes.data_ptr(), B,
-              {"reference": 0, "full": 1}[mode], int(S_out), out.data_ptr(), count.data_ptr(), _stream())
+              {"reference": 0, "full": 2 if wide else 1}[mode], int(S_out), out.data_ptr(), count.data_ptr(), _stream())
     return out, count

@@ -1,0 +1,120 @@
+#!/usr/bin/env python3
+"""Cost of whole-room clouds: the cooperative FPS against the single-workgroup one, and the whole-cloud codec above 1024
+patches against the block path.  A sibling of grid_nn_cost.py with the same discipline: one FRESH process per figure, 0.3 s of untimed
+fill kernels to settle the clocks, one warm-up call, then as many repeats as fit in about half a second (at least one) between two
+synchronisations; the contenders take turns, `rounds` times; every child runs under a time limit of its own and the first that fails or
+runs out of time ends the script.
+
+    python tools/experiments/rooms_cost.py --fps 65536,131072,262144,1048576 --codec 262144,524288,1048576 [--rounds 3] [--out FILE]
+
+--fps N: one CAD cloud of N points, npoint = N / 128 (S at K = 256): pccx_fps (fps_single) and pccx_fps_coop with G = the least
+ceil(N / 16384), twice and four times that, up to 64 (fps_coop@G).  --codec N: as grid_nn_cost.py --codec, with
+Codec(max_centres=8192): codec_whole and codec_blocks, ms per cloud, StageTimer's per-stage totals, bits per point, D1."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+PKG = os.path.join(ROOT, "point-cloud-compression_amd")
+sys.path[:0] = [HERE]
+from grid_nn_cost import settle, timed  # noqa: E402
+
+
+def fps_whats(n):
+    least = -(-n // 16384)
+    return ["fps_single"] + [f"fps_coop@{g}" for g in sorted({min(64, least), min(64, 2 * least), min(64, 4 * least)})]
+
+
+def child_fps(case, what):
+    sys.path[:0] = [ROOT, PKG]
+    import torch
+    from pccx import ops, synth
+    n = int(case)
+    y = torch.from_numpy(synth.cad_batch(300, 1, n)).cuda()
+    name, _, g = what.partition("@")
+    settle()
+    ms, reps = timed(lambda: ops.farthest_point_sample_batch(y, n // 128, [1], workgroups=int(g) if g else None))
+    print(json.dumps(dict(case=case, what=what, npoint=n // 128, ms=ms, reps=reps, us_per_round=round(1e3 * ms / (n // 128), 3))))
+
+
+def child_codec(case, what):
+    sys.path[:0] = [ROOT, PKG]
+    import numpy as np
+    import torch
+    from oracle import ref_model
+    from pccx import codec, large, models, ops, synth
+    N, K, d, L = int(case), 256, 16, 7
+    ae = models.AE(K, K // 2, d, L)
+    ae.load_state_dict(ref_model.seeded_state_dict(ae, 3, last_gain={"pn.mlp_Modules.3.0": 40.0}))
+    prob = models.ConditionalProbabilityModel(L, d)
+    prob.load_state_dict(ref_model.seeded_state_dict(prob, 4, gain=2.0))
+    cd = codec.Codec(ae.pack("cuda"), prob.pack("cuda"), K=K, octree_mode="full", max_centres=codec.OCTREE_WIDE_MAX_S)
+    pc = torch.from_numpy(synth.cad_batch(900, 1, N)).cuda()
+    res = {}
+    if what == "codec_whole":
+        def fn():
+            res["comp"] = [cd.compress(pc, np.array([1]))]
+            res["out"] = cd.decompress(res["comp"][0], S=N * 2 // K)
+    else:
+        def fn():
+            parts, nb, order, _ = large.compress_large(cd, pc[0])
+            res["comp"] = [c for _, c in parts]
+            res["out"] = large.decompress_large(cd, parts, nb, order, N)[None]
+    settle()
+    ms, reps = timed(fn)
+    timer = ops.StageTimer()
+    ops.set_timer(timer)
+    fn()
+    stages = {k: round(v[0], 3) for k, v in timer.totals_ms().items()}
+    ops.set_timer(None)
+    nbytes = sum(len(f) for c in res["comp"] for b in range(c.s_bytes.shape[0]) for f in c.files(b))
+    print(json.dumps(dict(case=case, what=what, ms=ms, reps=reps, bpp=round(8 * nbytes / N, 4),
+                          d1_psnr=round(float(codec.d1_psnr(pc, res["out"].reshape(1, -1, 3), search="grid")[0]), 3), stages=stages)))
+
+
+def run(mode, case, what, limit_s):
+    cmd = ["timeout", "-k", "10", str(int(limit_s)), sys.executable, os.path.abspath(__file__), "--child", case, "--what", what, "--mode", mode]
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    if p.returncode != 0:
+        raise SystemExit(f"{what} at {case} ended with {p.returncode} (limit {int(limit_s)} s): stop here\n{p.stderr[-2000:]}")
+    return json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--fps", default="")
+    ap.add_argument("--codec", default="")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--child", default=None)
+    ap.add_argument("--what", default=None)
+    ap.add_argument("--mode", default=None)
+    a = ap.parse_args()
+    if a.child:
+        return {"fps": child_fps, "codec": child_codec}[a.mode](a.child, a.what)
+    out = open(a.out, "a") if a.out else None
+    table = {}
+    for r in range(a.rounds):
+        for mode, cases in (("fps", a.fps), ("codec", a.codec)):
+            for case in [c for c in cases.split(",") if c]:
+                for what in (fps_whats(int(case)) if mode == "fps" else ["codec_whole", "codec_blocks"]):
+                    rec = dict(run(mode, case, what, 300), round=r)
+                    table.setdefault(f"{mode} {case}", {}).setdefault(what, []).append(rec["ms"])
+                    print(json.dumps(rec), flush=True)
+                    if out:
+                        out.write(json.dumps(rec) + "\n")
+                        out.flush()
+    lines = ["| case | figure | ms, each round |", "|---|---|---|"]
+    for case, row in table.items():
+        for what, v in row.items():
+            lines.append(f"| {case} | {what} | {', '.join(f'{m:.3f}' for m in v)} |")
+    print("\n" + "\n".join(lines))
+    if out:
+        out.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
