@@ -467,6 +467,32 @@ PCCX_API int pccx_range_decode(const int32_t *cdf_int, const uint8_t *in, int st
                                const int32_t *nbytes, int B, int nsym, int L, float *latent_q,
                                void *stream);
 
+/* Split form of the range-coded latent stream (opt-in; NOT a file the reference reads): the nsym symbols of a cloud are cut into
+ * P = ceil(nsym / seg_sym) independent segments, each coded by one wave exactly as pccx_range_encode codes a stream of that many
+ * symbols (fresh low / high, the same flush, zero-padded last byte), behind a directory of their byte counts.  Little-endian:
+ *     "PXS1" | nsym u32 | seg_sym u16 | reserved u16 = 0 | len[P] u16 | the P segment streams in order
+ * (nsym = 0: the 12 fixed bytes).  Both entry points always run the wave kernels and refuse, before anything is launched, L outside
+ * 2 .. 63, P above 8192, B above 65535 and a seg_sym above pccx_range_split_max_seg_sym(L) (host only: the largest seg_sym whose
+ * LDS images, at 2*seg_sym + 16 bytes per segment, fit the wave kernels' 60 KiB in both directions; 0 for an L they do not take).
+ * workspace: pccx_range_split_workspace_bytes(B, nsym, seg_sym) bytes on the device (host only; either direction: the encoder's
+ * (B*P) counts and (B*P, 2*seg_sym + 16) segment rows, the decoder's (B, P+1) offsets), 16-byte aligned.
+ * Encode: two launches (segments, then one pack kernel).  nbytes[b] = the file length, or -(bytes needed) when cap is too small;
+ *   row b of out receives the first min(|nbytes[b]|, cap) bytes of the file and nothing else.
+ * Decode: nbytes[b] is clamped to [0, stride]; a check kernel writes status[b] (below) and the segment offsets, then every segment is
+ *   decoded at its offset with its own length as the stream length (bytes past a segment read as zero).  A cloud whose status is
+ *   not 0 decodes every segment as from an empty stream: deterministic, and no byte of it is read beyond the check.
+ * pccx_split_stream_check_host: the same check (csrc/split_stream.h, one function for host and device) on host bytes, no GPU call;
+ *   segcap = 2*seg_sym + 16.  Returns the status: 0 ok; 1 shorter than its header, or wrong magic; 2 nsym / seg_sym / reserved
+ *   disagree with the call; 3 a length above segcap, or header + sum of the lengths != nbytes.  It reads no byte at or after nbytes. */
+PCCX_API int pccx_range_split_max_seg_sym(int L);
+PCCX_API size_t pccx_range_split_workspace_bytes(int B, int nsym, int seg_sym);
+PCCX_API int pccx_split_stream_check_host(const uint8_t *bytes, int64_t nbytes, int nsym, int seg_sym, int segcap);
+PCCX_API int pccx_range_encode_split(const int32_t *cdf_int, const float *latent_q, int B, int nsym, int seg_sym, int L,
+                                     uint8_t *out, int cap, int32_t *nbytes, void *workspace, void *stream);
+PCCX_API int pccx_range_decode_split(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes, int B,
+                                     int nsym, int seg_sym, int L, float *latent_q, int32_t *status, void *workspace,
+                                     void *stream);
+
 /* torchac's float -> 16-bit integer CDF conversion (torchac 0.9.3 _convert_to_int_and_normalize with
  * needs_normalization=True, the first step of encode_float_cdf / decode_float_cdf, compress.py:136, decompress.py:93):
  * cdf (nrows, Lp) f32 in [0,1] -> cdf_int (nrows, Lp) int32 holding 16-bit values. */

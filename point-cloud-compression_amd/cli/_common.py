@@ -79,5 +79,9 @@ def add_codec_flags(parser):
     parser.add_argument('--knn-search', choices=['auto', 'brute', 'grid'], default='auto',
                         help="Patch search of compress.py: 'brute' = the all-pairs kernels (clouds of up to 32768 points), 'grid' = the "
                              "exact grid index (any size, same patches), 'auto' = brute up to 32768 points and the grid above.")
+    parser.add_argument('--p-split', type=int, default=0, metavar='G',
+                        help="Write / read .p.bin in the split form: segments of G patches, each range-coded on its own behind a directory "
+                             "of segment lengths, coded and decoded in parallel (whole rooms; 64 is the measured choice).  0 = the "
+                             "reference's single stream.  Both sides must pass the same G; a split .p.bin is not a file the reference reads.")
     parser.add_argument('--batch', type=int, default=256, help='Clouds per launch sequence.')
     parser.add_argument('--seed', type=int, default=11, help='Seed of the per-file FPS start index.')

@@ -9,7 +9,7 @@ import numpy as np
 
 import _common  # noqa: F401
 import torch
-from pccx import codec, dist, ops, plyio
+from pccx import codec, dist, models, ops, plyio
 from pccx._lib import PccxError
 
 parser = argparse.ArgumentParser(prog='decompress.py', description='Deompress Point Clouds Using Trained Model.',
@@ -33,7 +33,8 @@ def main():
     rank, world = _common.setup_ranks(args)
     names = [names[i] for i in dist.shard_indices(len(names), rank, world)]                      # file i -> rank i mod world
     ae, prob = _common.load_models(args)
-    cd = codec.Codec(ae, prob, K=args.K, ALPHA=args.ALPHA, N0=args.N0, octree_mode=args.octree_mode, max_centres=codec.OCTREE_WIDE_MAX_S)
+    cd = codec.Codec(ae, prob, K=args.K, ALPHA=args.ALPHA, N0=args.N0, octree_mode=args.octree_mode, max_centres=codec.OCTREE_WIDE_MAX_S,
+                     p_split=args.p_split or None)
     times = []
     with torch.no_grad():
         for b0 in range(0, len(names), args.batch):
@@ -42,7 +43,19 @@ def main():
             t0 = time.time()                                                                     # decompress.py:77
             # the three files of every cloud of the chunk into ONE packed host buffer by the library's host threads
             # (pccx_read_streams_host; decompress.py:80-91,113 reads them one by one), then one upload
-            up = codec.Compressed.read_files(args.compressed_path, chunk, device=args.device)
+            if args.p_split:
+                # split .p.bin: the header rules on every file's bytes (pccx_split_stream_check_host) before the upload; the symbol count
+                # is taken from the file here and compared with the centres its .s.bin holds once those are decoded
+                up = codec.Compressed.read_files(args.compressed_path, chunk)
+                split_nsym = []
+                for n, row, nb in zip(chunk, up.p_bytes.numpy(), up.p_nbytes.numpy()):
+                    split_nsym.append(int.from_bytes(bytes(row[4:8]), 'little') if nb >= 8 else 0)
+                    why = models.split_stream_status(row[:nb], split_nsym[-1], args.p_split * args.d)
+                    if why:
+                        raise SystemExit(f"{n}.p.bin is not a split stream of --p-split {args.p_split}: {models.SPLIT_STATUS[why]}")
+                up = codec.Compressed.from_packed(up.packed.to(args.device, non_blocking=True), len(chunk), up.s_bytes.shape[1], up.p_bytes.shape[1], 0)
+            else:
+                up = codec.Compressed.read_files(args.compressed_path, chunk, device=args.device)
             s_b, s_n, p_b, p_n, c = up.s_bytes, up.s_nbytes, up.p_bytes, up.p_nbytes, up.c
             # number of centres each stream holds (decompress.py:85 takes S from the decoded array)
             _, count = ops.octree_decode(s_b, s_n, args.octree_mode, 64 if args.octree_mode == 'reference' else 1, wide=args.octree_mode == 'full')   # up to 8192 centres
@@ -57,6 +70,11 @@ def main():
             S_of = np.full(len(chunk), 64) if args.octree_mode == 'reference' else (count if args.S is None else np.full(len(chunk), args.S))
             if args.octree_mode == 'full' and args.S is not None and (count != args.S).any():
                 raise PccxError(f"--S {args.S} given but the streams hold {sorted(set(count.tolist()))} centres")
+            if args.p_split:
+                for n, nsym, S in zip(chunk, split_nsym, S_of.tolist()):
+                    if nsym != int(S) * args.d:
+                        raise SystemExit(f"{n}.p.bin holds {nsym} symbols but {n}.s.bin gives S={int(S)} patches of d={args.d}: "
+                                         + models.SPLIT_STATUS[2])
             clouds = [None] * len(chunk)
             for S in sorted(set(S_of.tolist())):                                                 # one launch sequence per S
                 sel = torch.from_numpy(np.flatnonzero(S_of == S)).to(args.device)

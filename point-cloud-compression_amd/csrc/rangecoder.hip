@@ -7,8 +7,11 @@
 // The coder is inherently serial per stream (S*d = 1024 symbols per cloud).  One wave per cloud:
 // the 64 lanes stage the cloud's tables and bytes through LDS with coalesced transfers and run the
 // serial recurrence wave-uniformly on the scalar unit (see "wave-uniform execution" below).  Streams
-// larger than the LDS budget fall back to one lane per cloud working from global memory.
+// larger than the LDS budget fall back to one lane per cloud working from global memory.  The opt-in
+// split form (split_stream.h) cuts a cloud's stream into segments that each fit the budget, one wave
+// per segment.
 #include "common.h"
+#include "split_stream.h"
 
 struct BitWriter {
     uint8_t *buf;
@@ -168,19 +171,18 @@ __device__ __forceinline__ unsigned rc_uni(unsigned v) { return __builtin_amdgcn
 // low 32 bits of (span * c) >> 16 with span = span32 + 1 in [1, 2^32]
 __device__ __forceinline__ unsigned rc_scale(unsigned span32, unsigned c) { return (unsigned)(((unsigned long long)span32 * c + c) >> 16); }
 
-__global__ __launch_bounds__(64) void range_encode_wave_kernel(const int32_t *__restrict__ cdf_int, const float *__restrict__ latent_q,
-                                                               int nsym, int Lp, int sym_offset, uint8_t *__restrict__ out, int cap,
-                                                               int32_t *__restrict__ nbytes)
+// One stream, one wave: c = the stream's tables [nsym][Lp], q = its nsym latents, out = its cap bytes, nbytes = its count.  The
+// pointers and counts must be wave-uniform (kernel arguments and blockIdx only).  LDS: rc_encode_lds(nsym, cap) bytes at smem.
+__device__ __forceinline__ void rc_encode_wave(unsigned char *smem, const int32_t *__restrict__ c, const float *__restrict__ q, int nsym,
+                                               int Lp, int sym_offset, uint8_t *__restrict__ out, int cap, int32_t *__restrict__ nbytes)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
-    uint2 *sc = (uint2 *)rc_smem;                                      // [nsym] (c_low, c_high)
+    uint2 *sc = (uint2 *)smem;                                         // [nsym] (c_low, c_high)
     unsigned *sout = (unsigned *)(sc + nsym);                          // [capw] output words (stream order = big endian)
-    const int b = blockIdx.x, lane = threadIdx.x;
+    const int lane = threadIdx.x;
     const int capw = (cap + 3) >> 2;
-    const int32_t *c = cdf_int + (size_t)b * nsym * Lp;
     const int max_symbol = Lp - 2;
     for (int i = lane; i < nsym; i += 64) {
-        int s = (int)latent_q[(size_t)b * nsym + i] + sym_offset;     // latent_quantized.to(int16) + L//2 (compress.py:135)
+        int s = (int)q[i] + sym_offset;                               // latent_quantized.to(int16) + L//2 (compress.py:135)
         s = s < 0 ? 0 : (s > max_symbol ? max_symbol : s);
         const int32_t *ci = c + (size_t)i * Lp;
         sc[i] = make_uint2((unsigned)ci[s] & 0xFFFFu, s == max_symbol ? 0x10000u : ((unsigned)ci[s + 1] & 0xFFFFu));
@@ -247,28 +249,37 @@ __global__ __launch_bounds__(64) void range_encode_wave_kernel(const int32_t *__
     run(!fb, pending);
     int n = nw * 4 + ((na + 7) >> 3);
     if (na > 0 && nw < capw && lane == 0) sout[nw] = __builtin_bswap32((unsigned)(acc << (32 - na)));   // zero-padded tail
-    if (lane == 0) nbytes[b] = n <= cap ? n : -n;                      // negative: capacity exceeded
+    if (lane == 0) *nbytes = n <= cap ? n : -n;                        // negative: capacity exceeded
     __syncthreads();
     if (n > cap) n = cap;
     const uint8_t *sb = (const uint8_t *)sout;
-    for (int i = lane; i < n; i += 64) out[(size_t)b * cap + i] = sb[i];
+    for (int i = lane; i < n; i += 64) out[i] = sb[i];
 }
 
-__global__ __launch_bounds__(64) void range_decode_wave_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in,
-                                                               int stride, const int32_t *__restrict__ nbytes, int nsym, int Lp,
-                                                               int sym_offset, float *__restrict__ latent_q)
+__global__ __launch_bounds__(64) void range_encode_wave_kernel(const int32_t *__restrict__ cdf_int, const float *__restrict__ latent_q,
+                                                               int nsym, int Lp, int sym_offset, uint8_t *__restrict__ out, int cap,
+                                                               int32_t *__restrict__ nbytes)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
+    const int b = blockIdx.x;
+    rc_encode_wave(rc_smem, cdf_int + (size_t)b * nsym * Lp, latent_q + (size_t)b * nsym, nsym, Lp, sym_offset, out + (size_t)b * cap, cap,
+                   nbytes + b);
+}
+
+// One stream, one wave: c = the stream's tables [nsym][Lp], in = its first byte, nb = its length already clamped to [0, stride]
+// (bytes from nb on are not read and count as zero), q = its nsym outputs.  The pointers and counts must be wave-uniform.  LDS:
+// rc_decode_lds(nsym, Lp - 1, stride) bytes at smem.
+__device__ __forceinline__ void rc_decode_wave(unsigned char *smem, const int32_t *__restrict__ c, const uint8_t *__restrict__ in, int stride,
+                                               int nb, int nsym, int Lp, int sym_offset, float *__restrict__ q)
+{
     const int ncdf = nsym * Lp;
-    unsigned short *scdf = (unsigned short *)rc_smem;                 // [ncdf]
-    unsigned *sin = (unsigned *)(rc_smem + (((size_t)ncdf * 2 + 3) & ~(size_t)3));   // [nwin] stream words, zero padded
+    unsigned short *scdf = (unsigned short *)smem;                    // [ncdf]
+    unsigned *sin = (unsigned *)(smem + (((size_t)ncdf * 2 + 3) & ~(size_t)3));      // [nwin] stream words, zero padded
     unsigned char *ssym = (unsigned char *)(sin + ((stride + 3) >> 2));               // [nsym]
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const int32_t *c = cdf_int + (size_t)b * ncdf;
-    const int nb = nbytes[b] < 0 ? 0 : (nbytes[b] > stride ? stride : nbytes[b]);
+    const int lane = threadIdx.x;
     const int nwin = (nb + 3) >> 2;
     for (int i = lane; i < ncdf; i += 64) scdf[i] = (unsigned short)c[i];
-    for (int i = lane; i < nwin * 4; i += 64) ((uint8_t *)sin)[i] = i < nb ? in[(size_t)b * stride + i] : (uint8_t)0;
+    for (int i = lane; i < nwin * 4; i += 64) ((uint8_t *)sin)[i] = i < nb ? in[i] : (uint8_t)0;
     __syncthreads();
     // bit reader: `buf` holds `have` unread bits in its low end, `nxt` is the word after them; words past
     // the stream read as 0
@@ -337,7 +348,18 @@ __global__ __launch_bounds__(64) void range_decode_wave_kernel(const int32_t *__
         }
     }
     __syncthreads();
-    for (int i = lane; i < nsym; i += 64) latent_q[(size_t)b * nsym + i] = (float)((int)ssym[i] - sym_offset);
+    for (int i = lane; i < nsym; i += 64) q[i] = (float)((int)ssym[i] - sym_offset);
+}
+
+__global__ __launch_bounds__(64) void range_decode_wave_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in,
+                                                               int stride, const int32_t *__restrict__ nbytes, int nsym, int Lp,
+                                                               int sym_offset, float *__restrict__ latent_q)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
+    const int b = blockIdx.x;
+    const int nb = nbytes[b] < 0 ? 0 : (nbytes[b] > stride ? stride : nbytes[b]);
+    rc_decode_wave(rc_smem, cdf_int + (size_t)b * nsym * Lp, in + (size_t)b * stride, stride, nb, nsym, Lp, sym_offset,
+                   latent_q + (size_t)b * nsym);
 }
 
 // LDS images of the two wave kernels: (c_low, c_high) per symbol + the output words; the 16-bit tables + the stream words +
@@ -392,6 +414,209 @@ extern "C" int pccx_range_decode(const int32_t *cdf_int, const uint8_t *in, int 
     hipLaunchKernelGGL(range_decode_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, cdf_int, in, stride, nbytes,
                        B, nsym, L + 1, L / 2, latent_q);
     PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+// ---- split stream: P independent segments per cloud, one wave each -----------------------------------------------------------
+// Layout and header rules: split_stream.h.  Encode = every segment by rc_encode_wave into a scratch row of segcap bytes, then one
+// pack kernel per call; decode = one check kernel per call (status + segment offsets per cloud), then every segment by
+// rc_decode_wave at its offset.  Scratch: counts (B*P) int32 | rows (B*P, segcap) u8 for encode, offsets (B, P+1) int32 for decode.
+static int rc_split_segcap(int seg_sym) { return 2 * seg_sym + 16; }            // models.range_cap
+
+// Largest seg_sym whose LDS images (encode and decode, at segcap bytes per segment) fit RC_MAX_LDS_BYTES; 0 for an L the wave decoder
+// does not take.  Both images grow with seg_sym.
+extern "C" int pccx_range_split_max_seg_sym(int L)
+{
+    if (L < 2 || L > 63) return 0;
+    int lo = 0, hi = RC_MAX_LDS_BYTES / 8;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (rc_encode_lds(mid, rc_split_segcap(mid)) <= RC_MAX_LDS_BYTES && rc_decode_lds(mid, L, rc_split_segcap(mid)) <= RC_MAX_LDS_BYTES) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+extern "C" size_t pccx_range_split_workspace_bytes(int B, int nsym, int seg_sym)
+{
+    if (B <= 0 || nsym < 0 || seg_sym < 1) return 0;
+    const size_t P = (size_t)pccx_split_segments(nsym, seg_sym);
+    const size_t enc = (size_t)B * P * 4 + (size_t)B * P * (size_t)rc_split_segcap(seg_sym), dec = (size_t)B * (P + 1) * 4;
+    return ((enc > dec ? enc : dec) + 15) & ~(size_t)15;
+}
+
+extern "C" int pccx_split_stream_check_host(const uint8_t *bytes, int64_t nbytes, int nsym, int seg_sym, int segcap)
+{
+    if (nsym < 0 || seg_sym < 1 || segcap < 0 || (!bytes && nbytes > 0)) return PCCX_SPLIT_BAD_FIELDS;   // no file agrees with such a call
+    return pccx_split_stream_check(bytes, nbytes, nsym, seg_sym, segcap, nullptr);
+}
+
+__global__ __launch_bounds__(64) void range_encode_split_kernel(const int32_t *__restrict__ cdf_int, const float *__restrict__ latent_q,
+                                                                int nsym, int seg_sym, int P, int Lp, int sym_offset,
+                                                                uint8_t *__restrict__ rows, int segcap, int32_t *__restrict__ counts)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
+    const int p = blockIdx.x, b = blockIdx.y;
+    const int first = p * seg_sym;                                     // < nsym: p < P
+    const int n = nsym - first < seg_sym ? nsym - first : seg_sym;     // ragged last segment
+    const size_t row = (size_t)b * P + p;
+    rc_encode_wave(rc_smem, cdf_int + ((size_t)b * nsym + first) * Lp, latent_q + (size_t)b * nsym + first, n, Lp, sym_offset,
+                   rows + row * segcap, segcap, counts + row);
+}
+
+// One cloud per blockIdx.x, gridDim.y workgroups share its segments.  Every workgroup scans the cloud's P counts (256 partial sums of
+// P/256 consecutive counts each), the first writes the header, and wave w of workgroup y copies segments y*4 + w, + 4*gridDim.y, ...
+// 64 consecutive bytes per store instruction.  Nothing is written at or after `cap`.  A count that overflowed its scratch row (a
+// table with zero-width symbols, outside the coder's contract) is copied as far as it was written and marks the cloud negative.
+#define RC_PACK_THREADS 256
+__global__ __launch_bounds__(RC_PACK_THREADS) void range_split_pack_kernel(const uint8_t *__restrict__ rows, const int32_t *__restrict__ counts,
+                                                                          int nsym, int seg_sym, int P, int segcap,
+                                                                          uint8_t *__restrict__ out, int cap, int32_t *__restrict__ nbytes)
+{
+    __shared__ int s_off[PCCX_SPLIT_MAX_SEGMENTS + 1];                 // segment offsets in the file
+    __shared__ long long s_part[RC_PACK_THREADS];
+    __shared__ int s_bad;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int32_t *cnt = counts + (size_t)b * P;
+    uint8_t *o = out + (size_t)b * cap;
+    const int per = (P + RC_PACK_THREADS - 1) / RC_PACK_THREADS;
+    const int p0 = t * per < P ? t * per : P, p1 = p0 + per < P ? p0 + per : P;
+    if (t == 0) s_bad = 0;
+    __syncthreads();
+    long long sum = 0;
+    int bad = 0;
+    for (int p = p0; p < p1; ++p) {
+        const int c = cnt[p];
+        bad |= c < 0;
+        sum += c < 0 ? -(long long)c : c;
+    }
+    s_part[t] = sum;
+    if (bad) s_bad = 1;
+    __syncthreads();
+    const long long header = PCCX_SPLIT_HEADER_BYTES + 2ll * P;
+    long long off = header;
+    for (int i = 0; i < t; ++i) off += s_part[i];
+    for (int p = p0; p < p1; ++p) {
+        s_off[p] = (int)(off < cap ? off : cap);                       // clamped: what lies at or after cap is not written
+        const int c = cnt[p];
+        off += c < 0 ? -(long long)c : c;
+    }
+    if (t == RC_PACK_THREADS - 1) {
+        // the last thread's running sum is the file length (p1 = P for it, or its range is empty and every range before it ends at P)
+        s_off[P] = (int)(off < cap ? off : cap);
+        if (blockIdx.y == 0) nbytes[b] = (off <= cap && !s_bad && off <= 0x7FFFFFFFll) ? (int)off : -(int)(off < 0x7FFFFFFFll ? off : 0x7FFFFFFFll);
+    }
+    __syncthreads();
+    if (blockIdx.y == 0) {
+        for (int i = t; i < header && i < cap; i += RC_PACK_THREADS) {
+            unsigned v;
+            if (i < 4) v = i == 0 ? 'P' : i == 1 ? 'X' : i == 2 ? 'S' : '1';
+            else if (i < 8) v = ((unsigned)nsym >> (8 * (i - 4))) & 0xFFu;
+            else if (i < 10) v = ((unsigned)seg_sym >> (8 * (i - 8))) & 0xFFu;
+            else if (i < 12) v = 0u;
+            else {
+                const int c = cnt[(i - 12) >> 1];
+                const unsigned len = (unsigned)(c < 0 ? (-(long long)c > 0xFFFF ? 0xFFFF : -c) : c);
+                v = (len >> (8 * (i & 1))) & 0xFFu;
+            }
+            o[i] = (uint8_t)v;
+        }
+    }
+    const int wave = t >> 6, lane = t & 63;
+    for (int p = blockIdx.y * (RC_PACK_THREADS / 64) + wave; p < P; p += gridDim.y * (RC_PACK_THREADS / 64)) {
+        const int c = cnt[p];
+        int len = c < 0 ? segcap : c;                                  // an overflowed row holds segcap bytes
+        len = len > segcap ? segcap : len;
+        const int at = s_off[p];
+        if (len > cap - at) len = cap - at;                            // at <= cap
+        const uint8_t *src = rows + ((size_t)b * P + p) * segcap;
+        for (int i = lane; i < len; i += 64) o[at + i] = src[i];
+    }
+}
+
+__global__ __launch_bounds__(64) void range_split_check_kernel(const uint8_t *__restrict__ in, int stride, const int32_t *__restrict__ nbytes,
+                                                               int B, int nsym, int seg_sym, int P, int segcap,
+                                                               int32_t *__restrict__ status, int32_t *__restrict__ offsets)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    // a count beyond the row is cut to the row before anything is read: such a file then fails its own length sum (status 3)
+    const int nb = nbytes[b] < 0 ? 0 : (nbytes[b] > stride ? stride : nbytes[b]);
+    status[b] = pccx_split_stream_check(in + (size_t)b * stride, nb, nsym, seg_sym, segcap, offsets + (size_t)b * (P + 1));
+}
+
+__global__ __launch_bounds__(64) void range_decode_split_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in, int stride,
+                                                                const int32_t *__restrict__ offsets, int nsym, int seg_sym, int P, int Lp,
+                                                                int sym_offset, int segcap, float *__restrict__ latent_q)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
+    const int p = blockIdx.x, b = blockIdx.y;
+    const int first = p * seg_sym;
+    const int n = nsym - first < seg_sym ? nsym - first : seg_sym;
+    const int32_t *off = offsets + (size_t)b * (P + 1) + p;
+    // the check kernel's offsets: 0 <= off[0] <= off[1] <= min(nbytes, stride), lengths <= segcap on status 0 and 0 otherwise; the
+    // clamps restate that here, where the addresses are formed
+    int at = (int)rc_uni((unsigned)off[0]), end = (int)rc_uni((unsigned)off[1]);
+    at = at < 0 ? 0 : (at > stride ? stride : at);
+    end = end < at ? at : (end > stride ? stride : end);
+    const int nb = end - at > segcap ? segcap : end - at;
+    rc_decode_wave(rc_smem, cdf_int + ((size_t)b * nsym + first) * Lp, in + (size_t)b * stride + at, segcap, nb, n, Lp, sym_offset,
+                   latent_q + (size_t)b * nsym + first);
+}
+
+static int rc_split_check_args(const char *who, int B, int nsym, int seg_sym, int L)
+{
+    PCCX_CHECK_ARG(B >= 0 && B <= 65535 && nsym >= 0 && seg_sym >= 1, "%s: bad shape (B=%d, nsym=%d, seg_sym=%d)", who, B, nsym, seg_sym);
+    PCCX_CHECK_ARG(L >= 2 && L <= 63, "%s: L=%d; the wave kernels take 2 <= L <= 63", who, L);
+    PCCX_CHECK_ARG(seg_sym <= pccx_range_split_max_seg_sym(L),
+                   "%s: seg_sym=%d does not fit the %d bytes of LDS a segment is staged in; the largest seg_sym at L=%d is %d", who, seg_sym,
+                   RC_MAX_LDS_BYTES, L, pccx_range_split_max_seg_sym(L));
+    PCCX_CHECK_ARG(pccx_split_segments(nsym, seg_sym) <= PCCX_SPLIT_MAX_SEGMENTS, "%s: %lld segments; at most %d (nsym=%d, seg_sym=%d)", who,
+                   (long long)pccx_split_segments(nsym, seg_sym), PCCX_SPLIT_MAX_SEGMENTS, nsym, seg_sym);
+    return PCCX_OK;
+}
+
+extern "C" int pccx_range_encode_split(const int32_t *cdf_int, const float *latent_q, int B, int nsym, int seg_sym, int L, uint8_t *out,
+                                       int cap, int32_t *nbytes, void *workspace, void *stream)
+{
+    if (B == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
+    const int rc = rc_split_check_args("pccx_range_encode_split", B, nsym, seg_sym, L);
+    if (rc != PCCX_OK) return rc;
+    const int P = (int)pccx_split_segments(nsym, seg_sym), segcap = rc_split_segcap(seg_sym);
+    PCCX_CHECK_ARG(out && nbytes && (nsym == 0 || (cdf_int && latent_q && workspace)), "pccx_range_encode_split: null pointer");
+    PCCX_CHECK_ARG(cap >= 8, "pccx_range_encode_split: bad shape (cap=%d)", cap);
+    int32_t *counts = (int32_t *)workspace;
+    uint8_t *rows = (uint8_t *)workspace + (size_t)B * P * 4;
+    if (P > 0) {
+        hipLaunchKernelGGL(range_encode_split_kernel, dim3(P, B), dim3(64), rc_encode_lds(seg_sym, segcap), (hipStream_t)stream, cdf_int,
+                           latent_q, nsym, seg_sym, P, L + 1, L / 2, rows, segcap, counts);
+        PCCX_CHECK_LAUNCH();
+    }
+    const int slices = P > 4 * 64 ? 64 : (P + 3) / 4 > 0 ? (P + 3) / 4 : 1;
+    hipLaunchKernelGGL(range_split_pack_kernel, dim3(B, slices), dim3(RC_PACK_THREADS), 0, (hipStream_t)stream, rows, counts, nsym, seg_sym, P,
+                       segcap, out, cap, nbytes);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+extern "C" int pccx_range_decode_split(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes, int B, int nsym,
+                                       int seg_sym, int L, float *latent_q, int32_t *status, void *workspace, void *stream)
+{
+    if (B == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
+    const int rc = rc_split_check_args("pccx_range_decode_split", B, nsym, seg_sym, L);
+    if (rc != PCCX_OK) return rc;
+    const int P = (int)pccx_split_segments(nsym, seg_sym), segcap = rc_split_segcap(seg_sym);
+    PCCX_CHECK_ARG(in && nbytes && status && workspace && (nsym == 0 || (cdf_int && latent_q)), "pccx_range_decode_split: null pointer");
+    PCCX_CHECK_ARG(stride >= 1, "pccx_range_decode_split: bad shape (stride=%d)", stride);
+    int32_t *offsets = (int32_t *)workspace;
+    hipLaunchKernelGGL(range_split_check_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, in, stride, nbytes, B, nsym, seg_sym, P,
+                       segcap, status, offsets);
+    PCCX_CHECK_LAUNCH();
+    if (P > 0) {
+        hipLaunchKernelGGL(range_decode_split_kernel, dim3(P, B), dim3(64), rc_decode_lds(seg_sym, L, segcap), (hipStream_t)stream, cdf_int, in,
+                           stride, offsets, nsym, seg_sym, P, L + 1, L / 2, segcap, latent_q);
+        PCCX_CHECK_LAUNCH();
+    }
     return PCCX_OK;
 }
 

@@ -173,7 +173,7 @@ OCTREE_WIDE_MAX_S = 8192       # ... and their wide forms (pccx_octree_encode_wi
 class Codec:
     def __init__(self, ae, prob, K=256, ALPHA=2, N0=1024, octree_mode="reference", margin=0.01, matmul=None,
                  decoder_matmul=None, sa_matmul=None, pn_matmul=None, group_duplicates=True, knn_search="auto",
-                 max_centres=OCTREE_MAX_S):
+                 max_centres=OCTREE_MAX_S, p_split=None):
         """matmul: how the three transforms (SetAbstraction, PointNet, decoder) form their fp32 products --
         "f32" = v_mfma_f32_16x16x4_f32 (bit-for-bit a k-ordered fmaf chain), "bf16x3" = each fp32 operand split exactly into
         three bf16 pieces, six products per pair on the bf16 matrix cores, fp32 accumulate (fp32-level error, 2.6x the
@@ -186,7 +186,13 @@ class Codec:
         size; "auto" = brute wherever it can run and the grid above (the hard limit, not a tuned crossover: DESIGN.md section 4.5).
         max_centres: the most patch centres S = N*ALPHA/K a cloud may have, 1 .. OCTREE_WIDE_MAX_S = 8192.  Up to OCTREE_MAX_S = 1024 (the
         default) everything runs as before; above it the octree coder, the full decode and the patch grouping take their wide forms and
-        the farthest point sampling its cooperative form (ops.farthest_point_sample_batch(workgroups="auto")) -- 1048576 points at K = 256."""
+        the farthest point sampling its cooperative form (ops.farthest_point_sample_batch(workgroups="auto")) -- 1048576 points at K = 256.
+        p_split: None (the default) writes ``.p.bin`` as the reference does, one range-coded stream per cloud, launch for launch as
+        before.  An int G >= 1 writes the split form (include/pccx.h): the S patches are cut into segments of G patches (G*d symbols),
+        each coded from a fresh coder state by its own wave behind a directory of segment lengths, so that a whole room's latents are
+        coded and decoded side by side and not by one lane.  Both sides must agree on p_split, as they must
+        on octree_mode: it is not recorded outside the stream's own header, which decompress checks.  A split ``.p.bin`` is NOT a file
+        the reference's decompress.py reads."""
         from . import DEFAULT_MATMUL
         matmul = matmul or DEFAULT_MATMUL
         self.ae, self.prob = ae, prob
@@ -205,6 +211,12 @@ class Codec:
         if isinstance(max_centres, bool) or not isinstance(max_centres, int) or not 1 <= max_centres <= OCTREE_WIDE_MAX_S:
             raise ValueError(f"max_centres must be an int in 1..{OCTREE_WIDE_MAX_S} (the wide octree coder's limit), got {max_centres!r}")
         self.max_centres = max_centres
+        if p_split is not None:
+            g_max = models.split_max_seg_sym(ae.L) // ae.d
+            if isinstance(p_split, bool) or not isinstance(p_split, int) or not 1 <= p_split <= g_max:
+                raise ValueError(f"p_split must be None or an int in 1..{g_max} patches per segment (a segment of p_split*d symbols is staged in "
+                                 f"LDS by one wave, d={ae.d}, L={ae.L}; L must be in 2..63), got {p_split!r}")
+        self.p_split = p_split
         if ae.K != K or ae.k != self.k:
             raise ValueError("AE was built for a different K / k")
 
@@ -239,7 +251,8 @@ class Codec:
                                                       workgroups="auto" if self.max_centres > OCTREE_MAX_S else None)
         with stage("gather"):
             sampled = ops.index_points(pcn, fps_idx)
-        comp = Compressed.alloc(B, (ops.octree_bits_capacity(S) + 7) // 8, models.range_cap(S * d), N, pc.device)
+        p_cap = models.range_cap(S * d) if self.p_split is None else models.split_cap(S * d, self.p_split * d)
+        comp = Compressed.alloc(B, (ops.octree_bits_capacity(S) + 7) // 8, p_cap, N, pc.device)
         with stage("octree_encode"):
             oc = ops.octree_encode(sampled, N, ops.OCTREE_BPP_DICT[self.K],          # compress.py:98
                                    out_bytes=comp.s_bytes, out_nbytes=comp.s_nbytes)
@@ -259,7 +272,10 @@ class Codec:
         with stage("prob"):
             cdf_int = self.prob.run(rec, ("cdf_int",), distinct=self._distinct())["cdf_int"]                    # compress.py:131-134
         with stage("range_encode"):
-            models.range_encode(cdf_int, q.view(B, S * d), L, out=comp.p_bytes, nb=comp.p_nbytes)   # compress.py:135-136
+            if self.p_split is None:
+                models.range_encode(cdf_int, q.view(B, S * d), L, out=comp.p_bytes, nb=comp.p_nbytes)   # compress.py:135-136
+            else:
+                models.range_encode_split(cdf_int, q.view(B, S * d), L, self.p_split * d, out=comp.p_bytes, nb=comp.p_nbytes)
         comp.c[:, :3].copy_(center)                                                  # compress.py:149-152
         comp.c[:, 3].copy_(longest)
         comp._cdf_int = cdf_int               # kept for decompress(reuse_cdf=True): the resident pipeline's shortcut, never part of the streams
@@ -284,7 +300,10 @@ class Codec:
             with stage("prob"):
                 cdf_int = self.prob.run(rec, ("cdf_int",), distinct=self._distinct())["cdf_int"]                     # decompress.py:88-92
         with stage("range_decode"):
-            q = models.range_decode(cdf_int, comp.p_bytes, comp.p_nbytes, L)              # decompress.py:93
+            if self.p_split is None:
+                q = models.range_decode(cdf_int, comp.p_bytes, comp.p_nbytes, L)          # decompress.py:93
+            else:
+                q = models.range_decode_split(cdf_int, comp.p_bytes, comp.p_nbytes, L, self.p_split * d)
         N = S * self.k                                                                    # decompress.py:106
         scale = float((N / self.N0) ** (1 / 3))
         with stage("ae_decode"):

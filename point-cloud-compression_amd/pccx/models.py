@@ -617,3 +617,84 @@ def range_decode(cdf_int, bytes_, nbytes, L):
     _lib.call("pccx_range_decode", cdf_int.contiguous().data_ptr(), bytes_.data_ptr(), bytes_.shape[1],
               nbytes.to(torch.int32).contiguous().data_ptr(), B, nsym, int(L), q.data_ptr(), _stream())
     return q
+
+
+# ---- split form of the latent stream (include/pccx.h: "PXS1" | nsym | seg_sym | 0 | len[P] | segments) -------------------------
+
+SPLIT_HEADER = 12
+SPLIT_MAX_SEGMENTS = 8192
+SPLIT_STATUS = {1: "shorter than its header, or no 'PXS1' magic (written without a split, or not a .p.bin)",
+                2: "nsym / seg_sym / reserved field disagree with the call (written with another split or another S)",
+                3: "a segment length above its capacity, or header + segment lengths != the byte count (truncated or extended)"}
+
+
+def split_segments(nsym, seg_sym):
+    return -(-int(nsym) // int(seg_sym))
+
+
+def split_cap(nsym, seg_sym):
+    """Capacity per cloud of the split stream: the 12 fixed bytes, P lengths, P segments of range_cap(seg_sym)."""
+    P = split_segments(nsym, seg_sym)
+    return SPLIT_HEADER + 2 * P + P * range_cap(seg_sym)
+
+
+def split_max_seg_sym(L):
+    """The largest seg_sym the split entry points take at L levels (the LDS image of one segment, both directions); 0 for an L
+    outside 2..63."""
+    return int(_lib.load().pccx_range_split_max_seg_sym(int(L)))
+
+
+def _split_workspace(B, nsym, seg_sym, device):
+    need = int(_lib.load().pccx_range_split_workspace_bytes(int(B), int(nsym), int(seg_sym)))
+    return workspace("range_split", max(need // 4, 4), device)
+
+
+def range_encode_split(cdf_int, latent_q, L, seg_sym, out=None, nb=None):
+    """The split stream of every cloud: cdf_int (B,nsym,L+1) int32, latent_q (B,nsym) -> (bytes (B,cap) u8, nbytes (B)); segment p
+    codes symbols [p*seg_sym, (p+1)*seg_sym) as range_encode codes a stream of that length.  nbytes < 0: `cap` too small, as there."""
+    B = cdf_int.shape[0]
+    nsym = cdf_int[0].numel() // (L + 1) if B else 0
+    seg_sym = int(seg_sym)
+    q = _f32c(latent_q.reshape(B, nsym), "range_encode_split")
+    if out is None:
+        out = torch.empty(B, split_cap(nsym, max(seg_sym, 1)), device=q.device, dtype=torch.uint8)
+    if nb is None:
+        nb = torch.empty(B, device=q.device, dtype=torch.int32)
+    if (out.dim() != 2 or out.shape[0] != B or out.dtype != torch.uint8 or not out.is_contiguous() or tuple(nb.shape) != (B,)
+            or nb.dtype != torch.int32 or not nb.is_contiguous()):
+        raise _lib.PccxError("range_encode_split: out must be dense (B,cap) u8 and nb dense (B,) i32")
+    ws = _split_workspace(B, nsym, seg_sym, q.device)
+    _lib.call("pccx_range_encode_split", cdf_int.contiguous().data_ptr(), q.data_ptr(), B, nsym, seg_sym, int(L), out.data_ptr(),
+              out.shape[1], nb.data_ptr(), ws.data_ptr(), _stream())
+    return out, nb
+
+
+def range_decode_split(cdf_int, bytes_, nbytes, L, seg_sym, check=True):
+    """The inverse -> latent_q (B,nsym) f32.  check=True reads the per-cloud status once and raises PccxError naming the clouds whose
+    header is refused (SPLIT_STATUS); check=False returns (latent_q, status (B,) i32 on the device) without a synchronisation -- a
+    refused cloud's symbols are those of an empty stream."""
+    B = cdf_int.shape[0]
+    nsym = cdf_int[0].numel() // (L + 1) if B else 0
+    seg_sym = int(seg_sym)
+    bytes_ = bytes_.contiguous()
+    q = torch.empty(B, nsym, device=bytes_.device, dtype=torch.float32)
+    status = torch.zeros(B, device=bytes_.device, dtype=torch.int32)
+    ws = _split_workspace(B, nsym, seg_sym, bytes_.device)
+    _lib.call("pccx_range_decode_split", cdf_int.contiguous().data_ptr(), bytes_.data_ptr(), bytes_.shape[1],
+              nbytes.to(torch.int32).contiguous().data_ptr(), B, nsym, seg_sym, int(L), q.data_ptr(), status.data_ptr(), ws.data_ptr(),
+              _stream())
+    if not check:
+        return q, status
+    st = status.cpu().numpy()
+    if st.any():
+        raise _lib.PccxError("range_decode_split: " + "; ".join(
+            f"clouds {[int(b) for b in (st == code).nonzero()[0]]}: {why}" for code, why in SPLIT_STATUS.items() if (st == code).any()))
+    return q
+
+
+def split_stream_status(data, nsym, seg_sym):
+    """pccx_split_stream_check_host on a bytes-like object (no GPU call): 0, or a key of SPLIT_STATUS."""
+    import ctypes
+    data = bytes(data)
+    buf = ctypes.create_string_buffer(data, max(len(data), 1))
+    return int(_lib.load().pccx_split_stream_check_host(ctypes.addressof(buf), len(data), int(nsym), int(seg_sym), range_cap(seg_sym)))

@@ -6,10 +6,14 @@ synchronisations; the contenders take turns, `rounds` times; every child runs un
 runs out of time ends the script.
 
     python tools/experiments/rooms_cost.py --fps 65536,131072,262144,1048576 --codec 262144,524288,1048576 [--rounds 3] [--out FILE]
+    python tools/experiments/rooms_cost.py --codec 65536,262144,524288,1048576 --p-split 64 --skip-blocks --out profiles/rooms_split_cost.jsonl
 
 --fps N: one CAD cloud of N points, npoint = N / 128 (S at K = 256): pccx_fps (fps_single) and pccx_fps_coop with G = the least
 ceil(N / 16384), twice and four times that, up to 64 (fps_coop@G).  --codec N: as grid_nn_cost.py --codec, with
-Codec(max_centres=8192): codec_whole and codec_blocks, ms per cloud, StageTimer's per-stage totals, bits per point, D1."""
+Codec(max_centres=8192): codec_whole and codec_blocks, ms per cloud, StageTimer's per-stage totals, bits per point, D1.
+--p-split G[,G...]: after codec_whole of every size, codec_whole_split@G = the same codec with Codec(p_split=G) on the same cloud with
+the same weights, the two layouts taking turns; a second table lists the range_encode / range_decode stages and the bits per point of
+every whole-cloud row.  --skip-blocks leaves codec_blocks out."""
 import argparse
 import json
 import os
@@ -51,10 +55,11 @@ def child_codec(case, what):
     ae.load_state_dict(ref_model.seeded_state_dict(ae, 3, last_gain={"pn.mlp_Modules.3.0": 40.0}))
     prob = models.ConditionalProbabilityModel(L, d)
     prob.load_state_dict(ref_model.seeded_state_dict(prob, 4, gain=2.0))
-    cd = codec.Codec(ae.pack("cuda"), prob.pack("cuda"), K=K, octree_mode="full", max_centres=codec.OCTREE_WIDE_MAX_S)
+    name, _, g = what.partition("@")
+    cd = codec.Codec(ae.pack("cuda"), prob.pack("cuda"), K=K, octree_mode="full", max_centres=codec.OCTREE_WIDE_MAX_S, p_split=int(g) if g else None)
     pc = torch.from_numpy(synth.cad_batch(900, 1, N)).cuda()
     res = {}
-    if what == "codec_whole":
+    if name in ("codec_whole", "codec_whole_split"):
         def fn():
             res["comp"] = [cd.compress(pc, np.array([1]))]
             res["out"] = cd.decompress(res["comp"][0], S=N * 2 // K)
@@ -88,6 +93,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--fps", default="")
     ap.add_argument("--codec", default="")
+    ap.add_argument("--p-split", default="")
+    ap.add_argument("--skip-blocks", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None)
     ap.add_argument("--what", default=None)
@@ -96,13 +103,16 @@ def main():
     if a.child:
         return {"fps": child_fps, "codec": child_codec}[a.mode](a.child, a.what)
     out = open(a.out, "a") if a.out else None
-    table = {}
+    table, coder = {}, {}
+    codec_whats = ["codec_whole"] + [f"codec_whole_split@{int(g)}" for g in a.p_split.split(",") if g] + ([] if a.skip_blocks else ["codec_blocks"])
     for r in range(a.rounds):
         for mode, cases in (("fps", a.fps), ("codec", a.codec)):
             for case in [c for c in cases.split(",") if c]:
-                for what in (fps_whats(int(case)) if mode == "fps" else ["codec_whole", "codec_blocks"]):
+                for what in (fps_whats(int(case)) if mode == "fps" else codec_whats):
                     rec = dict(run(mode, case, what, 300), round=r)
                     table.setdefault(f"{mode} {case}", {}).setdefault(what, []).append(rec["ms"])
+                    if what.startswith("codec_whole"):
+                        coder.setdefault((case, what), []).append((rec["stages"].get("range_encode", 0.0), rec["stages"].get("range_decode", 0.0), rec["bpp"]))
                     print(json.dumps(rec), flush=True)
                     if out:
                         out.write(json.dumps(rec) + "\n")
@@ -111,6 +121,10 @@ def main():
     for case, row in table.items():
         for what, v in row.items():
             lines.append(f"| {case} | {what} | {', '.join(f'{m:.3f}' for m in v)} |")
+    if a.p_split:
+        lines += ["", "| points | figure | range_encode ms, each round | range_decode ms, each round | bpp |", "|---|---|---|---|---|"]
+        for (case, what), v in coder.items():
+            lines.append(f"| {case} | {what} | {', '.join(f'{e:.3f}' for e, _, _ in v)} | {', '.join(f'{d_:.3f}' for _, d_, _ in v)} | {v[0][2]:.4f} |")
     print("\n" + "\n".join(lines))
     if out:
         out.write("\n".join(lines) + "\n")
