@@ -493,6 +493,40 @@ PCCX_API int pccx_range_decode_split(const int32_t *cdf_int, const uint8_t *in, 
                                      int nsym, int seg_sym, int L, float *latent_q, int32_t *status, void *workspace,
                                      void *stream);
 
+/* ---- region decode: the patches of ONE whole-room cloud that a box needs --------------------------------
+ * The reference has nothing like it (it stops at S = 64).  A cloud written with the split stream in segments of G patches is
+ * entered at its segments: these four entry points select the patches, evaluate the probability model for the touched segments'
+ * rows only, and decode those segments only.  Every result is, bit for bit, the corresponding rows of the full decode.
+ *
+ * pccx_region_select: one workgroup of 1024 threads, 1 <= S <= 8192, G >= 1.  centres (S,3) decoded patch centres; c4 = the four
+ *   floats of .c.bin on the device (centre xyz, longest side); box_host = lo xyz, hi xyz, six finite floats on the HOST with
+ *   lo <= hi, in the cloud's original coordinates; halo finite, >= 0.  Patch p is selected iff lo[a] - halo <= w[p][a] <= hi[a] + halo
+ *   on the three axes in fp32, w = pccx_denormalize of the centres (the same four rounded steps).  Outputs on the device, ascending,
+ *   from a block prefix scan (identical on every run): patch_idx (S) int64, the first n_sel valid; seg_idx (ceil(S/G)) int32, the
+ *   touched segments, the first n_seg valid; rows (S) int64, per selected patch (rank of its segment in seg_idx) * G + p % G;
+ *   counts (2) int32 = {n_sel, n_seg}.
+ * pccx_prob_feature: passes 1 and 1b of pccx_prob_forward for one cloud, S % 16 == 0: the tiles of 16 centres over up to 64
+ *   workgroups, whose 256 partial maxima each go to workspace (pccx_prob_feature_workspace_floats(S) floats, host only), then one
+ *   workgroup reduces them and writes feature (512 floats, 16-byte aligned).  Two launches in stream order.
+ * pccx_prob_rows: pass 2 + softmax + integer CDF of pccx_prob_forward for compact rows: compact row r stands for row
+ *   seg_idx[r / G] * G + r % G of the cloud (cut into [0, S - 1]; the rows past S of a ragged last segment are not to be read).
+ *   cdf_int (n_seg * G, d, L+1) int32, equal to the same rows of pccx_prob_forward's.  n_seg <= ceil(S/G); the d / L limits are
+ *   pccx_prob_forward's.  n_seg = 0 launches nothing.
+ * pccx_range_decode_split_list: pccx_range_decode_split for the listed segments of ONE cloud (B = 1; limits and refusals as there).
+ *   The check kernel writes status (1) and the offsets into workspace (pccx_range_split_workspace_bytes(1, nsym, seg_sym)); then
+ *   wave j decodes segment seg_idx[j] of the file with table rows j*seg_sym ... of cdf_int (n_list*seg_sym, L+1) into rows
+ *   j*seg_sym ... of latent_q (n_list*seg_sym); the ragged last segment has nsym - (P-1)*seg_sym symbols.  No byte of an unlisted
+ *   segment is read.  n_list = 0 runs the check alone. */
+PCCX_API int pccx_region_select(const float *centres, int S, const float *c4, double margin, const float *box_host, float halo, int G,
+                                int64_t *patch_idx, int32_t *seg_idx, int64_t *rows, int32_t *counts, void *stream);
+PCCX_API size_t pccx_prob_feature_workspace_floats(int S);
+PCCX_API int pccx_prob_feature(const float *centres, int S, const float *prob_blob, float *workspace, float *feature, void *stream);
+PCCX_API int pccx_prob_rows(const float *centres, int S, int d, int L, const float *prob_blob, const float *feature,
+                            const int32_t *seg_idx, int n_seg, int G, int32_t *cdf_int, void *stream);
+PCCX_API int pccx_range_decode_split_list(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes, int nsym,
+                                          int seg_sym, int L, const int32_t *seg_idx, int n_list, float *latent_q, int32_t *status,
+                                          void *workspace, void *stream);
+
 /* torchac's float -> 16-bit integer CDF conversion (torchac 0.9.3 _convert_to_int_and_normalize with
  * needs_normalization=True, the first step of encode_float_cdf / decode_float_cdf, compress.py:136, decompress.py:93):
  * cdf (nrows, Lp) f32 in [0,1] -> cdf_int (nrows, Lp) int32 holding 16-bit values. */

@@ -23,10 +23,22 @@ parser.add_argument('--S', type=int, default=None,
                          "'reference' mode is octree_np.decode as written, always 64).")
 parser.add_argument('--bin-ply-suffix', action='store_true',
                     help="Write <name>.bin.ply (what eval.py:172 looks for) instead of <name> (decompress.py:121).")
+parser.add_argument('--region', type=float, nargs=6, default=None, metavar=('X0', 'Y0', 'Z0', 'X1', 'Y1', 'Z1'),
+                    help="Decode only the patches whose centre lies in this box of the cloud's original coordinates "
+                         "(Codec.decompress_region); needs --p-split and --octree-mode full.")
+parser.add_argument('--region-halo', type=float, default=0.0, help="Grow the --region box by this much on every side when selecting patches.")
+parser.add_argument('--crop', action='store_true', help="With --region: drop the decoded points outside the box (the halo does not count).")
 
 
 def main():
     args = parser.parse_args()
+    if args.region is not None:
+        if not args.p_split:
+            raise SystemExit("--region needs --p-split G (a split .p.bin is what can be entered at a segment)")
+        if args.octree_mode != 'full':
+            raise SystemExit("--region needs --octree-mode full")
+    elif args.crop or args.region_halo:
+        raise SystemExit("--crop / --region-halo need --region")
     print(f"Processing on device (gpu/cpu): {args.device}")
     os.makedirs(args.decompressed_path, exist_ok=True)
     names = sorted(os.path.split(x)[1][:-6] for x in glob(os.path.join(args.compressed_path, '*.s.bin')))
@@ -76,14 +88,31 @@ def main():
                         raise SystemExit(f"{n}.p.bin holds {nsym} symbols but {n}.s.bin gives S={int(S)} patches of d={args.d}: "
                                          + models.SPLIT_STATUS[2])
             clouds = [None] * len(chunk)
-            for S in sorted(set(S_of.tolist())):                                                 # one launch sequence per S
-                sel = torch.from_numpy(np.flatnonzero(S_of == S)).to(args.device)
-                comp = codec.Compressed(s_b[sel], s_n[sel], p_b[sel], p_n[sel], c[sel], 0)
-                pc = cd.decompress(comp, S=int(S)).cpu().numpy()
-                for j, cloud in zip(sel.cpu().tolist(), pc):
-                    clouds[j] = cloud
+            if args.region is not None:
+                box = (args.region[:3], args.region[3:])
+                for j, n in enumerate(chunk):                                                    # one decompress_region call per file
+                    comp = codec.Compressed(s_b[j:j + 1], s_n[j:j + 1], p_b[j:j + 1], p_n[j:j + 1], c[j:j + 1], 0)
+                    reg = cd.decompress_region(comp, int(S_of[j]), box, halo=args.region_halo)
+                    pts = reg.points
+                    if args.crop:
+                        lo, hi = (torch.tensor(v, device=pts.device, dtype=torch.float32) for v in box)
+                        pts = pts[((pts >= lo) & (pts <= hi)).all(dim=1)]
+                    if pts.shape[0] == 0:
+                        print(f"{n}: no point in the region ({reg.segments.numel()} of {reg.n_segments_total} segments touched), skipped")
+                        continue
+                    print(f"{n}: {reg.patch_idx.numel()} patches from {reg.segments.numel()} of {reg.n_segments_total} segments")
+                    clouds[j] = pts.cpu().numpy()
+            else:
+                for S in sorted(set(S_of.tolist())):                                             # one launch sequence per S
+                    sel = torch.from_numpy(np.flatnonzero(S_of == S)).to(args.device)
+                    comp = codec.Compressed(s_b[sel], s_n[sel], p_b[sel], p_n[sel], c[sel], 0)
+                    pc = cd.decompress(comp, S=int(S)).cpu().numpy()
+                    for j, cloud in zip(sel.cpu().tolist(), pc):
+                        clouds[j] = cloud
             times += [(time.time() - t0) / len(chunk)] * len(chunk)                              # decompress.py:118
             for n, cloud in zip(chunk, clouds):
+                if cloud is None:                                                                # --region: nothing of this file in the box
+                    continue
                 plyio.save_point_cloud(cloud, os.path.join(args.decompressed_path, n + ('.bin.ply' if args.bin_ply_suffix else '')))
     g = dist.gather_summaries([0.0, 0.0, 0.0, 0.0, len(times), float(np.sum(times))], _common.summary_device(args))
     if rank == 0 and float(g[:, 4].sum()) > 0:

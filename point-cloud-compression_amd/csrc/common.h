@@ -43,6 +43,15 @@ __device__ __forceinline__ float pccx_sqdist(float ax, float ay, float az, float
     return d;
 }
 
+// One coordinate of pn_kit.denormalize (pn_kit.py:62-66): (v - 0.5) * longest / (1 - margin) + centre, each step rounded on its own.
+// denormalize_kernel and region_select_kernel both call it, so a patch centre lands on the same float in the cloud and in the box test.
+__device__ __forceinline__ float pccx_denorm1(float v, float longest, float one_minus_margin, float centre)
+{
+    v = __fsub_rn(v, 0.5f);
+    v = __fdiv_rn(__fmul_rn(v, longest), one_minus_margin);
+    return __fadd_rn(v, centre);
+}
+
 __device__ __forceinline__ int pccx_lane() { return threadIdx.x & 63; }
 
 // Zero `bytes` (a multiple of 4, 4-byte aligned) on the stream with a KERNEL rather than hipMemsetAsync.  The buffers cleared this way

@@ -75,9 +75,7 @@ __global__ void denormalize_kernel(const float *__restrict__ pc, int N, float on
     const float *p = pc + (size_t)b * N * 3;
     float *o = out + (size_t)b * N * 3;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < 3 * N; i += gridDim.x * blockDim.x) {
-        float v = __fsub_rn(p[i], 0.5f);
-        v = __fdiv_rn(__fmul_rn(v, lg), one_minus_margin);
-        o[i] = __fadd_rn(v, center[3 * b + i % 3]);
+        o[i] = pccx_denorm1(p[i], lg, one_minus_margin, center[3 * b + i % 3]);
     }
 }
 

@@ -17,6 +17,119 @@
 #include "common.h"
 #include "mfma_chain.h"
 
+// ---- the stages of prob_forward_kernel as functions, for the region kernels at the end of this file (pccx_prob_feature,
+// pccx_prob_rows): the same statements in the same order, so a centre's chain is prob_forward_kernel's k-tile for k-tile (a column of
+// an MFMA tile depends on nothing but its own input column).  prob_forward_kernel itself keeps its own text below: calling these
+// from it moved its register allocation (93 against 95 SGPRs, another instruction order), and that kernel is the headline's.
+// tests/test_region.py pins the two against each other bit for bit.  bl = the laundered blob pointer of the caller (opaque_uniform).
+
+// pass 1 on one tile: lane (g, n) carries the centre row at xyz; run[] keeps the maxima over the tiles seen so far
+__device__ __forceinline__ void prob_pn_tile(const float *bl, const float *xyz, int g, int lane, f32x4 (&run)[16])
+{
+    f32x4 in[1][1];
+    in[0][0][0] = g == 0 ? xyz[0] : 0.f;
+    in[0][0][1] = g == 0 ? xyz[1] : 0.f;
+    in[0][0][2] = g == 0 ? xyz[2] : 0.f;
+    in[0][0][3] = 0.f;
+    f32x4 a0[1][4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) a0[0][mt] = *(const f32x4 *)(bl + PRB_P_B0 + 16 * mt + 4 * g);
+    dense_acc<1, 4, 1, 4>((const f32x4 *)(bl + PRB_P_W0), lane, in, a0);
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) a0[0][mt] = relu4(a0[0][mt]);
+    f32x4 a1[1][8];
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) a1[0][mt] = *(const f32x4 *)(bl + PRB_P_B1 + 16 * mt + 4 * g);
+    dense_acc<4, 8, 1, 8>((const f32x4 *)(bl + PRB_P_W1), lane, a0, a1);
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) a1[0][mt] = relu4(a1[0][mt]);
+    f32x4 a2[1][16];
+#pragma unroll
+    for (int mt = 0; mt < 16; ++mt) a2[0][mt] = *(const f32x4 *)(bl + PRB_P_B2 + 16 * mt + 4 * g);
+    dense_acc<8, 16, 1, 16>((const f32x4 *)(bl + PRB_P_W2), lane, a1, a2);
+#pragma unroll
+    for (int mt = 0; mt < 16; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) run[mt][r] = fmaxf(run[mt][r], fmaxf(row16_max(a2[0][mt][r]), 0.f));
+}
+
+// pass 1b: u = b0 + W0[:, feature channels] feat, rows 128 wu .. 128 wu + 127 in wave wu (fragments from L2, as pass 1's)
+__device__ __forceinline__ void prob_feature_u(const float *bl, const float *sfeat, float *su, int lane, int g, int n, int wu)
+{
+    f32x4 fin[1][16];
+#pragma unroll
+    for (int kt = 0; kt < 16; ++kt) fin[0][kt] = *(const f32x4 *)(sfeat + 16 * kt + 4 * g);
+    f32x4 u[1][8];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) u[0][m] = *(const f32x4 *)(bl + PRB_M_B0 + 16 * (8 * wu + m) + 4 * g);
+    dense_acc<16, 8, 1, 32>((const f32x4 *)(bl + PRB_M_W0), lane, fin, u, 0, 8 * wu);
+    if (n == 0)
+#pragma unroll
+        for (int m = 0; m < 8; ++m) *(f32x4 *)(su + 16 * (8 * wu + m) + 4 * g) = u[0][m];
+}
+
+// pass 2 on one tile: su = pass 1b's 512 numbers in LDS, xyz = this lane's centre row, g from the laundered lane id the caller
+// also gave ws.lane; a2 receives the d*L logits of centre n
+template <class WS>
+__device__ __forceinline__ void prob_mlp_tile(const WS &ws, const float *bl, const float *su, const float *xyz, int g, f32x4 (&a2)[1][8])
+{
+    int f = 0;
+    f32x4 a0[1][32];
+#pragma unroll
+    for (int mt = 0; mt < 32; ++mt) a0[0][mt] = *(const f32x4 *)(su + 16 * mt + 4 * g);       // bias + the feature k-tiles (pass 1b)
+    {
+        f32x4 in[1][1];
+        in[0][0][0] = g == 0 ? xyz[0] : 0.f;
+        in[0][0][1] = g == 0 ? xyz[1] : 0.f;
+        in[0][0][2] = g == 0 ? xyz[2] : 0.f;
+        in[0][0][3] = 0.f;
+        dense_acc_stream<1, 32, 1>(ws, f, in, a0);                                              // the xyz k-tile, last as before
+    }
+#pragma unroll
+    for (int mt = 0; mt < 32; ++mt) a0[0][mt] = relu4(a0[0][mt]);
+#pragma unroll
+    for (int mt = 0; mt < 8; ++mt) a2[0][mt] = *(const f32x4 *)(bl + PRB_M_B2 + 16 * mt + 4 * g);
+#pragma clang loop unroll(full)
+    for (int mp = 0; mp < 16; ++mp) {
+        f32x4 a1[1][2];
+#pragma unroll
+        for (int m = 0; m < 2; ++m) a1[0][m] = *(const f32x4 *)(bl + PRB_M_B1 + 16 * (2 * mp + m) + 4 * g);
+        dense_acc_stream<32, 2, 1>(ws, f, a0, a1);
+#pragma unroll
+        for (int m = 0; m < 2; ++m) a1[0][m] = relu4(a1[0][m]);
+        dense_acc_stream<2, 8, 1>(ws, f, a1, a2);
+    }
+}
+
+// softmax + cumsum + integer CDF of the first ncen centres of a tile, one thread per (centre, latent dim); lg = the tile's
+// [16][128] logits in LDS, row0 = the output row of its centre 0
+__device__ __forceinline__ void prob_tables_tile(const float (*lgt)[128], int lane, int ncen, int d, int L, size_t row0,
+                                                 float *__restrict__ pmf, float *__restrict__ cdf, int32_t *__restrict__ cdf_int)
+{
+    const int Lp = L + 1;
+    for (int e = lane; e < ncen * d; e += 64) {
+        const int cn = e / d, i = e % d;
+        const float *lg = &lgt[cn][i * L];              // output.view(B,S,d,L): channel i*L + l
+        float mx = -INFINITY;
+        for (int l = 0; l < L; ++l) mx = fmaxf(mx, lg[l]);
+        float sum = 0.f;
+        for (int l = 0; l < L; ++l) sum += expf(lg[l] - mx);
+        const size_t row = (row0 + cn) * d + i;
+        float run_c = 0.f;
+        if (cdf) cdf[row * Lp] = 0.f;
+        if (cdf_int) cdf_int[row * Lp] = 0;
+        for (int l = 0; l < L; ++l) {
+            const float pv = expf(lg[l] - mx) / sum;
+            if (pmf) pmf[row * L + l] = pv;
+            run_c = run_c + pv;                                        // cumsum (pn_kit.py:453)
+            const float cv = fminf(run_c, 1.0f);                       // clamp(max=1) (pn_kit.py:460)
+            if (cdf) cdf[row * Lp + l + 1] = cv;
+            // torchac: round(cdf * (2^16 - (Lp-1))) + arange(Lp), kept to 16 bits
+            if (cdf_int) cdf_int[row * Lp + l + 1] = ((int)rintf(cv * (float)(65536 - (Lp - 1))) + (l + 1)) & 0xFFFF;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256, 2) void prob_forward_kernel(const float *__restrict__ centres, int S, int d, int L,
                                                               const float *__restrict__ blob, float *__restrict__ pmf,
                                                               float *__restrict__ cdf, int32_t *__restrict__ cdf_int)
@@ -454,6 +567,141 @@ extern "C" int pccx_prob_forward_distinct(const float *centres, int B, int S, in
     PCCX_CHECK_ARG(d >= 1 && d <= 16 && L >= 1 && L <= 15 && d * L <= 128, "pccx_prob_forward_distinct: unsupported d=%d L=%d", d, L);
     hipLaunchKernelGGL(prob_forward_distinct_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, centres, B, S, d, L, prob_blob,
                        pmf, cdf, cdf_int);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// The same function for a LIST of rows of one cloud (region decode): prob_forward_kernel cut at the one
+// quantity that couples a cloud's centres, pass 1's maximum.
+//   prob_feature_partial_kernel: pass 1 with the cloud's 16-centre tiles dealt over up to 64 workgroups x 4 waves; each workgroup
+//       leaves its 256 maxima (over its four waves) in the workspace.  fmaxf is exact in any grouping, so the maximum over the
+//       partials is prob_forward_kernel's sfeat[] bit for bit (the -INFINITY start and the fmaxf(., 0) stay as there).
+//   prob_feature_reduce_kernel: one workgroup takes that maximum and runs pass 1b with prob_forward_kernel's own call and wave
+//       split; the 512 numbers su[] go to HBM.  Two launches in stream order: no cooperative launch, no flag, no spin.
+//   prob_rows_kernel: pass 2 + softmax + integer CDF for compact rows: compact row r stands for row seg_idx[r / G] * G + r % G of
+//       the cloud (clamped into [0, S - 1]: the rows past S of a ragged last segment are computed on row S - 1 and never read).  A wave
+//       takes 16 compact rows, a workgroup four tiles in ONE pass over the weight ring; all four waves walk every chunk, an idle
+//       wave of the last workgroup on a clamped tile whose result it drops, and ws.drain() runs before the workgroup retires.
+// ------------------------------------------------------------------------------------------
+#define PRB_FEATURE_MAX_WG 64
+
+__global__ __launch_bounds__(256, 2) void prob_feature_partial_kernel(const float *__restrict__ centres, int S,
+                                                                      const float *__restrict__ blob, float *__restrict__ partial)
+{
+    __shared__ float smax[4][256];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int g = lane >> 4, n = lane & 15;
+    const int ntiles = S >> 4;
+    f32x4 run[16];
+#pragma unroll
+    for (int mt = 0; mt < 16; ++mt) run[mt][0] = run[mt][1] = run[mt][2] = run[mt][3] = -INFINITY;
+    for (int tile = blockIdx.x * 4 + w; tile < ntiles; tile += 4 * gridDim.x) {
+        const float *bl = opaque_uniform(blob);
+        prob_pn_tile(bl, centres + 3 * (tile * 16 + n), g, lane, run);
+    }
+    if (n == 0)
+#pragma unroll
+        for (int mt = 0; mt < 16; ++mt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) smax[w][16 * mt + 4 * g + r] = run[mt][r];
+    __syncthreads();
+    partial[(size_t)blockIdx.x * 256 + tid] = fmaxf(fmaxf(smax[0][tid], smax[1][tid]), fmaxf(smax[2][tid], smax[3][tid]));
+}
+
+__global__ __launch_bounds__(256, 2) void prob_feature_reduce_kernel(const float *__restrict__ partial, int nwg,
+                                                                     const float *__restrict__ blob, float *__restrict__ feature)
+{
+    __shared__ __attribute__((aligned(16))) float sfeat[256];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int g = lane >> 4, n = lane & 15;
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    float m = partial[tid];
+    for (int j = 1; j < nwg; ++j) m = fmaxf(m, partial[(size_t)j * 256 + tid]);
+    sfeat[tid] = m;
+    __syncthreads();
+    prob_feature_u(opaque_uniform(blob), sfeat, feature, lane, g, n, wu);
+}
+
+__global__ __launch_bounds__(256, 2) void prob_rows_kernel(const float *__restrict__ centres, int S, int d, int L,
+                                                           const float *__restrict__ blob, const float *__restrict__ feature,
+                                                           const int32_t *__restrict__ seg_idx, int n_seg, int G,
+                                                           int32_t *__restrict__ cdf_int)
+{
+    __shared__ __attribute__((aligned(16))) f32x4 swt[4 * PRB_WS_CHUNK * 64];   // 32 KiB weight ring, four chunks deep
+    __shared__ __attribute__((aligned(16))) float su[512];
+    __shared__ __attribute__((aligned(16))) float slog[4][16][128];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    const int nrows = n_seg * G, ntiles = (nrows + 15) >> 4;
+    WStreamT<PRB_WS_CHUNK, 4, 4> ws{blob + PRB_STREAM, swt, PRB_STREAM_CHUNKS, lane, wu, false};   // one pass: nothing is issued past it
+    ws.prologue();
+    if (tid < 128) *(f32x4 *)(su + 4 * tid) = *(const f32x4 *)(feature + 4 * tid);
+    __syncthreads();
+
+    const int tile = blockIdx.x * 4 + w;
+    {
+        const float *bl = opaque_uniform(blob);
+        ws.g = bl + PRB_STREAM;
+        // lane indices from a laundered lane id, as in prob_forward_kernel
+        int lane2 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        asm volatile("" : "+v"(lane2));
+        const int g = lane2 >> 4, n = lane2 & 15;
+        ws.lane = lane2;
+        int r = (tile < ntiles ? tile : ntiles - 1) * 16 + n;
+        r = r < nrows ? r : nrows - 1;                        // the ragged last tile: walked on its last row, not stored
+        int c = seg_idx[r / G] * G + r % G;
+        c = c < 0 ? 0 : (c < S ? c : S - 1);                  // whatever the list holds, the address stays inside the cloud
+        f32x4 a2[1][8];
+        prob_mlp_tile(ws, bl, su, centres + 3 * c, g, a2);
+        if (tile < ntiles)
+#pragma unroll
+            for (int mt = 0; mt < 8; ++mt) *(f32x4 *)(&slog[w][n][16 * mt + 4 * g]) = a2[0][mt];
+    }
+    __syncthreads();
+    if (tile < ntiles) {
+        const int left = nrows - tile * 16;
+        prob_tables_tile(slog[w], lane, left < 16 ? left : 16, d, L, (size_t)tile * 16, nullptr, nullptr, cdf_int);
+    }
+    ws.drain();                                           // no DMA may land after the workgroup retires
+}
+
+static int prob_feature_workgroups(int S)
+{
+    const int rounds = ((S >> 4) + 3) / 4;                // workgroup rounds of four tiles
+    return rounds < 1 ? 1 : (rounds > PRB_FEATURE_MAX_WG ? PRB_FEATURE_MAX_WG : rounds);
+}
+
+extern "C" size_t pccx_prob_feature_workspace_floats(int S)
+{
+    return S < 16 ? 0 : (size_t)prob_feature_workgroups(S) * 256;
+}
+
+extern "C" int pccx_prob_feature(const float *centres, int S, const float *prob_blob, float *workspace, float *feature, void *stream)
+{
+    PCCX_CHECK_ARG(centres && prob_blob && workspace && feature, "pccx_prob_feature: null pointer");
+    PCCX_CHECK_ARG(S >= 16 && S % 16 == 0, "pccx_prob_feature: need S %% 16 == 0 (S=%d)", S);
+    PCCX_CHECK_ARG(((uintptr_t)feature & 15) == 0, "pccx_prob_feature: feature must be 16-byte aligned");
+    const int nwg = prob_feature_workgroups(S);
+    hipLaunchKernelGGL(prob_feature_partial_kernel, dim3(nwg), dim3(256), 0, (hipStream_t)stream, centres, S, prob_blob, workspace);
+    PCCX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(prob_feature_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, workspace, nwg, prob_blob, feature);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+extern "C" int pccx_prob_rows(const float *centres, int S, int d, int L, const float *prob_blob, const float *feature,
+                              const int32_t *seg_idx, int n_seg, int G, int32_t *cdf_int, void *stream)
+{
+    if (n_seg == 0) return PCCX_OK;   // empty list: nothing to do, pointers may be null
+    PCCX_CHECK_ARG(centres && prob_blob && feature && seg_idx && cdf_int, "pccx_prob_rows: null pointer");
+    PCCX_CHECK_ARG(S >= 16 && S % 16 == 0, "pccx_prob_rows: need S %% 16 == 0 (S=%d)", S);
+    PCCX_CHECK_ARG(d >= 1 && d <= 16 && L >= 1 && L <= 15 && d * L <= 128, "pccx_prob_rows: unsupported d=%d L=%d", d, L);
+    PCCX_CHECK_ARG(G >= 1 && n_seg >= 0 && n_seg <= (S + G - 1) / G, "pccx_prob_rows: %d segments of G=%d patches listed for S=%d", n_seg, G, S);
+    PCCX_CHECK_ARG(((uintptr_t)feature & 15) == 0, "pccx_prob_rows: feature must be 16-byte aligned");
+    const int ntiles = (int)(((int64_t)n_seg * G + 15) >> 4);
+    hipLaunchKernelGGL(prob_rows_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, centres, S, d, L, prob_blob, feature,
+                       seg_idx, n_seg, G, cdf_int);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }

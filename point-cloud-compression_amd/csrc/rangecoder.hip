@@ -620,6 +620,51 @@ extern "C" int pccx_range_decode_split(const int32_t *cdf_int, const uint8_t *in
     return PCCX_OK;
 }
 
+// The listed form (region decode): wave j decodes segment seg_idx[j] of ONE cloud's file with table rows and output rows
+// j * seg_sym ..., both compact.  A thin caller of rc_decode_wave like the kernel above; the bytes it reads are the directory's
+// offsets of that segment alone, so no byte of an unlisted segment is touched.  An index outside [0, P) is cut into it.
+__global__ __launch_bounds__(64) void range_decode_split_list_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in,
+                                                                     int stride, const int32_t *__restrict__ offsets,
+                                                                     const int32_t *__restrict__ seg_idx, int nsym, int seg_sym, int P,
+                                                                     int Lp, int sym_offset, int segcap, float *__restrict__ latent_q)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
+    const int j = blockIdx.x;
+    int p = (int)rc_uni((unsigned)seg_idx[j]);
+    p = p < 0 ? 0 : (p > P - 1 ? P - 1 : p);
+    const int first = p * seg_sym;
+    const int n = nsym - first < seg_sym ? nsym - first : seg_sym;     // the ragged last segment, as range_decode_split_kernel
+    const int32_t *off = offsets + p;
+    int at = (int)rc_uni((unsigned)off[0]), end = (int)rc_uni((unsigned)off[1]);
+    at = at < 0 ? 0 : (at > stride ? stride : at);
+    end = end < at ? at : (end > stride ? stride : end);
+    const int nb = end - at > segcap ? segcap : end - at;
+    rc_decode_wave(rc_smem, cdf_int + (size_t)j * seg_sym * Lp, in + at, segcap, nb, n, Lp, sym_offset, latent_q + (size_t)j * seg_sym);
+}
+
+extern "C" int pccx_range_decode_split_list(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes, int nsym,
+                                            int seg_sym, int L, const int32_t *seg_idx, int n_list, float *latent_q, int32_t *status,
+                                            void *workspace, void *stream)
+{
+    const int rc = rc_split_check_args("pccx_range_decode_split_list", 1, nsym, seg_sym, L);
+    if (rc != PCCX_OK) return rc;
+    const int P = (int)pccx_split_segments(nsym, seg_sym), segcap = rc_split_segcap(seg_sym);
+    PCCX_CHECK_ARG(n_list >= 0 && n_list <= P, "pccx_range_decode_split_list: %d segments listed of %d", n_list, P);
+    PCCX_CHECK_ARG(in && nbytes && status && workspace && (n_list == 0 || (cdf_int && latent_q && seg_idx)),
+                   "pccx_range_decode_split_list: null pointer");
+    PCCX_CHECK_ARG(stride >= 1, "pccx_range_decode_split_list: bad shape (stride=%d)", stride);
+    int32_t *offsets = (int32_t *)workspace;
+    hipLaunchKernelGGL(range_split_check_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, in, stride, nbytes, 1, nsym, seg_sym, P, segcap,
+                       status, offsets);
+    PCCX_CHECK_LAUNCH();
+    if (n_list > 0) {
+        hipLaunchKernelGGL(range_decode_split_list_kernel, dim3(n_list), dim3(64), rc_decode_lds(seg_sym, L, segcap), (hipStream_t)stream,
+                           cdf_int, in, stride, offsets, seg_idx, nsym, seg_sym, P, L + 1, L / 2, segcap, latent_q);
+        PCCX_CHECK_LAUNCH();
+    }
+    return PCCX_OK;
+}
+
 // torchac's float -> 16-bit CDF conversion (torchac 0.9.3 _convert_to_int_and_normalize, needs_normalization=True; the
 // same formula as prob_forward_kernel's epilogue): cdf_int[l] = (round(cdf[l] * (2^16 - (Lp - 1))) + l) mod 2^16.
 __global__ void cdf_float_to_int_kernel(const float *__restrict__ cdf, int64_t n, int Lp, int32_t *__restrict__ out)

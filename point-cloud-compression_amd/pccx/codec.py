@@ -311,6 +311,74 @@ class Codec:
                                   comp.c[:, 3].contiguous(), S=S, scale=scale, margin=self.margin,
                                   matmul=self.decoder_matmul, group=self.group_duplicates, short_list=self._distinct())
 
+    def decompress_region(self, comp, S, box, halo=0.0):
+        """The decoded patches of ONE cloud whose centre lies in a box, without decoding the rest -> Region.
+
+        comp: a Compressed of one cloud (B == 1) written by a Codec with this p_split = G and octree_mode="full".  box = (lo, hi), six
+        finite floats with lo <= hi in the cloud's original coordinates; halo >= 0 grows it on every side.  With rec the S decoded
+        centres and w = ops.denormalize(rec, center, longest, margin), patch p is selected iff lo[a] - halo <= w[p][a] <= hi[a] + halo
+        on the three axes in fp32; a touched segment is one that holds a selected patch.  Region.points is bit for bit
+        ``decompress(comp, S)[0].view(S, k, 3)[patch_idx].reshape(-1, 3)``: the probability model's per-centre part, the range
+        decoder and the AE decoder run for the touched segments / selected patches only.  The decoded
+        centres come out in descending Morton order, so a box meets few segments.
+
+        ONE read-back sizes the launches that follow: the two counts of the selection, together with the status word of the split
+        stream's header check.  That read-back is the only synchronisation.  An empty selection returns points of shape (0, 3) and
+        launches nothing after it.  Where the fused probability kernel does not cover the shape (prob.fused_ok(S) false) or the AE
+        is not fused, the whole cloud is decoded by decompress() and the selected rows are taken: the same result by definition.
+        Refused with ValueError before any launch: p_split None, octree_mode other than "full", a batch, a bad box or halo, S above
+        max_centres.  A stream written without this split raises PccxError as decompress() does."""
+        if self.p_split is None:
+            raise ValueError("decompress_region needs p_split (the split .p.bin is what can be entered at a segment); this Codec has p_split=None")
+        if self.octree_mode != "full":
+            raise ValueError(f"decompress_region needs octree_mode='full', got octree_mode={self.octree_mode!r}")
+        B = comp.s_bytes.shape[0]
+        if B != 1:
+            raise ValueError(f"decompress_region takes comp holding ONE cloud, got B={B}")
+        ops.check_box(box, halo)
+        S = int(S)
+        self._check_centres(S, f"decompress_region(S={S})")
+        d, L, G = self.ae.d, self.ae.L, self.p_split
+        fast = self.prob.fused_ok(S) and self.ae.fused_d
+        with stage("octree_decode"):
+            rec, _ = ops.octree_decode(comp.s_bytes, comp.s_nbytes, self.octree_mode, S)
+        head = torch.zeros(3, device=rec.device, dtype=torch.int32)           # n_sel, n_seg, status of the stream's header
+        with stage("region_select"):
+            sel = ops.region_select(rec[0], comp.c[0], box, G, halo, self.margin, counts=head[:2])
+            if fast:
+                models.range_decode_split_list(None, comp.p_bytes[0], comp.p_nbytes, L, G * d, S * d, None, 0, status=head[2:])
+            n_sel, n_seg, status = (int(v) for v in head.cpu())               # THE synchronisation
+        err = models.split_status_error("decompress_region", [status])
+        if err is not None:
+            raise err
+        patch_idx, segments = sel.patch_idx[:n_sel], sel.seg_idx[:n_seg].to(torch.int64)
+        region = lambda pts: Region(pts, patch_idx, segments, -(-S // G))
+        if n_sel == 0:
+            return region(torch.empty(0, 3, device=rec.device, dtype=torch.float32))
+        if not fast:
+            return region(self.decompress(comp, S)[0].view(S, self.k, 3)[patch_idx].reshape(-1, 3))
+        with stage("prob"):
+            cdf_int = self.prob.run_segments(rec[0], sel.seg_idx, n_seg, G)
+        with stage("range_decode"):
+            q, _ = models.range_decode_split_list(cdf_int, comp.p_bytes[0], comp.p_nbytes, L, G * d, S * d, sel.seg_idx, n_seg)
+        with stage("gather"):
+            q_sel = ops.index_points(q.view(1, n_seg * G, d), sel.rows[:n_sel].view(1, n_sel))
+            c_sel = ops.index_points(rec, patch_idx.view(1, n_sel))
+        scale = float((S * self.k / self.N0) ** (1 / 3))                      # of the WHOLE cloud, as decompress
+        with stage("ae_decode"):
+            pts = self.ae.decode(q_sel.view(n_sel, d), c_sel.view(n_sel, 3), comp.c[:, :3].contiguous(), comp.c[:, 3].contiguous(),
+                                 S=n_sel, scale=scale, margin=self.margin, matmul=self.decoder_matmul)
+        return region(pts.view(-1, 3))
+
+
+@dataclasses.dataclass
+class Region:
+    """What Codec.decompress_region returns.  All tensors on the device."""
+    points: torch.Tensor          # (n_sel*k, 3) f32  the selected patches' points, in patch order
+    patch_idx: torch.Tensor       # (n_sel,) i64      ascending
+    segments: torch.Tensor        # (n_seg,) i64      the touched segments of the split stream, ascending
+    n_segments_total: int         # ceil(S / G)
+
 
 def d1_psnr(orig, recon, search=None, index=None):
     """eval.py:43-98 D1 (point-to-point) PSNR, batched: 10*log10(diag^2 / mean_recon min_orig |.|^2),

@@ -556,6 +556,31 @@ class ConditionalProbabilityModel(nn.Module):
         _lib.call(fn, x.data_ptr(), B, S, self.d, self.L, self._blob.data_ptr(), *ptrs, _stream())
         return r
 
+    def run_segments(self, sampled_xyz, seg_idx, n_seg, G):
+        """The integer CDF of the listed segments' rows only (region decode): sampled_xyz (S,3) or (1,S,3) the centres of ONE cloud,
+        seg_idx (>= n_seg) i32 on the device, ascending segments of G patches, n_seg a host int -> cdf_int (n_seg*G, d, L+1) i32
+        whose row r is row seg_idx[r // G] * G + r % G of run(...)["cdf_int"][0], bit for bit (the rows past S of a ragged last
+        segment hold row S - 1's table and are not to be read).  pccx_prob_feature (pass 1 over up to 64 workgroups, pass 1b) then
+        pccx_prob_rows; the fused kernel's shapes only (fused_ok(S)), anything else raises: the caller falls back to run()."""
+        x = _f32c(sampled_xyz, "ConditionalProbabilityModel.run_segments").reshape(-1, 3)
+        S, n_seg, G = x.shape[0], int(n_seg), int(G)
+        if not self.fused_ok(S):
+            raise _lib.PccxError(f"run_segments: the fused probability kernel does not cover d={self.d}, L={self.L}, S={S}")
+        if G < 1 or not 0 <= n_seg <= -(-S // G) or seg_idx.dtype != torch.int32 or seg_idx.numel() < n_seg:
+            raise ValueError(f"run_segments: n_seg={n_seg} segments of G={G} patches from an int32 list of {seg_idx.numel()} for S={S}")
+        if self._blob is None or self._blob.device != x.device:
+            self.pack(x.device)
+        out = torch.empty(n_seg * G, self.d, self.L + 1, device=x.device, dtype=torch.int32)
+        if n_seg == 0:
+            return out
+        lib = _lib.load()
+        ws = workspace("prob_feature", int(lib.pccx_prob_feature_workspace_floats(S)) + 512, x.device)
+        feature = ws[:512]                                   # the workspace's base is 16-byte aligned
+        _lib.call("pccx_prob_feature", x.data_ptr(), S, self._blob.data_ptr(), ws[512:].data_ptr(), feature.data_ptr(), _stream())
+        _lib.call("pccx_prob_rows", x.data_ptr(), S, self.d, self.L, self._blob.data_ptr(), feature.data_ptr(),
+                  seg_idx.contiguous().data_ptr(), n_seg, G, out.data_ptr(), _stream())
+        return out
+
     def _outputs(self, want, B, S, device):
         """The wanted ones of pmf / cdf / cdf_int, and the three pointers the kernels take (null for an output not wanted)."""
         kinds = {"pmf": (self.L, torch.float32), "cdf": (self.L + 1, torch.float32), "cdf_int": (self.L + 1, torch.int32)}
@@ -685,11 +710,38 @@ def range_decode_split(cdf_int, bytes_, nbytes, L, seg_sym, check=True):
               _stream())
     if not check:
         return q, status
-    st = status.cpu().numpy()
-    if st.any():
-        raise _lib.PccxError("range_decode_split: " + "; ".join(
-            f"clouds {[int(b) for b in (st == code).nonzero()[0]]}: {why}" for code, why in SPLIT_STATUS.items() if (st == code).any()))
+    err = split_status_error("range_decode_split", status.cpu().numpy())
+    if err is not None:
+        raise err
     return q
+
+
+def split_status_error(who, st):
+    """The PccxError range_decode_split raises for per-cloud status words ``st`` (a host sequence), or None when all are 0."""
+    import numpy as np
+    st = np.asarray(st).reshape(-1)
+    if not st.any():
+        return None
+    return _lib.PccxError(f"{who}: " + "; ".join(
+        f"clouds {[int(b) for b in (st == code).nonzero()[0]]}: {why}" for code, why in SPLIT_STATUS.items() if (st == code).any()))
+
+
+def range_decode_split_list(cdf_int, bytes_, nbytes, L, seg_sym, nsym, seg_idx, n_list, status=None):
+    """range_decode_split for the listed segments of ONE cloud: cdf_int (n_list*seg_sym, L+1) i32 compact table rows (segment j of
+    the list at rows j*seg_sym ...), bytes_ (cap,) or (1,cap) u8 the cloud's file, nbytes (1,) i32, nsym the cloud's symbol count,
+    seg_idx i32 on the device (the first n_list entries, ascending segment numbers), n_list a host int ->
+    (latent_q (n_list*seg_sym,) f32 compact, status (1,) i32 on the device, as range_decode_split(check=False) gives it).  No byte of
+    an unlisted segment is read.  n_list = 0 runs the header check alone.  status: an int32 device tensor to write instead of a new one."""
+    bytes_ = bytes_.contiguous().reshape(-1)
+    n_list, seg_sym, nsym = int(n_list), int(seg_sym), int(nsym)
+    q = torch.empty(n_list * seg_sym, device=bytes_.device, dtype=torch.float32)
+    if status is None:
+        status = torch.zeros(1, device=bytes_.device, dtype=torch.int32)
+    ws = _split_workspace(1, nsym, seg_sym, bytes_.device)
+    _lib.call("pccx_range_decode_split_list", cdf_int.contiguous().data_ptr() if n_list else None, bytes_.data_ptr(), bytes_.numel(),
+              nbytes.to(torch.int32).contiguous().data_ptr(), nsym, seg_sym, int(L), seg_idx.contiguous().data_ptr() if n_list else None,
+              n_list, q.data_ptr() if n_list else None, status.data_ptr(), ws.data_ptr(), _stream())
+    return q, status
 
 
 def split_stream_status(data, nsym, seg_sym):

@@ -98,7 +98,59 @@ def denormalize(pc, center, longest, margin=0.01):
     return out
 
 
-FPS_COOP_POINTS_PER_WORKGROUP = 16384     # 1024 threads x 16 points in registers (csrc/geometry.hip, fps_coop_kernel)
+REGION_MAX_S = 8192                       # pccx_region_select: one workgroup scans a cloud's centres (csrc/region.hip)
+RegionSelection = collections.namedtuple("RegionSelection", ["patch_idx", "seg_idx", "rows", "counts"])
+
+
+def check_box(box, halo=0.0):
+    """(six floats lo xyz + hi xyz, halo) of a region box ``(lo, hi)``: ValueError naming the argument unless the box is six finite
+    floats with lo <= hi on every axis and halo is finite and not negative.  Host only."""
+    import math
+    try:
+        lo, hi = (list(side) for side in box)
+        vals = [float(v) for v in lo] + [float(v) for v in hi]
+    except (TypeError, ValueError):
+        raise ValueError(f"box must be (lo, hi), two triples of floats, got {box!r}") from None
+    if len(lo) != 3 or len(hi) != 3 or not all(math.isfinite(v) for v in vals) or any(vals[a] > vals[3 + a] for a in range(3)):
+        raise ValueError(f"box must be six finite floats with lo <= hi on every axis, got {box!r}")
+    try:
+        h = float(halo)
+    except (TypeError, ValueError):
+        raise ValueError(f"halo must be a finite float >= 0, got {halo!r}") from None
+    if not math.isfinite(h) or h < 0:
+        raise ValueError(f"halo must be a finite float >= 0, got {halo!r}")
+    return vals, h
+
+
+def region_select(centres, c4, box, G, halo=0.0, margin=0.01, counts=None):
+    """pccx_region_select: the patches of ONE cloud whose denormalised centre (ops.denormalize's float) lies in the closed box
+    ``(lo, hi)`` grown by ``halo``, and the segments of G patches that hold one.  centres (S,3) decoded centres, c4 (4,) the cloud's
+    centre xyz + longest side.  -> RegionSelection of device tensors, never read back here: patch_idx (S) i64 and seg_idx
+    (ceil(S/G)) i32, ascending, of which the first counts[0] / counts[1] are valid; rows (S) i64, each selected patch's row among
+    the touched segments' patches; counts (2) i32 (``counts``: a dense int32 device tensor of two entries to write instead)."""
+    import ctypes
+    vals, h = check_box(box, halo)
+    x = _f32c(centres, "region_select")
+    S = x.shape[0]
+    if x.dim() != 2 or x.shape[1] != 3 or not 1 <= S <= REGION_MAX_S:
+        raise ValueError(f"region_select: centres must be (S,3) with 1 <= S <= {REGION_MAX_S}, got {tuple(x.shape)}")
+    G = int(G)
+    if G < 1:
+        raise ValueError(f"region_select: G must be >= 1, got {G}")
+    c4 = _f32c(c4.reshape(4), "region_select.c4")
+    if counts is None:
+        counts = torch.empty(2, device=x.device, dtype=torch.int32)
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (2,) or not counts.is_contiguous() or counts.device != x.device:
+        raise ValueError("region_select: counts must be a dense (2,) int32 tensor on the centres' device")
+    sel = RegionSelection(torch.empty(S, device=x.device, dtype=torch.int64), torch.empty(-(-S // G), device=x.device, dtype=torch.int32),
+                          torch.empty(S, device=x.device, dtype=torch.int64), counts)
+    box_c = (ctypes.c_float * 6)(*vals)
+    _lib.call("pccx_region_select", x.data_ptr(), S, c4.data_ptr(), float(margin), ctypes.addressof(box_c), h, G,
+              sel.patch_idx.data_ptr(), sel.seg_idx.data_ptr(), sel.rows.data_ptr(), sel.counts.data_ptr(), _stream())
+    return sel
+
+
+FPS_COOP_POINTS_PER_WORKGROUP = 16384    # 1024 threads x 16 points in registers (csrc/geometry.hip, fps_coop_kernel)
 FPS_COOP_MAX_WORKGROUPS = 64              # per cloud: the flat barrier of pccx_fps_coop is sized for that many arrivals
 FPS_COOP_SPREAD = 2                       # "auto" aims at this many times the least G, i.e. 8 points per thread (DESIGN.md 4.5)
 
