@@ -527,6 +527,54 @@ PCCX_API int pccx_range_decode_split_list(const int32_t *cdf_int, const uint8_t 
                                           int seg_sym, int L, const int32_t *seg_idx, int n_list, float *latent_q, int32_t *status,
                                           void *workspace, void *stream);
 
+/* ---- entry-point index of the single stream: parallel and region decode of the reference's own .p.bin ------
+ * The stream is pccx_range_encode's, byte for byte.  A sidecar <name>.p.idx holds the coder's state at every seg_sym-th symbol, so
+ * that one wave per segment can enter the one stream.  Little-endian (csrc/entry_index.h, one statement for host and device):
+ *     "PXI1" | nsym u32 | seg_sym u32 | P u32 | P entries {low u32, high u32, pos u32},  P = ceil(nsym / seg_sym)
+ * pos bits 0..30 = the stream bits the decoder has shifted in beyond its first 32 when it reaches symbol p*seg_sym, bit 31 = an
+ * underflow run is pending there; the decoder's value is the 32 stream bits at pos with bit 31 inverted under that flag.  Entry 0 is
+ * {0, 0xFFFFFFFF, 0}.  pccx_range_index_bytes(nsym, seg_sym) = 16 + 12 P (host only); index rows on the device are that many bytes
+ * each and 4-byte aligned.  Limits and refusals are the split path's (L in 2 .. 63, seg_sym <= pccx_range_split_max_seg_sym(L),
+ * P <= 8192, B <= 65535), and a stream row of at most 2^27 bytes.
+ * pccx_range_encode_indexed: pccx_range_encode (either of its two kernels, the same choice) that also writes row b of index.  The
+ *   stream bytes and nbytes are pccx_range_encode's.
+ * pccx_range_index_build: the index of existing streams (files the reference wrote): the sequential decoder (either kernel, as
+ *   pccx_range_decode chooses) run once, storing its state at every boundary.  latent_q: NULL, or (B,nsym) to receive the symbols too.
+ *   Bit for bit the entries the encoder writes for the same stream.
+ * pccx_range_decode_indexed: a check kernel writes status[b] and, into workspace (pccx_range_index_workspace_bytes(B, nsym, seg_sym)
+ *   bytes, host only), four words per segment; then a P x B grid, one wave per segment, each started from its entry, staging only the
+ *   bytes from its position to the next entry's plus the 32-bit window (at most 2*seg_sym + 24).  index (B, idx_stride) bytes;
+ *   idx_nbytes: NULL (every row holds idx_stride bytes) or (B) byte counts, clamped to [0, idx_stride].  Status: 0 ok; 1 shorter than
+ *   its header, wrong magic, or not 16 + 12 P bytes; 2 nsym / seg_sym / P disagree with the call; 3 a position below the one before;
+ *   4 a position beyond 8 * nbytes; 5 consecutive positions more than 8 * (2*seg_sym + 16) bits apart; 6 an entry outside the coder's
+ *   post-renormalisation states (low < 2^31 <= high and not (low >= 2^30 and high < 3 * 2^30)), or entry 0 not the initial state.
+ *   A cloud whose status is not 0 decodes every segment as an empty stream from the initial state, and no byte of its stream is
+ *   read.  A sidecar that passes and is wrong decodes wrong symbols; no address leaves the staged bytes.
+ * pccx_range_decode_indexed_list: the same for the listed segments of ONE cloud, as pccx_range_decode_split_list: index = the
+ *   idx_bytes bytes of the sidecar, compact table rows and outputs, n_list = 0 runs the check alone.  No byte outside the listed
+ *   segments' spans is read.
+ * pccx_entry_index_check_host: the same check on host bytes, no GPU call. */
+PCCX_API size_t pccx_range_index_bytes(int nsym, int seg_sym);
+PCCX_API size_t pccx_range_index_workspace_bytes(int B, int nsym, int seg_sym);
+PCCX_API int pccx_entry_index_check_host(const uint8_t *index, int64_t idx_bytes, int64_t stream_bytes, int nsym, int seg_sym);
+PCCX_API int pccx_range_encode_indexed(const int32_t *cdf_int, const float *latent_q, int B, int nsym, int seg_sym, int L,
+                                       uint8_t *out, int cap, int32_t *nbytes, uint8_t *index, void *stream);
+PCCX_API int pccx_range_index_build(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes, int B, int nsym,
+                                    int seg_sym, int L, uint8_t *index, float *latent_q, void *stream);
+PCCX_API int pccx_range_decode_indexed(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes,
+                                       const uint8_t *index, int idx_stride, const int32_t *idx_nbytes, int B, int nsym, int seg_sym,
+                                       int L, float *latent_q, int32_t *status, void *workspace, void *stream);
+PCCX_API int pccx_range_decode_indexed_list(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes,
+                                            const uint8_t *index, int idx_bytes, int nsym, int seg_sym, int L, const int32_t *seg_idx,
+                                            int n_list, float *latent_q, int32_t *status, void *workspace, void *stream);
+/* The sidecars of B clouds, <dir>/<name>.p.idx, by the host threads of pccx_write_streams_host (names as there).  Write: row b of
+ * index_host (B, idx_stride), whole.  Read: the file into row b (a longer file is an error, a shorter one leaves zeros behind it)
+ * and its length into idx_nbytes[b]; a missing file is an error. */
+PCCX_API int pccx_write_index_host(const void *index_host, int B, int idx_stride, const char *dir, const char *names,
+                                   const int64_t *name_off, int threads);
+PCCX_API int pccx_read_index_host(void *index_host, int B, int idx_stride, int32_t *idx_nbytes, const char *dir, const char *names,
+                                  const int64_t *name_off, int threads);
+
 /* torchac's float -> 16-bit integer CDF conversion (torchac 0.9.3 _convert_to_int_and_normalize with
  * needs_normalization=True, the first step of encode_float_cdf / decode_float_cdf, compress.py:136, decompress.py:93):
  * cdf (nrows, Lp) f32 in [0,1] -> cdf_int (nrows, Lp) int32 holding 16-bit values. */

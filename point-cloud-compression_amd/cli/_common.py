@@ -83,5 +83,9 @@ def add_codec_flags(parser):
                         help="Write / read .p.bin in the split form: segments of G patches, each range-coded on its own behind a directory "
                              "of segment lengths, coded and decoded in parallel (whole rooms; 64 is the measured choice).  0 = the "
                              "reference's single stream.  Both sides must pass the same G; a split .p.bin is not a file the reference reads.")
+    parser.add_argument('--p-index', type=int, default=0, metavar='G',
+                        help="Keep .p.bin the reference's single stream and write / read an entry-point index <name>.p.idx beside it: the "
+                             "coder's state every G patches (12 bytes each), so that decompress.py decodes the one stream with one wave "
+                             "per G patches and --region can enter it.  0 = no index.  Excludes --p-split.")
     parser.add_argument('--batch', type=int, default=256, help='Clouds per launch sequence.')
     parser.add_argument('--seed', type=int, default=11, help='Seed of the per-file FPS start index.')

@@ -29,9 +29,9 @@ def main():
     ae, prob = _common.load_models(args)
     cd = codec.Codec(ae, prob, K=args.K, ALPHA=args.ALPHA, N0=args.N0, octree_mode=args.octree_mode, knn_search=args.knn_search,
                      max_centres=codec.OCTREE_WIDE_MAX_S,             # whole clouds up to 8192 patches: 1048576 points at K = 256
-                     p_split=args.p_split or None)
+                     p_split=args.p_split or None, p_index=args.p_index or None)
     mine = set(dist.shard_indices(len(files), rank, world))                                      # file i -> rank i mod world
-    times, todo, bits, points = [], [t for t in enumerate(files) if t[0] in mine], 0, 0
+    times, todo, bits, points, index_bits = [], [t for t in enumerate(files) if t[0] in mine], 0, 0, 0
     with torch.no_grad():
         while todo:
             clouds = [(i, f, plyio.read_point_cloud(f)) for i, f in todo[:args.batch]]          # outside the timed window
@@ -45,16 +45,20 @@ def main():
             t0 = time.time()                                                                     # compress.py:85
             comp = cd.compress(pc, starts)
             # ONE D2H of the batch's packed streams, then the library's host threads cut the three files of every cloud out of it
-            # (pccx_write_streams_host): <name>.p.bin / .s.bin / .c.bin, the bytes of compress.py:139-152
+            # (pccx_write_streams_host): <name>.p.bin / .s.bin / .c.bin, the bytes of compress.py:139-152; with --p-index also <name>.p.idx
             nbytes = comp.write_files(args.compressed_path, [os.path.split(f)[1] for _, f, _ in batch])
             times += [(time.time() - t0) / len(batch)] * len(batch)                              # compress.py:154
             bits += 8 * nbytes
+            index_bits += int(comp.index_bits().sum())                                           # derived from the shape: no transfer
             points += n0 * len(batch)
-    g = dist.gather_summaries([bits, points, 0.0, 0.0, len(times), float(np.sum(times))], _common.summary_device(args))
+    # the six-slot vector of dist.SUMMARY_FIELDS; this tool has no PSNR to report, so slot 2 ("psnr_sum") carries the sidecars' bits.
+    # Summed over ranks here, never passed to dist.reduce_summaries.
+    g = dist.gather_summaries([bits, points, index_bits, 0.0, len(times), float(np.sum(times))], _common.summary_device(args))
     if rank == 0 and float(g[:, 4].sum()) > 0:
         tot = g.sum(dim=0)
         print(f"Done! Execution time: {round(float(tot[5] / tot[4]), 5)}s per point cloud." +
-              (f" ({int(tot[4])} clouds on {world} ranks, {float(tot[0] / tot[1]):.4f} bpp)" if world > 1 else ""))
+              (f" ({int(tot[4])} clouds on {world} ranks, {float(tot[0] / tot[1]):.4f} bpp)" if world > 1 else "") +
+              (f" Files {float(tot[0] / tot[1]):.4f} bpp, index {float(tot[2] / tot[1]):.4f} bpp beside them." if args.p_index else ""))
     _common.finish_ranks(world)
 
 

@@ -25,20 +25,27 @@ parser.add_argument('--bin-ply-suffix', action='store_true',
                     help="Write <name>.bin.ply (what eval.py:172 looks for) instead of <name> (decompress.py:121).")
 parser.add_argument('--region', type=float, nargs=6, default=None, metavar=('X0', 'Y0', 'Z0', 'X1', 'Y1', 'Z1'),
                     help="Decode only the patches whose centre lies in this box of the cloud's original coordinates "
-                         "(Codec.decompress_region); needs --p-split and --octree-mode full.")
+                         "(Codec.decompress_region); needs --p-split or --p-index, and --octree-mode full.")
 parser.add_argument('--region-halo', type=float, default=0.0, help="Grow the --region box by this much on every side when selecting patches.")
+parser.add_argument('--build-index', action='store_true',
+                    help="With --p-index: where <name>.p.idx is missing, build it from the .p.bin first (one sequential decode) and write it.")
 parser.add_argument('--crop', action='store_true', help="With --region: drop the decoded points outside the box (the halo does not count).")
 
 
 def main():
     args = parser.parse_args()
     if args.region is not None:
-        if not args.p_split:
-            raise SystemExit("--region needs --p-split G (a split .p.bin is what can be entered at a segment)")
+        if not args.p_split and not args.p_index:
+            raise SystemExit("--region needs --p-split G or --p-index G (a stream is entered at a segment through the split .p.bin's "
+                             "directory or the single stream's entry-point index)")
         if args.octree_mode != 'full':
             raise SystemExit("--region needs --octree-mode full")
     elif args.crop or args.region_halo:
         raise SystemExit("--crop / --region-halo need --region")
+    if args.p_split and args.p_index:
+        raise SystemExit("--p-index and --p-split exclude each other")
+    if args.build_index and not args.p_index:
+        raise SystemExit("--build-index needs --p-index G")
     print(f"Processing on device (gpu/cpu): {args.device}")
     os.makedirs(args.decompressed_path, exist_ok=True)
     names = sorted(os.path.split(x)[1][:-6] for x in glob(os.path.join(args.compressed_path, '*.s.bin')))
@@ -46,8 +53,8 @@ def main():
     names = [names[i] for i in dist.shard_indices(len(names), rank, world)]                      # file i -> rank i mod world
     ae, prob = _common.load_models(args)
     cd = codec.Codec(ae, prob, K=args.K, ALPHA=args.ALPHA, N0=args.N0, octree_mode=args.octree_mode, max_centres=codec.OCTREE_WIDE_MAX_S,
-                     p_split=args.p_split or None)
-    times = []
+                     p_split=args.p_split or None, p_index=args.p_index or None)
+    times, index_bits, points = [], 0, 0
     with torch.no_grad():
         for b0 in range(0, len(names), args.batch):
             chunk = names[b0:b0 + args.batch]
@@ -87,11 +94,41 @@ def main():
                     if nsym != int(S) * args.d:
                         raise SystemExit(f"{n}.p.bin holds {nsym} symbols but {n}.s.bin gives S={int(S)} patches of d={args.d}: "
                                          + models.SPLIT_STATUS[2])
+            side = None
+            if args.p_index:
+                # the sidecars as the three streams: per distinct S (their size follows from it) ONE threaded read of every file
+                # (pccx_read_index_host), the check on the host bytes against each .p.bin's length, ONE upload.  A missing one is built
+                # first with --build-index (the sequential decoder once) and written beside the three files.
+                side, seg = {}, args.p_index * args.d
+                p_n_host = p_n.cpu().numpy()
+                for S in sorted(set(S_of.tolist())):
+                    js = np.flatnonzero(S_of == S).tolist()
+                    for j in js:
+                        n = chunk[j]
+                        if os.path.exists(os.path.join(args.compressed_path, n + '.p.idx')):
+                            continue
+                        if not args.build_index:
+                            raise SystemExit(f"{n}.p.idx is missing: pass --build-index to make it from {n}.p.bin, or compress with --p-index {args.p_index}")
+                        one = codec.Compressed(s_b[j:j + 1], s_n[j:j + 1], p_b[j:j + 1], p_n[j:j + 1], c[j:j + 1], 0)
+                        cd.build_index(one, int(S))
+                        codec.write_index(one.p_index.cpu().contiguous(), args.compressed_path, [n])
+                        print(f"{n}: built {n}.p.idx ({one.p_index.shape[1]} bytes)")
+                    idx, cnt = codec.read_index(args.compressed_path, [chunk[j] for j in js], models.index_bytes(int(S) * args.d, seg))
+                    for r, j in enumerate(js):
+                        why = models.index_status(bytes(idx[r, :int(cnt[r])].numpy()), int(p_n_host[j]), int(S) * args.d, seg)
+                        if why:
+                            raise SystemExit(f"{chunk[j]}.p.idx is not the index of {chunk[j]}.p.bin at --p-index {args.p_index}: {models.INDEX_STATUS[why]}")
+                    side[int(S)] = (idx.to(args.device, non_blocking=True), {j: r for r, j in enumerate(js)})   # whole rows: the check passed
+                    index_bits += 8 * int(cnt.sum())
+                    points += int(S) * args.K // args.ALPHA * len(js)
             clouds = [None] * len(chunk)
             if args.region is not None:
                 box = (args.region[:3], args.region[3:])
                 for j, n in enumerate(chunk):                                                    # one decompress_region call per file
                     comp = codec.Compressed(s_b[j:j + 1], s_n[j:j + 1], p_b[j:j + 1], p_n[j:j + 1], c[j:j + 1], 0)
+                    if side is not None:
+                        rows, at = side[int(S_of[j])]
+                        comp.p_index = rows[at[j]:at[j] + 1]
                     reg = cd.decompress_region(comp, int(S_of[j]), box, halo=args.region_halo)
                     pts = reg.points
                     if args.crop:
@@ -106,6 +143,8 @@ def main():
                 for S in sorted(set(S_of.tolist())):                                             # one launch sequence per S
                     sel = torch.from_numpy(np.flatnonzero(S_of == S)).to(args.device)
                     comp = codec.Compressed(s_b[sel], s_n[sel], p_b[sel], p_n[sel], c[sel], 0)
+                    if side is not None:
+                        comp.p_index = side[int(S)][0]                                           # rows in the order of `sel`: ascending j
                     pc = cd.decompress(comp, S=int(S)).cpu().numpy()
                     for j, cloud in zip(sel.cpu().tolist(), pc):
                         clouds[j] = cloud
@@ -114,10 +153,13 @@ def main():
                 if cloud is None:                                                                # --region: nothing of this file in the box
                     continue
                 plyio.save_point_cloud(cloud, os.path.join(args.decompressed_path, n + ('.bin.ply' if args.bin_ply_suffix else '')))
-    g = dist.gather_summaries([0.0, 0.0, 0.0, 0.0, len(times), float(np.sum(times))], _common.summary_device(args))
+    # the six-slot vector of dist.SUMMARY_FIELDS; this tool has no PSNR to report, so slot 2 ("psnr_sum") carries the sidecars' bits and
+    # slot 1 the points they index.  Summed over ranks here, never passed to dist.reduce_summaries.
+    g = dist.gather_summaries([0.0, points, index_bits, 0.0, len(times), float(np.sum(times))], _common.summary_device(args))
     if rank == 0 and float(g[:, 4].sum()) > 0:
         tot = g.sum(dim=0)
-        print(f"Done! Execution time: {round(float(tot[5] / tot[4]), 5)}s per point cloud." + (f" ({int(tot[4])} clouds on {world} ranks)" if world > 1 else ""))
+        print(f"Done! Execution time: {round(float(tot[5] / tot[4]), 5)}s per point cloud." + (f" ({int(tot[4])} clouds on {world} ranks)" if world > 1 else "")
+              + (f" Index {float(tot[2] / tot[1]):.4f} bpp beside the files." if args.p_index and float(tot[1]) > 0 else ""))
     _common.finish_ranks(world)
 
 

@@ -269,6 +269,59 @@ extern "C" int pccx_stream_sizes_host(int B, const char *dir, const char *names,
     return PCCX_OK;
 }
 
+// The sidecars of the entry-point index (entry_index.h), one <name>.p.idx per cloud, beside the three files and by the same threads.
+// They are rows of their own (B, idx_stride): the packed layout of the three streams does not change.
+extern "C" int pccx_write_index_host(const void *index_host, int B, int idx_stride, const char *dir, const char *names, const int64_t *name_off,
+                                     int threads)
+{
+    PCCX_CHECK_ARG(index_host && dir && names && name_off, "pccx_write_index_host: null pointer");
+    PCCX_CHECK_ARG(B >= 0 && idx_stride >= 0, "pccx_write_index_host: negative size");
+    const uint8_t *base = (const uint8_t *)index_host;
+    const Names nm{dir, names, name_off};
+    std::mutex emu;
+    std::string first;
+    Pool::get().run(B, threads > 0 ? threads : default_threads(), [&](int b) {
+        std::string err;
+        if (!write_all(nm.path(b, ".p.idx").c_str(), base + (size_t)b * idx_stride, (size_t)idx_stride, err)) {
+            std::lock_guard<std::mutex> g(emu);
+            if (first.empty()) first = err;
+        }
+    });
+    if (!first.empty()) {
+        pccx_set_error("pccx_write_index_host: %s", first.c_str());
+        return PCCX_ERR_ARG;
+    }
+    return PCCX_OK;
+}
+
+extern "C" int pccx_read_index_host(void *index_host, int B, int idx_stride, int32_t *idx_nbytes, const char *dir, const char *names,
+                                    const int64_t *name_off, int threads)
+{
+    PCCX_CHECK_ARG(index_host && idx_nbytes && dir && names && name_off, "pccx_read_index_host: null pointer");
+    PCCX_CHECK_ARG(B >= 0 && idx_stride >= 0, "pccx_read_index_host: negative size");
+    uint8_t *base = (uint8_t *)index_host;
+    const Names nm{dir, names, name_off};
+    std::mutex emu;
+    std::string first;
+    Pool::get().run(B, threads > 0 ? threads : default_threads(), [&](int b) {
+        std::string err;
+        const long n = read_all(nm.path(b, ".p.idx").c_str(), base + (size_t)b * idx_stride, (size_t)idx_stride, err);
+        if (n < 0) {
+            idx_nbytes[b] = 0;
+            std::lock_guard<std::mutex> g(emu);
+            if (first.empty()) first = err;
+            return;
+        }
+        idx_nbytes[b] = (int32_t)n;
+        memset(base + (size_t)b * idx_stride + n, 0, (size_t)idx_stride - (size_t)n);
+    });
+    if (!first.empty()) {
+        pccx_set_error("pccx_read_index_host: %s", first.c_str());
+        return PCCX_ERR_ARG;
+    }
+    return PCCX_OK;
+}
+
 extern "C" size_t pccx_streams_packed_bytes(int B, int s_stride, int p_cap)
 {
     if (B < 0 || s_stride < 0 || p_cap < 0) return 0;

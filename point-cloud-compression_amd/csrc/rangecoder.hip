@@ -12,6 +12,7 @@
 // per segment.
 #include "common.h"
 #include "split_stream.h"
+#include "entry_index.h"
 
 struct BitWriter {
     uint8_t *buf;
@@ -43,18 +44,57 @@ struct BitWriter {
     }
 };
 
-__global__ void range_encode_kernel(const int32_t *__restrict__ cdf_int, const float *__restrict__ latent_q, int B, int nsym,
-                                    int Lp, int sym_offset, uint8_t *__restrict__ out, int cap, int32_t *__restrict__ nbytes)
+// The entry of the index (entry_index.h) a coder is at: its interval, the bits behind it (emitted plus pending on the encoder,
+// shifted in beyond the first 32 on the decoder -- the same number) and whether an underflow run is pending.  One 12-byte store.
+// Outside the coder's contract -- a table with a zero-width symbol can drive high below low (see `fix` in rc_encode_wave) -- the state
+// is recorded as it is; such an entry fails pccx_index_state_ok, so the indexed decoder refuses that cloud's sidecar with status 6
+// where the sequential decoder returns symbols (which are not the coded ones either: such a stream does not decode to its input).
+__device__ __forceinline__ void rc_record(uint32_t *entry, unsigned low, unsigned high, unsigned long long bits, bool pending)
+{
+    entry[0] = low;
+    entry[1] = high;
+    entry[2] = (unsigned)(bits < 0x7FFFFFFFull ? bits : 0x7FFFFFFFull) | (pending ? PCCX_INDEX_FLAG : 0u);
+}
+// The 16 fixed bytes of a sidecar at `index` (4-byte aligned).
+__device__ __forceinline__ void rc_index_header(uint32_t *index, int nsym, int seg_sym)
+{
+    index[0] = 0x31495850u;                                            // "PXI1", little-endian
+    index[1] = (unsigned)nsym;
+    index[2] = (unsigned)seg_sym;
+    index[3] = (unsigned)pccx_index_segments(nsym, seg_sym);
+}
+
+// One lane per cloud.  REC: also write the cloud's sidecar of idx_stride bytes at index + b * idx_stride (the header and the entry at
+// every seg_sym boundary); the stream does not depend on it.
+template <bool REC>
+__device__ __forceinline__ void rc_encode_lane(const int32_t *__restrict__ cdf_int, const float *__restrict__ latent_q, int B, int nsym,
+                                               int Lp, int sym_offset, uint8_t *__restrict__ out, int cap, int32_t *__restrict__ nbytes,
+                                               int seg_sym, uint8_t *__restrict__ index, int idx_stride)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
+    uint32_t *entry = nullptr;
+    if (REC) {
+        entry = (uint32_t *)(index + (size_t)b * idx_stride);
+        rc_index_header(entry, nsym, seg_sym);
+        entry += PCCX_INDEX_HEADER_BYTES / 4;
+    }
     BitWriter w{out + (size_t)b * cap, cap, 0, 0u, 0};
     unsigned low = 0u, high = 0xFFFFFFFFu;
     unsigned long long pending = 0;
     const int max_symbol = Lp - 2;
     const int32_t *c = cdf_int + (size_t)b * nsym * Lp;
     const float *q = latent_q + (size_t)b * nsym;
-    for (int i = 0; i < nsym; ++i, c += Lp) {
+    // Without REC one pass over all symbols; with it one pass per segment (seg_sym >= 1: P passes), the entry stored in front of
+    // each, so that the symbol loop itself carries no test for a boundary.
+    int i = 0, stop = REC ? 0 : nsym;
+    do {
+    if (REC && i < nsym) {
+        rc_record(entry, low, high, (unsigned long long)w.n * 8ull + (unsigned long long)w.count + pending, pending > 0);
+        entry += PCCX_INDEX_ENTRY_BYTES / 4;
+        stop = nsym - i < seg_sym ? nsym : i + seg_sym;
+    }
+    for (; i < stop; ++i, c += Lp) {
         int s = (int)q[i] + sym_offset;                       // latent_quantized.to(int16) + L//2 (compress.py:135)
         s = s < 0 ? 0 : (s > max_symbol ? max_symbol : s);
         const unsigned long long span = (unsigned long long)high - (unsigned long long)low + 1ull;
@@ -77,6 +117,7 @@ __global__ void range_encode_kernel(const int32_t *__restrict__ cdf_int, const f
                 break;
         }
     }
+    } while (REC && i < nsym);
     ++pending;
     if (low < 0x40000000u) w.bit_pending(0, pending);
     else w.bit_pending(1, pending);
@@ -84,12 +125,37 @@ __global__ void range_encode_kernel(const int32_t *__restrict__ cdf_int, const f
     nbytes[b] = w.n <= cap ? w.n : -w.n;                      // negative: capacity exceeded
 }
 
-__global__ void range_decode_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in, int stride,
-                                    const int32_t *__restrict__ nbytes, int B, int nsym, int Lp, int sym_offset,
-                                    float *__restrict__ latent_q)
+__global__ void range_encode_kernel(const int32_t *__restrict__ cdf_int, const float *__restrict__ latent_q, int B, int nsym,
+                                    int Lp, int sym_offset, uint8_t *__restrict__ out, int cap, int32_t *__restrict__ nbytes)
+{
+    rc_encode_lane<false>(cdf_int, latent_q, B, nsym, Lp, sym_offset, out, cap, nbytes, 0, nullptr, 0);
+}
+
+__global__ void range_encode_indexed_kernel(const int32_t *__restrict__ cdf_int, const float *__restrict__ latent_q, int B, int nsym,
+                                            int Lp, int sym_offset, uint8_t *__restrict__ out, int cap, int32_t *__restrict__ nbytes,
+                                            int seg_sym, uint8_t *__restrict__ index, int idx_stride)
+{
+    rc_encode_lane<true>(cdf_int, latent_q, B, nsym, Lp, sym_offset, out, cap, nbytes, seg_sym, index, idx_stride);
+}
+
+// One lane per cloud.  REC: write the cloud's sidecar as rc_encode_lane does (the decoder passes through the encoder's states), and
+// latent_q may then be null.
+template <bool REC>
+__device__ __forceinline__ void rc_decode_lane(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in, int stride,
+                                               const int32_t *__restrict__ nbytes, int B, int nsym, int Lp, int sym_offset,
+                                               float *__restrict__ latent_q, int seg_sym, uint8_t *__restrict__ index, int idx_stride)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
+    uint32_t *entry = nullptr;
+    int next = 0;
+    unsigned long long shifted = 0;                           // REC: bits taken beyond the first 32; an underflow run is pending
+    bool under = false;
+    if (REC) {
+        entry = (uint32_t *)(index + (size_t)b * idx_stride);
+        rc_index_header(entry, nsym, seg_sym);
+        entry += PCCX_INDEX_HEADER_BYTES / 4;
+    }
     const uint8_t *buf = in + (size_t)b * stride;
     const int nb = nbytes[b] < 0 ? 0 : (nbytes[b] > stride ? stride : nbytes[b]);
     int pos = 0, cached = 0;
@@ -107,6 +173,11 @@ __global__ void range_decode_kernel(const int32_t *__restrict__ cdf_int, const u
     const int max_symbol = Lp - 2;
     const int32_t *c = cdf_int + (size_t)b * nsym * Lp;
     for (int i = 0; i < nsym; ++i, c += Lp) {
+        if (REC && i == next) {
+            rc_record(entry, low, high, shifted, under);
+            entry += PCCX_INDEX_ENTRY_BYTES / 4;
+            next += seg_sym;
+        }
         const unsigned long long span = (unsigned long long)high - (unsigned long long)low + 1ull;
         const unsigned count =
             (unsigned)((((unsigned long long)value - (unsigned long long)low + 1ull) * 0x10000ull - 1ull) / span) & 0xFFFFu;
@@ -116,7 +187,7 @@ __global__ void range_decode_kernel(const int32_t *__restrict__ cdf_int, const u
             if (((unsigned)c[mid] & 0xFFFFu) <= count) left = mid; else right = mid;
         }
         const int s = left;
-        latent_q[(size_t)b * nsym + i] = (float)(s - sym_offset);            // decode - L//2 (decompress.py:93)
+        if (!REC || latent_q) latent_q[(size_t)b * nsym + i] = (float)(s - sym_offset);            // decode - L//2 (decompress.py:93)
         const unsigned c_low = (unsigned)c[s] & 0xFFFFu;
         const unsigned c_high = s == max_symbol ? 0x10000u : ((unsigned)c[s + 1] & 0xFFFFu);
         high = (unsigned)((low - 1u) + (unsigned)((span * c_high) >> 16));
@@ -124,15 +195,31 @@ __global__ void range_decode_kernel(const int32_t *__restrict__ cdf_int, const u
         for (;;) {
             if (low >= 0x80000000u || high < 0x80000000u) {
                 low <<= 1; high <<= 1; high |= 1u; get();
+                if (REC) ++shifted, under = false;
             } else if (low >= 0x40000000u && high < 0xC0000000u) {
                 low <<= 1; low &= 0x7FFFFFFFu;
                 high <<= 1; high |= 0x80000001u;
                 value -= 0x40000000u;
                 get();
+                if (REC) ++shifted, under = true;
             } else
                 break;
         }
     }
+}
+
+__global__ void range_decode_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in, int stride,
+                                    const int32_t *__restrict__ nbytes, int B, int nsym, int Lp, int sym_offset,
+                                    float *__restrict__ latent_q)
+{
+    rc_decode_lane<false>(cdf_int, in, stride, nbytes, B, nsym, Lp, sym_offset, latent_q, 0, nullptr, 0);
+}
+
+__global__ void range_index_build_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in, int stride,
+                                         const int32_t *__restrict__ nbytes, int B, int nsym, int Lp, int sym_offset,
+                                         float *__restrict__ latent_q, int seg_sym, uint8_t *__restrict__ index, int idx_stride)
+{
+    rc_decode_lane<true>(cdf_int, in, stride, nbytes, B, nsym, Lp, sym_offset, latent_q, seg_sym, index, idx_stride);
 }
 
 #define RC_MAX_LDS_BYTES (60 * 1024)
@@ -173,8 +260,12 @@ __device__ __forceinline__ unsigned rc_scale(unsigned span32, unsigned c) { retu
 
 // One stream, one wave: c = the stream's tables [nsym][Lp], q = its nsym latents, out = its cap bytes, nbytes = its count.  The
 // pointers and counts must be wave-uniform (kernel arguments and blockIdx only).  LDS: rc_encode_lds(nsym, cap) bytes at smem.
+// REC: lane 0 also stores the entry (rc_record) of every seg_sym boundary at entry, entry + 3, ...; the stream does not depend on it,
+// and without REC the two arguments are not looked at.
+template <bool REC = false>
 __device__ __forceinline__ void rc_encode_wave(unsigned char *smem, const int32_t *__restrict__ c, const float *__restrict__ q, int nsym,
-                                               int Lp, int sym_offset, uint8_t *__restrict__ out, int cap, int32_t *__restrict__ nbytes)
+                                               int Lp, int sym_offset, uint8_t *__restrict__ out, int cap, int32_t *__restrict__ nbytes,
+                                               uint32_t *__restrict__ entry = nullptr, int seg_sym = 0)
 {
     uint2 *sc = (uint2 *)smem;                                         // [nsym] (c_low, c_high)
     unsigned *sout = (unsigned *)(sc + nsym);                          // [capw] output words (stream order = big endian)
@@ -208,12 +299,18 @@ __device__ __forceinline__ void rc_encode_wave(unsigned char *smem, const int32_
             cnt -= m;
         }
     };
+    int next = 0;                                                      // REC: the next boundary
     uint2 nxt = lane < nsym ? sc[lane] : make_uint2(0u, 0x10000u);
     for (int i0 = 0; i0 < nsym; i0 += 64) {
         const uint2 cur = nxt;
         if (i0 + 64 + lane < nsym) nxt = sc[i0 + 64 + lane];
         const int cnt = nsym - i0 < 64 ? nsym - i0 : 64;
         for (int j = 0; j < cnt; ++j) {
+            if (REC && i0 + j == next) {
+                if (lane == 0) rc_record(entry, low, high, (unsigned long long)nw * 32ull + (unsigned long long)na + pending, pending > 0);
+                entry += PCCX_INDEX_ENTRY_BYTES / 4;
+                next += seg_sym;
+            }
             const unsigned c_low = __builtin_amdgcn_readlane(cur.x, j), c_high = __builtin_amdgcn_readlane(cur.y, j);
             const unsigned span32 = high - low;
             high = (low - 1u) + rc_scale(span32, c_high);
@@ -269,8 +366,15 @@ __global__ __launch_bounds__(64) void range_encode_wave_kernel(const int32_t *__
 // One stream, one wave: c = the stream's tables [nsym][Lp], in = its first byte, nb = its length already clamped to [0, stride]
 // (bytes from nb on are not read and count as zero), q = its nsym outputs.  The pointers and counts must be wave-uniform.  LDS:
 // rc_decode_lds(nsym, Lp - 1, stride) bytes at smem.
+// INIT: the stream is entered at an entry of its index (entry_index.h): `in` is the byte that holds stream bit pos, skip = pos & 7
+// the bits of it that lie before pos, (low0, high0) the interval and under0 the pending flag; value is rebuilt from the 32 bits at pos.
+// REC: lane 0 also stores the entry of every seg_sym boundary at entry, entry + 3, ... (rc_record), and q may be null.
+// Without INIT / REC their arguments are not looked at.
+template <bool INIT = false, bool REC = false>
 __device__ __forceinline__ void rc_decode_wave(unsigned char *smem, const int32_t *__restrict__ c, const uint8_t *__restrict__ in, int stride,
-                                               int nb, int nsym, int Lp, int sym_offset, float *__restrict__ q)
+                                               int nb, int nsym, int Lp, int sym_offset, float *__restrict__ q, unsigned low0 = 0u,
+                                               unsigned high0 = 0xFFFFFFFFu, int skip = 0, bool under0 = false,
+                                               uint32_t *__restrict__ entry = nullptr, int seg_sym = 0)
 {
     const int ncdf = nsym * Lp;
     unsigned short *scdf = (unsigned short *)smem;                    // [ncdf]
@@ -297,7 +401,16 @@ __device__ __forceinline__ void rc_decode_wave(unsigned char *smem, const int32_
         have -= m;
         return (unsigned)(buf >> have) & ones(m);
     };
-    unsigned low = 0u, high = 0xFFFFFFFFu, value = getbits(32);
+    unsigned low = 0u, high = 0xFFFFFFFFu;
+    if (INIT) {
+        low = low0, high = high0;
+        getbits(skip & 7);
+    }
+    unsigned value = getbits(32);
+    if (INIT) value ^= under0 ? 0x80000000u : 0u;
+    unsigned long long shifted = 0;                                    // REC: bits taken beyond the first 32; an underflow run is pending
+    bool under = false;
+    int next = 0;
     const int max_symbol = Lp - 2;
     const int G = 64 / Lp;                                             // symbols per block of lanes
     unsigned cn = lane < G * Lp && lane < ncdf ? scdf[lane] : 0u;
@@ -307,6 +420,11 @@ __device__ __forceinline__ void rc_decode_wave(unsigned char *smem, const int32_
         if (lane < G * Lp && inext < ncdf) cn = scdf[inext];
         const int cnt = nsym - i0 < G ? nsym - i0 : G;
         for (int j = 0; j < cnt; ++j) {
+            if (REC && i0 + j == next) {
+                if (lane == 0) rc_record(entry, low, high, shifted, under);
+                entry += PCCX_INDEX_ENTRY_BYTES / 4;
+                next += seg_sym;
+            }
             const unsigned span32 = high - low, off = value - low;
             // largest s with cdf[s] <= ((value-low+1)*2^16 - 1) / span  <=>  (span*cdf[s]) >> 16 <= value - low
             const unsigned t = rc_scale(span32, cv);
@@ -338,6 +456,7 @@ __device__ __forceinline__ void rc_decode_wave(unsigned char *smem, const int32_
             high = (high << k) | fix | ones(k);
             // value' = ((value << m | bits_m) << k ^ 2^31) | bits_k  =  (value << (m+k) | bits_(m+k)) ^ (k ? 2^31 : 0)
             const int n = m + k;
+            if (REC) shifted += (unsigned)n, under = k > 0 || (m == 0 && under);
             if (n <= 32) {
                 const unsigned nbits = getbits(n);
                 value = ((unsigned)((unsigned long long)value << n) | nbits) ^ fix;
@@ -348,6 +467,7 @@ __device__ __forceinline__ void rc_decode_wave(unsigned char *smem, const int32_
         }
     }
     __syncthreads();
+    if (REC && !q) return;
     for (int i = lane; i < nsym; i += 64) q[i] = (float)((int)ssym[i] - sym_offset);
 }
 
@@ -660,6 +780,225 @@ extern "C" int pccx_range_decode_split_list(const int32_t *cdf_int, const uint8_
     if (n_list > 0) {
         hipLaunchKernelGGL(range_decode_split_list_kernel, dim3(n_list), dim3(64), rc_decode_lds(seg_sym, L, segcap), (hipStream_t)stream,
                            cdf_int, in, stride, offsets, seg_idx, nsym, seg_sym, P, L + 1, L / 2, segcap, latent_q);
+        PCCX_CHECK_LAUNCH();
+    }
+    return PCCX_OK;
+}
+
+// ---- entry-point index: any number of waves enter the ONE stream of a cloud side by side -------------------------------------
+// Format and check: entry_index.h.  The stream is pccx_range_encode's, byte for byte; the sidecar holds the coder's state at every
+// seg_sym boundary.  Encode = the sequential encoder (wave or one lane, as pccx_range_coder_form says) that also stores the entries;
+// build = the sequential decoder doing the same on an existing stream; decode = one check kernel per call (status per cloud + 4 words
+// per segment in workspace), then every segment by rc_decode_wave<INIT> from its entry, staging only the bytes between its position
+// and the next one's plus the 32-bit window: at most rc_index_stage bytes (maxspan + 32 bits starting inside a byte).
+static int rc_index_maxspan(int seg_sym) { return 8 * rc_split_segcap(seg_sym); }        // bits a segment may shift in
+static int rc_index_stage(int seg_sym) { return rc_split_segcap(seg_sym) + 8; }
+
+extern "C" size_t pccx_range_index_bytes(int nsym, int seg_sym)
+{
+    if (nsym < 0 || seg_sym < 1) return 0;
+    return (size_t)pccx_index_bytes(nsym, seg_sym);
+}
+
+extern "C" size_t pccx_range_index_workspace_bytes(int B, int nsym, int seg_sym)
+{
+    if (B <= 0 || nsym < 0 || seg_sym < 1) return 0;
+    return (((size_t)B * (size_t)pccx_index_segments(nsym, seg_sym) * PCCX_INDEX_SEG_WORDS * 4) + 15) & ~(size_t)15;
+}
+
+extern "C" int pccx_entry_index_check_host(const uint8_t *index, int64_t idx_bytes, int64_t stream_bytes, int nsym, int seg_sym)
+{
+    if (nsym < 0 || seg_sym < 1 || seg_sym > (1 << 24) || idx_bytes < 0 || stream_bytes < 0 || stream_bytes > 0x7FFFFFFFll || (!index && idx_bytes > 0))
+        return PCCX_INDEX_BAD_FIELDS;                                   // no file agrees with such a call
+    return pccx_entry_index_check(index, idx_bytes, stream_bytes, nsym, seg_sym, rc_index_maxspan(seg_sym), nullptr);
+}
+
+__global__ __launch_bounds__(64) void range_encode_indexed_wave_kernel(const int32_t *__restrict__ cdf_int, const float *__restrict__ latent_q,
+                                                                       int nsym, int Lp, int sym_offset, uint8_t *__restrict__ out, int cap,
+                                                                       int32_t *__restrict__ nbytes, int seg_sym, uint8_t *__restrict__ index,
+                                                                       int idx_stride)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
+    const int b = blockIdx.x;
+    uint32_t *side = (uint32_t *)(index + (size_t)b * idx_stride);
+    if (threadIdx.x == 0) rc_index_header(side, nsym, seg_sym);
+    rc_encode_wave<true>(rc_smem, cdf_int + (size_t)b * nsym * Lp, latent_q + (size_t)b * nsym, nsym, Lp, sym_offset, out + (size_t)b * cap,
+                         cap, nbytes + b, side + PCCX_INDEX_HEADER_BYTES / 4, seg_sym);
+}
+
+__global__ __launch_bounds__(64) void range_index_build_wave_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in,
+                                                                    int stride, const int32_t *__restrict__ nbytes, int nsym, int Lp,
+                                                                    int sym_offset, float *__restrict__ latent_q, int seg_sym,
+                                                                    uint8_t *__restrict__ index, int idx_stride)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
+    const int b = blockIdx.x;
+    const int nb = nbytes[b] < 0 ? 0 : (nbytes[b] > stride ? stride : nbytes[b]);
+    uint32_t *side = (uint32_t *)(index + (size_t)b * idx_stride);
+    if (threadIdx.x == 0) rc_index_header(side, nsym, seg_sym);
+    rc_decode_wave<false, true>(rc_smem, cdf_int + (size_t)b * nsym * Lp, in + (size_t)b * stride, stride, nb, nsym, Lp, sym_offset,
+                                latent_q ? latent_q + (size_t)b * nsym : nullptr, 0u, 0xFFFFFFFFu, 0, false,
+                                side + PCCX_INDEX_HEADER_BYTES / 4, seg_sym);
+}
+
+__global__ __launch_bounds__(64) void range_index_check_kernel(const uint8_t *__restrict__ index, int idx_stride, const int32_t *__restrict__ idx_nbytes,
+                                                               int stride, const int32_t *__restrict__ nbytes, int B, int nsym, int seg_sym,
+                                                               int P, int maxspan, int32_t *__restrict__ status, uint32_t *__restrict__ seg)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    // counts beyond their rows are cut to the rows before anything is read
+    const int nb = nbytes[b] < 0 ? 0 : (nbytes[b] > stride ? stride : nbytes[b]);
+    const int ni = !idx_nbytes ? idx_stride : (idx_nbytes[b] < 0 ? 0 : (idx_nbytes[b] > idx_stride ? idx_stride : idx_nbytes[b]));
+    status[b] = pccx_entry_index_check(index + (size_t)b * idx_stride, ni, nb, nsym, seg_sym, maxspan, seg + (size_t)b * P * PCCX_INDEX_SEG_WORDS);
+}
+
+// Segment p of one cloud from the check kernel's four words, decoded into q.  in / nbrow: the cloud's row and its byte count cut to
+// the row.  The check gives pos <= end <= 8 * nbrow and end - pos <= maxspan + 32 (all 0 on a refused sidecar); the clamps restate
+// that here, where the addresses are formed: the bytes read are in[at .. at + nb) with 0 <= at <= at + nb <= nbrow and nb <= stage.
+__device__ __forceinline__ void rc_decode_entry(unsigned char *smem, const int32_t *__restrict__ c, const uint8_t *__restrict__ in, int nbrow,
+                                                const uint32_t *__restrict__ seg, int stage, int n, int Lp, int sym_offset,
+                                                float *__restrict__ q)
+{
+    const unsigned low = rc_uni(seg[0]), high = rc_uni(seg[1]), pf = rc_uni(seg[2]), end = rc_uni(seg[3]);
+    const unsigned pos = pf & ~PCCX_INDEX_FLAG;
+    int at = (int)(pos >> 3);                                          // < 2^28
+    const unsigned endb = (end >> 3) + ((end & 7u) ? 1u : 0u);         // < 2^29 + 1
+    int to = endb > (unsigned)nbrow ? nbrow : (int)endb;
+    at = at > nbrow ? nbrow : at;
+    to = to < at ? at : to;
+    const int nb = to - at > stage ? stage : to - at;
+    rc_decode_wave<true>(smem, c, in + at, stage, nb, n, Lp, sym_offset, q, low, high, (int)(pos & 7u), (pf & PCCX_INDEX_FLAG) != 0u);
+}
+
+__global__ __launch_bounds__(64) void range_decode_indexed_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in, int stride,
+                                                                  const int32_t *__restrict__ nbytes, const uint32_t *__restrict__ seg,
+                                                                  int nsym, int seg_sym, int P, int Lp, int sym_offset, int stage,
+                                                                  float *__restrict__ latent_q)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
+    const int p = blockIdx.x, b = blockIdx.y;
+    const int first = p * seg_sym;                                     // < nsym: p < P
+    const int n = nsym - first < seg_sym ? nsym - first : seg_sym;     // ragged last segment
+    const int nbr = (int)rc_uni((unsigned)nbytes[b]);
+    const int nbrow = nbr < 0 ? 0 : (nbr > stride ? stride : nbr);
+    rc_decode_entry(rc_smem, cdf_int + ((size_t)b * nsym + first) * Lp, in + (size_t)b * stride, nbrow,
+                    seg + ((size_t)b * P + p) * PCCX_INDEX_SEG_WORDS, stage, n, Lp, sym_offset, latent_q + (size_t)b * nsym + first);
+}
+
+// The listed form (region decode): wave j decodes segment seg_idx[j] of ONE cloud with table rows and output rows j * seg_sym ...,
+// both compact, as range_decode_split_list_kernel.  It stages the bytes of that segment's span alone.  An index outside [0, P) is cut
+// into it.
+__global__ __launch_bounds__(64) void range_decode_indexed_list_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in,
+                                                                       int stride, const int32_t *__restrict__ nbytes,
+                                                                       const uint32_t *__restrict__ seg, const int32_t *__restrict__ seg_idx,
+                                                                       int nsym, int seg_sym, int P, int Lp, int sym_offset, int stage,
+                                                                       float *__restrict__ latent_q)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
+    const int j = blockIdx.x;
+    int p = (int)rc_uni((unsigned)seg_idx[j]);
+    p = p < 0 ? 0 : (p > P - 1 ? P - 1 : p);
+    const int first = p * seg_sym;
+    const int n = nsym - first < seg_sym ? nsym - first : seg_sym;
+    const int nbr = (int)rc_uni((unsigned)nbytes[0]);
+    const int nbrow = nbr < 0 ? 0 : (nbr > stride ? stride : nbr);
+    rc_decode_entry(rc_smem, cdf_int + (size_t)j * seg_sym * Lp, in, nbrow, seg + (size_t)p * PCCX_INDEX_SEG_WORDS, stage, n, Lp, sym_offset,
+                    latent_q + (size_t)j * seg_sym);
+}
+
+// The shapes every indexed entry point takes: those of the split path, and a stream whose bit positions fit the 31 bits of an entry.
+static int rc_index_check_args(const char *who, int B, int nsym, int seg_sym, int L, int64_t stream_bytes)
+{
+    const int rc = rc_split_check_args(who, B, nsym, seg_sym, L);
+    if (rc != PCCX_OK) return rc;
+    PCCX_CHECK_ARG(stream_bytes >= 1 && stream_bytes <= (1 << 27), "%s: a stream row of %lld bytes; 1 .. 2^27 (bit positions are 31 bits wide)", who,
+                   (long long)stream_bytes);
+    return PCCX_OK;
+}
+
+extern "C" int pccx_range_encode_indexed(const int32_t *cdf_int, const float *latent_q, int B, int nsym, int seg_sym, int L, uint8_t *out,
+                                         int cap, int32_t *nbytes, uint8_t *index, void *stream)
+{
+    if (B == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
+    const int rc = rc_index_check_args("pccx_range_encode_indexed", B, nsym, seg_sym, L, cap);
+    if (rc != PCCX_OK) return rc;
+    PCCX_CHECK_ARG(cdf_int && latent_q && out && nbytes && index, "pccx_range_encode_indexed: null pointer");
+    PCCX_CHECK_ARG(cap >= 8 && ((uintptr_t)index & 3) == 0, "pccx_range_encode_indexed: bad shape (cap=%d) or an index that is not 4-byte aligned", cap);
+    const int idx_stride = (int)pccx_index_bytes(nsym, seg_sym);
+    if (pccx_range_coder_form(0, nsym, L, cap) == 0) {
+        hipLaunchKernelGGL(range_encode_indexed_wave_kernel, dim3(B), dim3(64), rc_encode_lds(nsym, cap), (hipStream_t)stream, cdf_int, latent_q,
+                           nsym, L + 1, L / 2, out, cap, nbytes, seg_sym, index, idx_stride);
+        PCCX_CHECK_LAUNCH();
+        return PCCX_OK;
+    }
+    hipLaunchKernelGGL(range_encode_indexed_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, cdf_int, latent_q, B, nsym, L + 1,
+                       L / 2, out, cap, nbytes, seg_sym, index, idx_stride);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+extern "C" int pccx_range_index_build(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes, int B, int nsym,
+                                      int seg_sym, int L, uint8_t *index, float *latent_q, void *stream)
+{
+    if (B == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
+    const int rc = rc_index_check_args("pccx_range_index_build", B, nsym, seg_sym, L, stride);
+    if (rc != PCCX_OK) return rc;
+    PCCX_CHECK_ARG(cdf_int && in && nbytes && index, "pccx_range_index_build: null pointer");
+    PCCX_CHECK_ARG(((uintptr_t)index & 3) == 0, "pccx_range_index_build: an index that is not 4-byte aligned");
+    const int idx_stride = (int)pccx_index_bytes(nsym, seg_sym);
+    if (pccx_range_coder_form(1, nsym, L, stride) == 0) {
+        hipLaunchKernelGGL(range_index_build_wave_kernel, dim3(B), dim3(64), rc_decode_lds(nsym, L, stride), (hipStream_t)stream, cdf_int, in,
+                           stride, nbytes, nsym, L + 1, L / 2, latent_q, seg_sym, index, idx_stride);
+        PCCX_CHECK_LAUNCH();
+        return PCCX_OK;
+    }
+    hipLaunchKernelGGL(range_index_build_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, cdf_int, in, stride, nbytes, B, nsym,
+                       L + 1, L / 2, latent_q, seg_sym, index, idx_stride);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+extern "C" int pccx_range_decode_indexed(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes, const uint8_t *index,
+                                         int idx_stride, const int32_t *idx_nbytes, int B, int nsym, int seg_sym, int L, float *latent_q,
+                                         int32_t *status, void *workspace, void *stream)
+{
+    if (B == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
+    const int rc = rc_index_check_args("pccx_range_decode_indexed", B, nsym, seg_sym, L, stride);
+    if (rc != PCCX_OK) return rc;
+    const int P = (int)pccx_index_segments(nsym, seg_sym), stage = rc_index_stage(seg_sym);
+    PCCX_CHECK_ARG(in && nbytes && index && status && workspace && (nsym == 0 || (cdf_int && latent_q)), "pccx_range_decode_indexed: null pointer");
+    PCCX_CHECK_ARG(idx_stride >= 0, "pccx_range_decode_indexed: bad shape (idx_stride=%d)", idx_stride);
+    uint32_t *seg = (uint32_t *)workspace;
+    hipLaunchKernelGGL(range_index_check_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, index, idx_stride, idx_nbytes, stride,
+                       nbytes, B, nsym, seg_sym, P, rc_index_maxspan(seg_sym), status, seg);
+    PCCX_CHECK_LAUNCH();
+    if (P > 0) {
+        hipLaunchKernelGGL(range_decode_indexed_kernel, dim3(P, B), dim3(64), rc_decode_lds(seg_sym, L, stage), (hipStream_t)stream, cdf_int, in,
+                           stride, nbytes, seg, nsym, seg_sym, P, L + 1, L / 2, stage, latent_q);
+        PCCX_CHECK_LAUNCH();
+    }
+    return PCCX_OK;
+}
+
+extern "C" int pccx_range_decode_indexed_list(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes,
+                                              const uint8_t *index, int idx_bytes, int nsym, int seg_sym, int L, const int32_t *seg_idx,
+                                              int n_list, float *latent_q, int32_t *status, void *workspace, void *stream)
+{
+    const int rc = rc_index_check_args("pccx_range_decode_indexed_list", 1, nsym, seg_sym, L, stride);
+    if (rc != PCCX_OK) return rc;
+    const int P = (int)pccx_index_segments(nsym, seg_sym), stage = rc_index_stage(seg_sym);
+    PCCX_CHECK_ARG(n_list >= 0 && n_list <= P, "pccx_range_decode_indexed_list: %d segments listed of %d", n_list, P);
+    PCCX_CHECK_ARG(in && nbytes && index && status && workspace && (n_list == 0 || (cdf_int && latent_q && seg_idx)),
+                   "pccx_range_decode_indexed_list: null pointer");
+    PCCX_CHECK_ARG(idx_bytes >= 0, "pccx_range_decode_indexed_list: bad shape (idx_bytes=%d)", idx_bytes);
+    uint32_t *seg = (uint32_t *)workspace;
+    hipLaunchKernelGGL(range_index_check_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, index, idx_bytes, (const int32_t *)nullptr, stride,
+                       nbytes, 1, nsym, seg_sym, P, rc_index_maxspan(seg_sym), status, seg);
+    PCCX_CHECK_LAUNCH();
+    if (n_list > 0) {
+        hipLaunchKernelGGL(range_decode_indexed_list_kernel, dim3(n_list), dim3(64), rc_decode_lds(seg_sym, L, stage), (hipStream_t)stream,
+                           cdf_int, in, stride, nbytes, seg, seg_idx, nsym, seg_sym, P, L + 1, L / 2, stage, latent_q);
         PCCX_CHECK_LAUNCH();
     }
     return PCCX_OK;

@@ -39,6 +39,8 @@ class Compressed:
     n_points: int
     extras: dict = None       # intermediates for tests / diagnostics
     packed: torch.Tensor = None   # the u8 buffer the five fields above are views of (packed_layout), when built by Codec
+    p_index: torch.Tensor = None  # (B, 16 + 12*P) u8  entry-point index of p_bytes (<name>.p.idx), or None: no index
+    p_index_nbytes: torch.Tensor = None   # (B) i32 byte counts of the sidecars when they came from files, or None: whole rows
 
     @classmethod
     def alloc(cls, B, s_stride, p_cap, n_points, device):
@@ -61,6 +63,13 @@ class Compressed:
 
     def bpp(self):
         return self.bits().double() / self.n_points
+
+    def index_bits(self):
+        """Bits per cloud of the entry-point index (<name>.p.idx), 0 without one.  Not part of bits() / bpp(), which stay the
+        reference's three files.  Derived from the shape alone: 96 per segment of G patches and 128 of header, that is
+        96 / (G*K/ALPHA) bits per input point plus 128 / N."""
+        B = self.s_bytes.shape[0]
+        return torch.full((B,), 0 if self.p_index is None else 8 * self.p_index.shape[1], dtype=torch.int64, device=self.s_bytes.device)
 
     def to_host(self):
         """ONE device->host transfer of everything the three files need (cached).  Raises PccxError when a range-coder
@@ -92,19 +101,24 @@ class Compressed:
 
     def write_files(self, directory, names, threads=0):
         """<directory>/<names[b]>.p.bin / .s.bin / .c.bin for every cloud (compress.py:139-152), cut from ONE host copy of the packed
-        buffer by the library's host threads (pccx_write_streams_host).  Returns the total number of bytes of the three files."""
+        buffer by the library's host threads (pccx_write_streams_host).  Returns the total number of bytes of the three files.
+        With p_index present also <names[b]>.p.idx (pccx_write_index_host; not counted in the total)."""
         B = self.s_bytes.shape[0]
         if len(names) != B:
             raise ValueError(f"write_files: {len(names)} names for {B} clouds")
         self.to_host()                                         # ONE D2H (cached); raises on a negative byte count
         host = self._host_packed
         write_streams(host, B, self.s_bytes.shape[1], self.p_bytes.shape[1], directory, names, threads)
+        if self.p_index is not None:
+            write_index(self.p_index.cpu().contiguous(), directory, names, threads)
         return int(self._host[1].sum()) + int(self._host[3].sum()) + 16 * B
 
     @classmethod
-    def read_files(cls, directory, names, n_points=0, s_stride=None, p_cap=None, device=None, threads=0, out=None):
+    def read_files(cls, directory, names, n_points=0, s_stride=None, p_cap=None, device=None, threads=0, out=None, p_index=None):
         """The inverse (decompress.py:80-91,113): the three files of every name into one packed host buffer (rows sized from the largest
-        file unless s_stride / p_cap are given; `out` = a host uint8 tensor to fill, e.g. pinned), then -- with `device` -- ONE upload."""
+        file unless s_stride / p_cap are given; `out` = a host uint8 tensor to fill, e.g. pinned), then -- with `device` -- ONE upload.
+        p_index = (nsym, seg_sym): also read <name>.p.idx of every name into p_index / p_index_nbytes (rows of the 16 + 12*P bytes
+        that shape gives; a missing or longer file raises PccxError, a shorter one is refused by the decoder's check)."""
         B = len(names)
         if s_stride is None or p_cap is None:
             ss, ps = stream_sizes(directory, names, threads)
@@ -119,7 +133,13 @@ class Compressed:
             raise ValueError(f"read_files: `out` must be a host uint8 tensor of {need} bytes")
         read_streams(host, B, s_stride, p_cap, directory, names, threads)
         packed = host.to(device, non_blocking=True) if device is not None else host
-        return cls.from_packed(packed, B, s_stride, p_cap, n_points)
+        comp = cls.from_packed(packed, B, s_stride, p_cap, n_points)
+        if p_index is not None:
+            idx, n = read_index(directory, names, models.index_bytes(*p_index), threads)
+            comp.p_index = idx.to(device) if device is not None else idx
+            comp.p_index_nbytes = n.to(device) if device is not None else n
+            comp._p_index_nbytes_host = n.tolist()
+        return comp
 
 
 def _name_table(names):
@@ -156,6 +176,25 @@ def read_streams(packed_host, B, s_stride, p_cap, directory, names, threads=0):
     _lib.call("pccx_read_streams_host", packed_host.data_ptr(), B, s_stride, p_cap, os.fsencode(directory), blob, off.ctypes.data, int(threads))
 
 
+def write_index(index_host, directory, names, threads=0):
+    """pccx_write_index_host: <directory>/<names[b]>.p.idx = row b of a host (B, bytes) u8 tensor (no GPU call)."""
+    from . import _lib
+    blob, off = _name_table(names)
+    if index_host.is_cuda or index_host.dtype != torch.uint8 or index_host.dim() != 2 or index_host.shape[0] != len(names) or not index_host.is_contiguous():
+        raise ValueError(f"write_index: a contiguous host uint8 tensor of ({len(names)}, bytes) is expected")
+    _lib.call("pccx_write_index_host", index_host.data_ptr(), len(names), index_host.shape[1], os.fsencode(directory), blob, off.ctypes.data, int(threads))
+
+
+def read_index(directory, names, idx_bytes, threads=0):
+    """pccx_read_index_host: the sidecars of every name -> (host (B, idx_bytes) u8 rows, host (B,) i32 byte counts)."""
+    from . import _lib
+    blob, off = _name_table(names)
+    idx = torch.zeros(len(names), int(idx_bytes), dtype=torch.uint8)
+    n = torch.zeros(max(len(names), 1), dtype=torch.int32)
+    _lib.call("pccx_read_index_host", idx.data_ptr() if idx.numel() else n.data_ptr(), len(names), int(idx_bytes), n.data_ptr(), os.fsencode(directory), blob, off.ctypes.data, int(threads))
+    return idx, n[:len(names)]
+
+
 def stream_sizes(directory, names, threads=0):
     """(sizes of <name>.s.bin, sizes of <name>.p.bin) as int64 arrays, -1 where the file does not exist."""
     from . import _lib
@@ -173,7 +212,7 @@ OCTREE_WIDE_MAX_S = 8192       # ... and their wide forms (pccx_octree_encode_wi
 class Codec:
     def __init__(self, ae, prob, K=256, ALPHA=2, N0=1024, octree_mode="reference", margin=0.01, matmul=None,
                  decoder_matmul=None, sa_matmul=None, pn_matmul=None, group_duplicates=True, knn_search="auto",
-                 max_centres=OCTREE_MAX_S, p_split=None):
+                 max_centres=OCTREE_MAX_S, p_split=None, p_index=None):
         """matmul: how the three transforms (SetAbstraction, PointNet, decoder) form their fp32 products --
         "f32" = v_mfma_f32_16x16x4_f32 (bit-for-bit a k-ordered fmaf chain), "bf16x3" = each fp32 operand split exactly into
         three bf16 pieces, six products per pair on the bf16 matrix cores, fp32 accumulate (fp32-level error, 2.6x the
@@ -192,7 +231,12 @@ class Codec:
         each coded from a fresh coder state by its own wave behind a directory of segment lengths, so that a whole room's latents are
         coded and decoded side by side and not by one lane.  Both sides must agree on p_split, as they must
         on octree_mode: it is not recorded outside the stream's own header, which decompress checks.  A split ``.p.bin`` is NOT a file
-        the reference's decompress.py reads."""
+        the reference's decompress.py reads.
+        p_index: None (the default) changes nothing.  An int G >= 1 keeps ``.p.bin`` the reference's single stream, byte for byte, and
+        makes compress also write an entry-point index (Compressed.p_index, the file ``.p.idx``): the coder's state every G patches,
+        12 bytes each.  decompress then enters the one stream with one wave per G patches when comp.p_index is present (and decodes
+        sequentially when it is absent), decompress_region takes it in place of p_split, and build_index makes the index of a file
+        written without one, the reference's own included.  The same limits as p_split; the two exclude each other."""
         from . import DEFAULT_MATMUL
         matmul = matmul or DEFAULT_MATMUL
         self.ae, self.prob = ae, prob
@@ -217,6 +261,14 @@ class Codec:
                 raise ValueError(f"p_split must be None or an int in 1..{g_max} patches per segment (a segment of p_split*d symbols is staged in "
                                  f"LDS by one wave, d={ae.d}, L={ae.L}; L must be in 2..63), got {p_split!r}")
         self.p_split = p_split
+        if p_index is not None:
+            if p_split is not None:
+                raise ValueError("p_index and p_split exclude each other: the index enters the single stream, the split form has no single stream")
+            g_max = models.split_max_seg_sym(ae.L) // ae.d
+            if isinstance(p_index, bool) or not isinstance(p_index, int) or not 1 <= p_index <= g_max:
+                raise ValueError(f"p_index must be None or an int in 1..{g_max} patches per entry (a segment of p_index*d symbols is staged in "
+                                 f"LDS by one wave, d={ae.d}, L={ae.L}; L must be in 2..63), got {p_index!r}")
+        self.p_index = p_index
         if ae.K != K or ae.k != self.k:
             raise ValueError("AE was built for a different K / k")
 
@@ -272,7 +324,9 @@ class Codec:
         with stage("prob"):
             cdf_int = self.prob.run(rec, ("cdf_int",), distinct=self._distinct())["cdf_int"]                    # compress.py:131-134
         with stage("range_encode"):
-            if self.p_split is None:
+            if self.p_index is not None:
+                comp.p_index = models.range_encode_indexed(cdf_int, q.view(B, S * d), L, self.p_index * d, out=comp.p_bytes, nb=comp.p_nbytes)[2]
+            elif self.p_split is None:
                 models.range_encode(cdf_int, q.view(B, S * d), L, out=comp.p_bytes, nb=comp.p_nbytes)   # compress.py:135-136
             else:
                 models.range_encode_split(cdf_int, q.view(B, S * d), L, self.p_split * d, out=comp.p_bytes, nb=comp.p_nbytes)
@@ -300,7 +354,10 @@ class Codec:
             with stage("prob"):
                 cdf_int = self.prob.run(rec, ("cdf_int",), distinct=self._distinct())["cdf_int"]                     # decompress.py:88-92
         with stage("range_decode"):
-            if self.p_split is None:
+            if self.p_index is not None and comp.p_index is not None:
+                q = models.range_decode_indexed(cdf_int, comp.p_bytes, comp.p_nbytes, comp.p_index, L, self.p_index * d,
+                                                index_nbytes=comp.p_index_nbytes)
+            elif self.p_split is None:
                 q = models.range_decode(cdf_int, comp.p_bytes, comp.p_nbytes, L)          # decompress.py:93
             else:
                 q = models.range_decode_split(cdf_int, comp.p_bytes, comp.p_nbytes, L, self.p_split * d)
@@ -310,6 +367,22 @@ class Codec:
             return self.ae.decode(q.view(B * S, d), rec.view(B * S, 3), comp.c[:, :3].contiguous(),
                                   comp.c[:, 3].contiguous(), S=S, scale=scale, margin=self.margin,
                                   matmul=self.decoder_matmul, group=self.group_duplicates, short_list=self._distinct())
+
+    def build_index(self, comp, S=64):
+        """The entry-point index of a Compressed that has none (files written without p_index, the reference's own included): the
+        probability model and the sequential decoder run once, and comp.p_index is set (and returned) -- bit for bit what compress
+        with this p_index writes.  The three streams are not touched."""
+        if self.p_index is None:
+            raise ValueError("build_index needs p_index (patches per entry); this Codec has p_index=None")
+        self._check_centres(int(S), f"build_index(S={S})")
+        with stage("octree_decode"):
+            rec, _ = ops.octree_decode(comp.s_bytes, comp.s_nbytes, self.octree_mode, S)
+        with stage("prob"):
+            cdf_int = self.prob.run(rec, ("cdf_int",), distinct=self._distinct())["cdf_int"]
+        with stage("build_index"):
+            comp.p_index = models.range_index_build(cdf_int, comp.p_bytes, comp.p_nbytes, self.ae.L, self.p_index * self.ae.d)
+        comp.p_index_nbytes = None
+        return comp.p_index
 
     def decompress_region(self, comp, S, box, halo=0.0):
         """The decoded patches of ONE cloud whose centre lies in a box, without decoding the rest -> Region.
@@ -328,8 +401,12 @@ class Codec:
         is not fused, the whole cloud is decoded by decompress() and the selected rows are taken: the same result by definition.
         Refused with ValueError before any launch: p_split None, octree_mode other than "full", a batch, a bad box or halo, S above
         max_centres.  A stream written without this split raises PccxError as decompress() does."""
-        if self.p_split is None:
-            raise ValueError("decompress_region needs p_split (the split .p.bin is what can be entered at a segment); this Codec has p_split=None")
+        if self.p_split is None and self.p_index is None:
+            raise ValueError("decompress_region needs p_split or p_index (a stream is entered at a segment through the split .p.bin's "
+                             "directory or the single stream's entry-point index); this Codec has p_split=None and p_index=None")
+        indexed = self.p_index is not None
+        if indexed and comp.p_index is None:
+            raise ValueError("decompress_region with p_index needs comp.p_index (read_files(p_index=...) or Codec.build_index first)")
         if self.octree_mode != "full":
             raise ValueError(f"decompress_region needs octree_mode='full', got octree_mode={self.octree_mode!r}")
         B = comp.s_bytes.shape[0]
@@ -338,17 +415,24 @@ class Codec:
         ops.check_box(box, halo)
         S = int(S)
         self._check_centres(S, f"decompress_region(S={S})")
-        d, L, G = self.ae.d, self.ae.L, self.p_split
+        d, L, G = self.ae.d, self.ae.L, self.p_index if indexed else self.p_split
+        if indexed:
+            side = comp.p_index[0]
+            if comp.p_index_nbytes is not None:              # from a file: the sidecar is as long as the file was (read_files keeps the
+                host_n = getattr(comp, "_p_index_nbytes_host", None)     # counts on the host too, so this is no synchronisation)
+                side = side[:max(int(host_n[0] if host_n is not None else comp.p_index_nbytes[0]), 1)]
         fast = self.prob.fused_ok(S) and self.ae.fused_d
         with stage("octree_decode"):
             rec, _ = ops.octree_decode(comp.s_bytes, comp.s_nbytes, self.octree_mode, S)
         head = torch.zeros(3, device=rec.device, dtype=torch.int32)           # n_sel, n_seg, status of the stream's header
         with stage("region_select"):
             sel = ops.region_select(rec[0], comp.c[0], box, G, halo, self.margin, counts=head[:2])
-            if fast:
+            if fast and indexed:
+                models.range_decode_indexed_list(None, comp.p_bytes[0], comp.p_nbytes, side, L, G * d, S * d, None, 0, status=head[2:])
+            elif fast:
                 models.range_decode_split_list(None, comp.p_bytes[0], comp.p_nbytes, L, G * d, S * d, None, 0, status=head[2:])
             n_sel, n_seg, status = (int(v) for v in head.cpu())               # THE synchronisation
-        err = models.split_status_error("decompress_region", [status])
+        err = (models.index_status_error if indexed else models.split_status_error)("decompress_region", [status])
         if err is not None:
             raise err
         patch_idx, segments = sel.patch_idx[:n_sel], sel.seg_idx[:n_seg].to(torch.int64)
@@ -360,7 +444,10 @@ class Codec:
         with stage("prob"):
             cdf_int = self.prob.run_segments(rec[0], sel.seg_idx, n_seg, G)
         with stage("range_decode"):
-            q, _ = models.range_decode_split_list(cdf_int, comp.p_bytes[0], comp.p_nbytes, L, G * d, S * d, sel.seg_idx, n_seg)
+            if indexed:
+                q, _ = models.range_decode_indexed_list(cdf_int, comp.p_bytes[0], comp.p_nbytes, side, L, G * d, S * d, sel.seg_idx, n_seg)
+            else:
+                q, _ = models.range_decode_split_list(cdf_int, comp.p_bytes[0], comp.p_nbytes, L, G * d, S * d, sel.seg_idx, n_seg)
         with stage("gather"):
             q_sel = ops.index_points(q.view(1, n_seg * G, d), sel.rows[:n_sel].view(1, n_sel))
             c_sel = ops.index_points(rec, patch_idx.view(1, n_sel))

@@ -750,3 +750,135 @@ def split_stream_status(data, nsym, seg_sym):
     data = bytes(data)
     buf = ctypes.create_string_buffer(data, max(len(data), 1))
     return int(_lib.load().pccx_split_stream_check_host(ctypes.addressof(buf), len(data), int(nsym), int(seg_sym), range_cap(seg_sym)))
+
+
+# ---- entry-point index of the single stream (include/pccx.h: "PXI1" | nsym | seg_sym | P | {low, high, pos}[P]) -----------------
+# The .p.bin stays range_encode's bytes; the sidecar lets one wave per segment enter it.  Limits are the split path's.
+
+INDEX_HEADER = 16
+INDEX_ENTRY = 12
+INDEX_STATUS = {1: "shorter than its header, no 'PXI1' magic, or not 16 + 12*P bytes (truncated, or not a .p.idx)",
+                2: "nsym / seg_sym / P field disagree with the call (written with another p_index or another S)",
+                3: "an entry's position lies below the one before it",
+                4: "an entry's position lies beyond the stream's last bit (the index of another .p.bin)",
+                5: "consecutive positions further apart than the bits a segment may take",
+                6: "an entry's interval is no state of the coder, or entry 0 is not the initial state"}
+
+
+def index_bytes(nsym, seg_sym):
+    """Bytes of one cloud's sidecar: 16 + 12 * ceil(nsym / seg_sym)."""
+    return INDEX_HEADER + INDEX_ENTRY * split_segments(nsym, seg_sym)
+
+
+def _index_workspace(B, nsym, seg_sym, device):
+    need = int(_lib.load().pccx_range_index_workspace_bytes(int(B), int(nsym), int(seg_sym)))
+    return workspace("range_index", max(need // 4, 4), device)
+
+
+def _index_rows(index, B, who):
+    """A sidecar tensor as dense (B, idx_stride) u8 rows on the device."""
+    if index.dtype != torch.uint8 or index.dim() not in (1, 2):
+        raise _lib.PccxError(f"{who}: index must be (B, bytes) or (bytes,) u8")
+    index = index.reshape(B, -1).contiguous()
+    return index
+
+
+def range_encode_indexed(cdf_int, latent_q, L, seg_sym, cap=None, out=None, nb=None):
+    """range_encode that also writes the entry-point index: -> (bytes (B,cap) u8, nbytes (B), index (B, index_bytes(nsym, seg_sym)) u8).
+    The bytes and counts are range_encode's; index row b is the file <name>.p.idx of cloud b."""
+    B = cdf_int.shape[0]
+    nsym = cdf_int[0].numel() // (L + 1) if B else 0
+    seg_sym = int(seg_sym)
+    q = _f32c(latent_q.reshape(B, nsym), "range_encode_indexed")
+    if out is None:
+        out = torch.empty(B, cap or range_cap(nsym), device=q.device, dtype=torch.uint8)
+    if nb is None:
+        nb = torch.empty(B, device=q.device, dtype=torch.int32)
+    if (out.dim() != 2 or out.shape[0] != B or out.dtype != torch.uint8 or not out.is_contiguous() or tuple(nb.shape) != (B,)
+            or nb.dtype != torch.int32 or not nb.is_contiguous()):
+        raise _lib.PccxError("range_encode_indexed: out must be dense (B,cap) u8 and nb dense (B,) i32")
+    index = torch.empty(B, index_bytes(nsym, max(seg_sym, 1)), device=q.device, dtype=torch.uint8)
+    _lib.call("pccx_range_encode_indexed", cdf_int.contiguous().data_ptr(), q.data_ptr(), B, nsym, seg_sym, int(L), out.data_ptr(),
+              out.shape[1], nb.data_ptr(), index.data_ptr(), _stream())
+    return out, nb, index
+
+
+def range_index_build(cdf_int, bytes_, nbytes, L, seg_sym, return_latent=False):
+    """The index of existing streams (files written without one, the reference's included): the sequential decoder run once ->
+    index (B, index_bytes) u8, bit for bit what range_encode_indexed writes for the same stream; with return_latent also the
+    symbols it decoded on the way, (index, latent_q (B,nsym) f32)."""
+    B = cdf_int.shape[0]
+    nsym = cdf_int[0].numel() // (L + 1) if B else 0
+    seg_sym = int(seg_sym)
+    bytes_ = bytes_.contiguous()
+    index = torch.empty(B, index_bytes(nsym, max(seg_sym, 1)), device=bytes_.device, dtype=torch.uint8)
+    q = torch.empty(B, nsym, device=bytes_.device, dtype=torch.float32) if return_latent else None
+    _lib.call("pccx_range_index_build", cdf_int.contiguous().data_ptr(), bytes_.data_ptr(), bytes_.shape[1],
+              nbytes.to(torch.int32).contiguous().data_ptr(), B, nsym, seg_sym, int(L), index.data_ptr(),
+              q.data_ptr() if return_latent else None, _stream())
+    return (index, q) if return_latent else index
+
+
+def range_decode_indexed(cdf_int, bytes_, nbytes, index, L, seg_sym, index_nbytes=None, check=True):
+    """range_decode by one wave per segment of seg_sym symbols, each entering the ONE stream at its entry of `index` (B, bytes) u8 ->
+    latent_q (B,nsym) f32, equal to range_decode's.  index_nbytes: (B) i32 byte counts of the sidecars where they may be shorter
+    than their rows (files).  check=True reads the per-cloud status once and raises PccxError naming the clouds whose sidecar is
+    refused (INDEX_STATUS); check=False returns (latent_q, status (B,) i32 on the device) without a synchronisation -- a refused
+    cloud's symbols are those of empty segments."""
+    B = cdf_int.shape[0]
+    nsym = cdf_int[0].numel() // (L + 1) if B else 0
+    seg_sym = int(seg_sym)
+    bytes_ = bytes_.contiguous()
+    index = _index_rows(index, B, "range_decode_indexed")
+    q = torch.empty(B, nsym, device=bytes_.device, dtype=torch.float32)
+    status = torch.zeros(B, device=bytes_.device, dtype=torch.int32)
+    ws = _index_workspace(B, nsym, seg_sym, bytes_.device)
+    _lib.call("pccx_range_decode_indexed", cdf_int.contiguous().data_ptr(), bytes_.data_ptr(), bytes_.shape[1],
+              nbytes.to(torch.int32).contiguous().data_ptr(), index.data_ptr(), index.shape[1],
+              index_nbytes.to(torch.int32).contiguous().data_ptr() if index_nbytes is not None else None, B, nsym, seg_sym, int(L),
+              q.data_ptr(), status.data_ptr(), ws.data_ptr(), _stream())
+    if not check:
+        return q, status
+    err = index_status_error("range_decode_indexed", status.cpu().numpy())
+    if err is not None:
+        raise err
+    return q
+
+
+def index_status_error(who, st):
+    """The PccxError range_decode_indexed raises for per-cloud status words ``st`` (a host sequence), or None when all are 0."""
+    import numpy as np
+    st = np.asarray(st).reshape(-1)
+    if not st.any():
+        return None
+    return _lib.PccxError(f"{who}: " + "; ".join(
+        f"clouds {[int(b) for b in (st == code).nonzero()[0]]}: {why}" for code, why in INDEX_STATUS.items() if (st == code).any()))
+
+
+def range_decode_indexed_list(cdf_int, bytes_, nbytes, index, L, seg_sym, nsym, seg_idx, n_list, status=None):
+    """range_decode_indexed for the listed segments of ONE cloud, the counterpart of range_decode_split_list: cdf_int
+    (n_list*seg_sym, L+1) i32 compact table rows, bytes_ the cloud's .p.bin, nbytes (1,) i32, index the idx bytes of its sidecar
+    (a 1-d u8 tensor: its length is the sidecar's), seg_idx i32 on the device, n_list a host int -> (latent_q (n_list*seg_sym,) f32
+    compact, status (1,) i32 on the device).  Only the bytes of the listed segments' spans are read.  n_list = 0 runs the check alone."""
+    bytes_ = bytes_.contiguous().reshape(-1)
+    index = index.contiguous().reshape(-1)
+    if index.dtype != torch.uint8:
+        raise _lib.PccxError("range_decode_indexed_list: index must be u8")
+    n_list, seg_sym, nsym = int(n_list), int(seg_sym), int(nsym)
+    q = torch.empty(n_list * seg_sym, device=bytes_.device, dtype=torch.float32)
+    if status is None:
+        status = torch.zeros(1, device=bytes_.device, dtype=torch.int32)
+    ws = _index_workspace(1, nsym, seg_sym, bytes_.device)
+    _lib.call("pccx_range_decode_indexed_list", cdf_int.contiguous().data_ptr() if n_list else None, bytes_.data_ptr(), bytes_.numel(),
+              nbytes.to(torch.int32).contiguous().data_ptr(), index.data_ptr(), index.numel(), nsym, seg_sym, int(L),
+              seg_idx.contiguous().data_ptr() if n_list else None, n_list, q.data_ptr() if n_list else None, status.data_ptr(),
+              ws.data_ptr(), _stream())
+    return q, status
+
+
+def index_status(data, stream_bytes, nsym, seg_sym):
+    """pccx_entry_index_check_host on a bytes-like sidecar for a .p.bin of stream_bytes bytes (no GPU call): 0, or a key of INDEX_STATUS."""
+    import ctypes
+    data = bytes(data)
+    buf = ctypes.create_string_buffer(data, max(len(data), 1))
+    return int(_lib.load().pccx_entry_index_check_host(ctypes.addressof(buf), len(data), int(stream_bytes), int(nsym), int(seg_sym)))
