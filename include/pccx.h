@@ -69,6 +69,19 @@ PCCX_API size_t pccx_fps_coop_workspace_bytes(int B, int npoint);
 PCCX_API int pccx_fps_coop(const float *xyz, int B, int N, int npoint, const int32_t *start_idx, int64_t *idx_out, int G,
                            void *workspace, void *stream);
 
+/* Block-parallel centre selection: P independent farthest point samplings per cloud, side by side (one launch of P * B workgroups of
+ * 1024 threads; no cooperative launch, no workspace, no read-back, so it can be captured).  NOT the indices of pccx_fps unless P == 1.
+ * order: (B,N) int64, a permutation of 0..N-1 per cloud (in use: the cloud's Morton order); checked for range only -- an entry
+ * outside 0..N-1 is clamped and never forms an address.  Block j = 0..P-1 of a cloud holds the sorted positions [lo_j, lo_{j+1}),
+ * lo_j = floor(j*N/P) (64-bit), and fills the output slots [o_j, o_{j+1}), o_j = floor(j*npoint/P); its local point i is
+ * xyz[order[lo_j + i]], its first centre the local index start_idx[b] mod n_j (0 when start_idx is NULL or the entry lies outside
+ * 0..N-1).  Inside a block the recurrence is pccx_fps's to the operation (running minimum from 1e10, (dx*dx + dy*dy) + dz*dz without
+ * contraction, fminf, the largest minimum, ties to the LOWER LOCAL index); slot o_j + t receives order[lo_j + winner_t], an index
+ * into the original cloud.  PCCX_ERR_ARG before any launch: P < 1, ceil(N/P) > 16384 (a block lives in one workgroup's registers),
+ * floor(npoint/P) < 1, ceil(npoint/P) > floor(N/P). */
+PCCX_API int pccx_fps_blocks(const float *xyz, int B, int N, const int64_t *order, int P, int npoint, const int32_t *start_idx,
+                             int64_t *idx_out, void *stream);
+
 /* 63-bit Morton keys over the bounding box [lo, lo+extent]^3 (lo_host: 3 floats on the HOST), used to
  * cut clouds larger than one block into spatially compact 8192-point blocks (BASELINE configs[3]).
  * xyz: (n,3) f32; keys: (n) int64. */

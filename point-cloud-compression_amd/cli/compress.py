@@ -18,6 +18,13 @@ parser.add_argument('input_glob', help='Point clouds glob pattern for compressio
 parser.add_argument('compressed_path', help='Comressed .bin files folder.')
 parser.add_argument('model_load_folder', help='Directory where to load trained models.')
 _common.add_codec_flags(parser)
+# how the centres are chosen concerns the encoder alone: decompress.py reads the files of either choice without a flag
+parser.add_argument('--centres', choices=['fps', 'blocks'], default='fps',
+                    help="Patch centres: 'fps' = the reference's farthest point sampling over the whole cloud; 'blocks' = an independent "
+                         "sampling in every run of --fps-block points of the cloud's Morton order, all runs side by side (whole rooms: "
+                         "a fraction of the time, other centres, hence other bytes and quality).  The files are read by decompress.py as they are.")
+parser.add_argument('--fps-block', type=int, default=8192, metavar='N',
+                    help="Points per block of --centres blocks, 1024..16384; a cloud of at most N points gets the exact sampling.")
 
 
 def main():
@@ -29,7 +36,7 @@ def main():
     ae, prob = _common.load_models(args)
     cd = codec.Codec(ae, prob, K=args.K, ALPHA=args.ALPHA, N0=args.N0, octree_mode=args.octree_mode, knn_search=args.knn_search,
                      max_centres=codec.OCTREE_WIDE_MAX_S,             # whole clouds up to 8192 patches: 1048576 points at K = 256
-                     p_split=args.p_split or None, p_index=args.p_index or None)
+                     p_split=args.p_split or None, p_index=args.p_index or None, centres=args.centres, fps_block=args.fps_block)
     mine = set(dist.shard_indices(len(files), rank, world))                                      # file i -> rank i mod world
     times, todo, bits, points, index_bits = [], [t for t in enumerate(files) if t[0] in mine], 0, 0, 0
     with torch.no_grad():

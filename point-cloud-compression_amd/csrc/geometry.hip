@@ -596,6 +596,132 @@ extern "C" int pccx_fps_coop(const float *xyz, int B, int N, int npoint, const i
 }
 
 // ------------------------------------------------------------------------------------------
+// pccx_fps_blocks: P independent farthest point samplings per cloud, one per block of a permutation (in use: the cloud's Morton
+// order), side by side -- a grid of P * B workgroups of 1024 threads, no cooperative launch, no workspace, no read-back.
+//
+// Block j of a cloud holds the sorted positions [lo_j, lo_{j+1}), lo_j = floor(j * N / P), and fills the output slots
+// [o_j, o_{j+1}), o_j = floor(j * npoint / P).  Its local point i is xyz[order[lo_j + i]], read ONCE through the permutation into
+// registers (thread t owns the local points t, t + 1024, ...); from there on a round is fps_kernel's to the operation: running
+// minimum from 1e10, (dx*dx + dy*dy) + dz*dz as packed fp32 without contraction, fminf, the largest minimum with ties to the lower
+// LOCAL index, the winner's coordinates carried beside its key.  Slot o_j + t receives order[lo_j + winner_t], an index into the
+// original cloud.  An entry of `order` outside 0..N-1 is clamped before it forms an address.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ long long fps_blocks_entry(const int64_t *__restrict__ ord, int i, int N)
+{
+    const long long g = ord[i];
+    return g < 0 ? 0 : g >= N ? (long long)N - 1 : g;
+}
+
+template <int PPT>
+__global__ __launch_bounds__(1024) void fps_blocks_kernel(const float *__restrict__ xyz, int N, const int64_t *__restrict__ order,
+                                                          int P, int npoint, const int32_t *__restrict__ start,
+                                                          int64_t *__restrict__ out)
+{
+    __shared__ unsigned long long part_k[2][16];              // wave winners as 64-bit keys (argmax_key)
+    __shared__ float part_c[2][16][4];                        // ... and their coordinates
+    const int b = blockIdx.x / P, blk = blockIdx.x - b * P, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const long long lo = (long long)blk * N / P;
+    const int n = (int)((long long)(blk + 1) * N / P - lo);                      // <= 1024 * PPT (checked by the entry)
+    const long long o0 = (long long)blk * npoint / P;
+    const int quota = (int)((long long)(blk + 1) * npoint / P - o0);             // 1 <= quota <= n (checked by the entry)
+    const float *p = xyz + (size_t)b * N * 3;
+    const int64_t *ord = order + (size_t)b * N + lo;
+    int64_t *o = out + (size_t)b * npoint + o0;
+
+    constexpr int PP = (PPT + 1) / 2;
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    f32x2 px[PP], py[PP], pz[PP], md[PP];
+#pragma unroll
+    for (int j = 0; j < PP; ++j)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int i = tid + (2 * j + e) * 1024;
+            if (2 * j + e < PPT && i < n) {
+                const long long g = fps_blocks_entry(ord, i, N);
+                px[j][e] = p[3 * g]; py[j][e] = p[3 * g + 1]; pz[j][e] = p[3 * g + 2];
+                md[j][e] = 1e10f;              // distance = ones * 1e10 (:320)
+            } else {
+                px[j][e] = py[j][e] = pz[j][e] = 0.f;
+                md[j][e] = -INFINITY;          // never selected
+            }
+        }
+
+    int far = start ? start[b] : 0;
+    if (far < 0 || far >= N) far = 0;
+    far %= n;                                                                    // the cloud's start index, folded into the block
+    long long gfar = fps_blocks_entry(ord, far, N);
+    float cx = p[3 * gfar], cy = p[3 * gfar + 1], cz = p[3 * gfar + 2];
+    int par = 0;
+    for (int s = 0; s < quota; ++s) {
+        if (tid == 0) o[s] = fps_blocks_entry(ord, far, N);          // off the round's serial path: nothing waits for this load
+        if (s + 1 == quota) break;                                    // the last centre needs no successor
+        float best = -INFINITY, bx = 0.f, by = 0.f, bz = 0.f;
+        int bi = 0x7fffffff;
+#pragma unroll
+        for (int j = 0; j < PP; ++j) {
+            const f32x2 dx = px[j] - cx, dy = py[j] - cy, dz = pz[j] - cz;   // (:326): (x - c)^2 summed x, y, z
+            f32x2 d = dx * dx;
+            d = d + dy * dy;
+            d = d + dz * dz;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                md[j][e] = fminf(md[j][e], d[e]);                             // (:327-328)
+                const bool up = md[j][e] > best;                              // ascending local index, strict '>'
+                best = up ? md[j][e] : best;
+                bi = up ? tid + (2 * j + e) * 1024 : bi;
+                bx = up ? px[j][e] : bx;
+                by = up ? py[j][e] : by;
+                bz = up ? pz[j][e] : bz;
+            }
+        }
+        const unsigned long long mk = argmax_key(best, bi);
+        const unsigned long long wk = wave_argmax_key(mk);
+        if (mk == wk) {                        // the owner of the wave's winner (lanes with no point tie on -inf and write zeros)
+            part_k[par][w] = wk;
+            part_c[par][w][0] = bx; part_c[par][w][1] = by; part_c[par][w][2] = bz;
+        }
+        __syncthreads();
+        const unsigned long long k16 = part_k[par][lane & 15];       // the 16 wave winners, one per lane of every row
+        const unsigned long long vk = row16_argmax_key(k16);
+        far = __builtin_amdgcn_readfirstlane(argmax_key_index(vk));
+        if (far < 0 || far >= n) far = 0;                             // cannot happen (n >= 1: some lane holds a point); never index out of the block
+        const int ww = __builtin_amdgcn_readfirstlane(__ffsll((long long)__ballot(k16 == vk)) - 1) & 15;
+        cx = part_c[par][ww][0]; cy = part_c[par][ww][1]; cz = part_c[par][ww][2];
+        par ^= 1;
+    }
+}
+
+template <int PPT>
+static int launch_fps_blocks(const float *xyz, int B, int N, const int64_t *order, int P, int npoint, const int32_t *start,
+                             int64_t *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(fps_blocks_kernel<PPT>, dim3((unsigned)(B * P)), dim3(1024), 0, st, xyz, N, order, P, npoint, start, out);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+extern "C" int pccx_fps_blocks(const float *xyz, int B, int N, const int64_t *order, int P, int npoint, const int32_t *start_idx,
+                               int64_t *idx_out, void *stream)
+{
+    if (B == 0) return PCCX_OK;                  // empty batch: nothing to do, pointers may be null
+    PCCX_CHECK_ARG(B >= 0 && N >= 1 && npoint >= 0, "pccx_fps_blocks: bad shape B=%d N=%d npoint=%d", B, N, npoint);
+    PCCX_CHECK_ARG(P >= 1, "pccx_fps_blocks: P=%d blocks, need P >= 1", P);
+    const long long most = ((long long)N + P - 1) / P, least = N / P, qmost = ((long long)npoint + P - 1) / P, qleast = npoint / P;
+    PCCX_CHECK_ARG(most <= 16384, "pccx_fps_blocks: N=%d points in P=%d blocks puts %lld points in a block, 16384 at the most", N, P, most);
+    PCCX_CHECK_ARG(qleast >= 1, "pccx_fps_blocks: npoint=%d over P=%d blocks leaves a block without a centre", npoint, P);
+    PCCX_CHECK_ARG(qmost <= least, "pccx_fps_blocks: a block of %lld points cannot give %lld centres (N=%d, npoint=%d, P=%d)", least,
+                   qmost, N, npoint, P);
+    PCCX_CHECK_ARG((long long)B * P <= 0x7fffffffll, "pccx_fps_blocks: B*P = %d*%d workgroups exceed the grid", B, P);
+    PCCX_CHECK_ARG(xyz && order && idx_out, "pccx_fps_blocks: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (most <= 1024) return launch_fps_blocks<1>(xyz, B, N, order, P, npoint, start_idx, idx_out, st);
+    if (most <= 2048) return launch_fps_blocks<2>(xyz, B, N, order, P, npoint, start_idx, idx_out, st);
+    if (most <= 4096) return launch_fps_blocks<4>(xyz, B, N, order, P, npoint, start_idx, idx_out, st);
+    if (most <= 8192) return launch_fps_blocks<8>(xyz, B, N, order, P, npoint, start_idx, idx_out, st);
+    return launch_fps_blocks<16>(xyz, B, N, order, P, npoint, start_idx, idx_out, st);
+}
+
+// ------------------------------------------------------------------------------------------
 // Morton keys for block-partitioning large clouds (BASELINE configs[3]: S3DIS rooms chunked into
 // 8192-point blocks so that S = N*ALPHA/K stays 64).  21 bits per axis over the cloud's bounding box.
 // ------------------------------------------------------------------------------------------

@@ -212,7 +212,7 @@ OCTREE_WIDE_MAX_S = 8192       # ... and their wide forms (pccx_octree_encode_wi
 class Codec:
     def __init__(self, ae, prob, K=256, ALPHA=2, N0=1024, octree_mode="reference", margin=0.01, matmul=None,
                  decoder_matmul=None, sa_matmul=None, pn_matmul=None, group_duplicates=True, knn_search="auto",
-                 max_centres=OCTREE_MAX_S, p_split=None, p_index=None):
+                 max_centres=OCTREE_MAX_S, p_split=None, p_index=None, centres="fps", fps_block=8192):
         """matmul: how the three transforms (SetAbstraction, PointNet, decoder) form their fp32 products --
         "f32" = v_mfma_f32_16x16x4_f32 (bit-for-bit a k-ordered fmaf chain), "bf16x3" = each fp32 operand split exactly into
         three bf16 pieces, six products per pair on the bf16 matrix cores, fp32 accumulate (fp32-level error, 2.6x the
@@ -236,7 +236,16 @@ class Codec:
         makes compress also write an entry-point index (Compressed.p_index, the file ``.p.idx``): the coder's state every G patches,
         12 bytes each.  decompress then enters the one stream with one wave per G patches when comp.p_index is present (and decodes
         sequentially when it is absent), decompress_region takes it in place of p_split, and build_index makes the index of a file
-        written without one, the reference's own included.  The same limits as p_split; the two exclude each other."""
+        written without one, the reference's own included.  The same limits as p_split; the two exclude each other.
+        centres: how compress picks the S patch centres of a cloud.  "fps" (the default) is the reference's farthest point sampling over
+        the whole cloud, launch for launch as before.  "blocks" cuts the normalised cloud into ceil(N / fps_block) runs of its Morton
+        order and samples every run on its own, all side by side (ops.farthest_point_sample_blocks; fps_block an int in 1024..16384
+        points) -- a whole room's centres in a few launches instead of S dependent rounds.  The normalisation, the whole-cloud kNN
+        patches and everything downstream stay as they are, and the decoder never learns how the centres were chosen (``.s.bin`` is the
+        octree of whatever S points it was given): the three files are ones any decoder of this codec reads -- decompress,
+        build_index, decompress_region and the reference's decompress.py, none of which takes this argument.  The choice does change
+        the centres, hence the bytes and the quality (DESIGN.md section 4.5 has the measured cost).  A cloud of one block
+        (N <= fps_block) gets the exact indices and the same files as "fps"."""
         from . import DEFAULT_MATMUL
         matmul = matmul or DEFAULT_MATMUL
         self.ae, self.prob = ae, prob
@@ -269,6 +278,9 @@ class Codec:
                 raise ValueError(f"p_index must be None or an int in 1..{g_max} patches per entry (a segment of p_index*d symbols is staged in "
                                  f"LDS by one wave, d={ae.d}, L={ae.L}; L must be in 2..63), got {p_index!r}")
         self.p_index = p_index
+        if centres not in ("fps", "blocks"):
+            raise ValueError(f"centres must be 'fps' or 'blocks', got {centres!r}")
+        self.centres, self.fps_block = centres, ops.check_fps_block(fps_block)
         if ae.K != K or ae.k != self.k:
             raise ValueError("AE was built for a different K / k")
 
@@ -299,8 +311,11 @@ class Codec:
             raise ValueError(f"octree_mode='reference' reproduces octree_np.decode's hard-coded S=64 "
                              f"(octree_np.py:100; compress.py:102 asserts); got S={S}. Use octree_mode='full'.")
         with stage("fps"):
-            fps_idx = ops.farthest_point_sample_batch(pcn, S, start_idx,             # compress.py:96
-                                                      workgroups="auto" if self.max_centres > OCTREE_MAX_S else None)
+            if self.centres == "blocks":
+                fps_idx = ops.farthest_point_sample_blocks(pcn, S, start_idx, block=self.fps_block)
+            else:
+                fps_idx = ops.farthest_point_sample_batch(pcn, S, start_idx,         # compress.py:96
+                                                          workgroups="auto" if self.max_centres > OCTREE_MAX_S else None)
         with stage("gather"):
             sampled = ops.index_points(pcn, fps_idx)
         p_cap = models.range_cap(S * d) if self.p_split is None else models.split_cap(S * d, self.p_split * d)

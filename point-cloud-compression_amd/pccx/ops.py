@@ -245,6 +245,60 @@ def farthest_point_sample_batch(xyz, npoint, start_idx=None, workgroups=None, wo
     return out
 
 
+FPS_BLOCK_MIN, FPS_BLOCK_MAX = 1024, 16384   # points per block of pccx_fps_blocks: one workgroup's registers hold at most 1024 x 16
+
+
+def check_fps_block(block):
+    """``block`` as an int in 1024..16384 points per block, or a ValueError naming fps_block.  Host only."""
+    if isinstance(block, bool) or not isinstance(block, int) or not FPS_BLOCK_MIN <= block <= FPS_BLOCK_MAX:
+        raise ValueError(f"fps_block must be an int in {FPS_BLOCK_MIN}..{FPS_BLOCK_MAX} points per block, got {block!r}")
+    return block
+
+
+def fps_block_plan(N, npoint, block):
+    """How farthest_point_sample_blocks cuts a cloud of N points with npoint centres: (P, lo, o) with P = ceil(N / block) blocks,
+    lo[j] = floor(j*N/P) the first sorted position of block j and o[j] = floor(j*npoint/P) its first output slot (P + 1 entries each,
+    ending at N and npoint), the arithmetic of pccx_fps_blocks.  Host only.  ``block`` is an int in 1024..16384; anything else, or a
+    shape the kernel refuses (a block without a centre, or asked for more centres than it has points), is a ValueError."""
+    check_fps_block(block)
+    N, npoint = int(N), int(npoint)
+    if N < 1 or npoint < 0:
+        raise ValueError(f"fps_block_plan: need N >= 1 and npoint >= 0, got N={N} npoint={npoint}")
+    P = -(-N // block)
+    if P > 1 and (npoint // P < 1 or -(-npoint // P) > N // P):
+        raise ValueError(f"fps_block_plan: {npoint} centres over {P} blocks of {N // P} points: every block needs at least one centre "
+                         f"and at most as many as it has points")
+    return P, [j * N // P for j in range(P + 1)], [j * npoint // P for j in range(P + 1)]
+
+
+def farthest_point_sample_blocks(xyz, npoint, start_idx=None, block=8192, order=None):
+    """Block-parallel centre selection (pccx_fps_blocks): the cloud is cut into P = ceil(N / block) runs of its Morton order
+    (fps_block_plan) and every run picks its share of the npoint centres by a farthest point sampling of its own, all runs side by
+    side in one launch -> (B, npoint) int64 indices into xyz.  These are NOT farthest_point_sample_batch's indices unless P == 1,
+    where that function is called and nothing is sorted.  A run starts at its local point start_idx[b] mod (points of the run).
+    order: (B,N) int64, each row a permutation of 0..N-1, instead of large.morton_orders of the clouds."""
+    xyz = _f32c(xyz, "farthest_point_sample_blocks")
+    B, N, _ = xyz.shape
+    P = fps_block_plan(N, npoint, block)[0]
+    if P == 1:
+        return farthest_point_sample_batch(xyz, npoint, start_idx)
+    if start_idx is None:
+        start_idx = torch.randint(0, N, (B,), dtype=torch.long)
+    start = None if isinstance(start_idx, str) and start_idx == "zero" else torch.as_tensor(start_idx).to(device=xyz.device, dtype=torch.int32).contiguous()
+    if order is None:
+        from . import large
+        rows = large.morton_orders(list(xyz.unbind(0)))
+        order = rows[0].view(1, N) if B == 1 else torch.stack(rows)
+    order = _dev(order, "farthest_point_sample_blocks.order")
+    if order.dtype != torch.int64 or tuple(order.shape) != (B, N) or order.device != xyz.device:
+        raise ValueError(f"farthest_point_sample_blocks: order must be a ({B}, {N}) int64 tensor on {xyz.device}, got {tuple(order.shape)} {order.dtype}")
+    order = order.contiguous()
+    out = torch.empty(B, npoint, device=xyz.device, dtype=torch.int64)
+    _lib.call("pccx_fps_blocks", xyz.data_ptr(), B, N, order.data_ptr(), P, int(npoint), start.data_ptr() if start is not None else None,
+              out.data_ptr(), _stream())
+    return out
+
+
 def sample_farthest_points(xyz, K):
     """pytorch3d.ops.sample_farthest_points as pointnet_sa_module.py:12 uses it: start index 0,
     returns (points, idx)."""

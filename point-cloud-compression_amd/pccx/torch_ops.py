@@ -62,6 +62,17 @@ def _(xyz, npoint, start_idx):
     return xyz.new_empty(xyz.shape[0], npoint, dtype=torch.int64)
 
 
+@_op("fps_blocks")
+def fps_blocks(xyz: Tensor, npoint: int, start_idx: Tensor, block: int = 8192) -> Tensor:
+    """ops.farthest_point_sample_blocks: an independent FPS in every run of ``block`` points of the Morton order -> (B,npoint) int64."""
+    return _ops.farthest_point_sample_blocks(xyz, npoint, start_idx, block)
+
+
+@fps_blocks.register_fake
+def _(xyz, npoint, start_idx, block=8192):
+    return xyz.new_empty(xyz.shape[0], npoint, dtype=torch.int64)
+
+
 @_op("index_points")
 def index_points(points: Tensor, idx: Tensor) -> Tensor:
     """pn_kit.index_points (pn_kit.py:332-360) / pytorch3d knn_gather."""
@@ -307,4 +318,4 @@ def _(sampled_xyz, prob_blob, d, L):
 
 
 OPS = ("sa_forward", "pn_forward", "ae_decode", "prob_cdf", "normalize", "denormalize", "fps", "index_points", "knn_points", "ball_query", "nn_dist", "chamfer_distance",
-       "chamfer_grad", "ste_round", "octree_encode", "octree_decode", "range_encode", "range_decode")
+       "chamfer_grad", "ste_round", "octree_encode", "octree_decode", "range_encode", "range_decode", "fps_blocks")
