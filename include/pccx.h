@@ -455,6 +455,17 @@ PCCX_API int pccx_prob_forward(const float *centres, int B, int S, int d, int L,
  * distinct centre row of a cloud (compared bit for bit) is evaluated once and its tables are copied to the duplicates.  S <= 64. */
 PCCX_API int pccx_prob_forward_distinct(const float *centres, int B, int S, int d, int L, const float *prob_blob,
                                         float *pmf, float *cdf, int32_t *cdf_int, void *stream);
+/* The same outputs, bit for bit, with the 16-centre tiles of every cloud dealt over the chip (opt-in; for few clouds of many centres,
+ * a whole room's 8192: pccx_prob_forward gives a cloud to one workgroup).  Three launches in stream order, no cooperative launch:
+ * pass 1 on a grid of (min(ceil(S/64), 64), B) workgroups, whose 256 partial maxima each go to workspace; one workgroup per cloud
+ * reduces them and runs pass 1b (512 floats per cloud, also in workspace); pass 2 + softmax + the tables on a grid of
+ * (ceil(S/64), B), four tiles per workgroup in one pass over the weights.  fmaxf is exact in any grouping and a centre's chain is
+ * pccx_prob_forward's k-tile for k-tile, hence the equality.  workspace: pccx_prob_forward_tiled_workspace_floats(B, S) floats on
+ * the device (host only; 0 for B < 1 or S < 16), 16-byte aligned, free for reuse once the call's launches have run.  The S / d / L
+ * limits are pccx_prob_forward's; B <= 65535 (the grid's second dimension); B = 0 launches nothing. */
+PCCX_API size_t pccx_prob_forward_tiled_workspace_floats(int B, int S);
+PCCX_API int pccx_prob_forward_tiled(const float *centres, int B, int S, int d, int L, const float *prob_blob,
+                                     float *pmf, float *cdf, int32_t *cdf_int, float *workspace, void *stream);
 
 /* torchac.encode_float_cdf (compress.py:134-136) / decode_float_cdf (decompress.py:92-93) on the
  * integer CDFs of pccx_prob_forward.  One independent stream per cloud of nsym = S*d symbols.

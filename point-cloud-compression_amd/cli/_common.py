@@ -83,6 +83,10 @@ def add_codec_flags(parser):
                         help="Write / read .p.bin in the split form: segments of G patches, each range-coded on its own behind a directory "
                              "of segment lengths, coded and decoded in parallel (whole rooms; 64 is the measured choice).  0 = the "
                              "reference's single stream.  Both sides must pass the same G; a split .p.bin is not a file the reference reads.")
+    parser.add_argument('--prob', choices=['cloud', 'tiles'], default='cloud',
+                        help="Probability model: 'cloud' = one workgroup per cloud (many small clouds); 'tiles' = every cloud's 16-centre "
+                             "tiles dealt over the chip (whole rooms: a fraction of the time).  The same tables bit for bit, hence the same "
+                             "files: the two sides need not agree.")
     parser.add_argument('--p-index', type=int, default=0, metavar='G',
                         help="Keep .p.bin the reference's single stream and write / read an entry-point index <name>.p.idx beside it: the "
                              "coder's state every G patches (12 bytes each), so that decompress.py decodes the one stream with one wave "

@@ -36,7 +36,8 @@ def main():
     ae, prob = _common.load_models(args)
     cd = codec.Codec(ae, prob, K=args.K, ALPHA=args.ALPHA, N0=args.N0, octree_mode=args.octree_mode, knn_search=args.knn_search,
                      max_centres=codec.OCTREE_WIDE_MAX_S,             # whole clouds up to 8192 patches: 1048576 points at K = 256
-                     p_split=args.p_split or None, p_index=args.p_index or None, centres=args.centres, fps_block=args.fps_block)
+                     p_split=args.p_split or None, p_index=args.p_index or None, centres=args.centres, fps_block=args.fps_block,
+                     prob_path=args.prob)
     mine = set(dist.shard_indices(len(files), rank, world))                                      # file i -> rank i mod world
     times, todo, bits, points, index_bits = [], [t for t in enumerate(files) if t[0] in mine], 0, 0, 0
     with torch.no_grad():

@@ -53,7 +53,8 @@ def main():
     names = [names[i] for i in dist.shard_indices(len(names), rank, world)]                      # file i -> rank i mod world
     ae, prob = _common.load_models(args)
     cd = codec.Codec(ae, prob, K=args.K, ALPHA=args.ALPHA, N0=args.N0, octree_mode=args.octree_mode, max_centres=codec.OCTREE_WIDE_MAX_S,
-                     p_split=args.p_split or None, p_index=args.p_index or None)
+                     p_split=args.p_split or None, p_index=args.p_index or None,
+                     prob_path=args.prob)         # decompress, --build-index, and --region's fallback through decompress()
     times, index_bits, points = [], 0, 0
     with torch.no_grad():
         for b0 in range(0, len(names), args.batch):

@@ -17,8 +17,8 @@
 #include "common.h"
 #include "mfma_chain.h"
 
-// ---- the stages of prob_forward_kernel as functions, for the region kernels at the end of this file (pccx_prob_feature,
-// pccx_prob_rows): the same statements in the same order, so a centre's chain is prob_forward_kernel's k-tile for k-tile (a column of
+// ---- the stages of prob_forward_kernel as functions, for the region kernels (pccx_prob_feature, pccx_prob_rows) and the
+// tiled whole-cloud kernels (pccx_prob_forward_tiled) at the end of this file: the same statements in the same order, so a centre's chain is prob_forward_kernel's k-tile for k-tile (a column of
 // an MFMA tile depends on nothing but its own input column).  prob_forward_kernel itself keeps its own text below: calling these
 // from it moved its register allocation (93 against 95 SGPRs, another instruction order), and that kernel is the headline's.
 // tests/test_region.py pins the two against each other bit for bit.  bl = the laundered blob pointer of the caller (opaque_uniform).
@@ -702,6 +702,128 @@ extern "C" int pccx_prob_rows(const float *centres, int S, int d, int L, const f
     const int ntiles = (int)(((int64_t)n_seg * G + 15) >> 4);
     hipLaunchKernelGGL(prob_rows_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, centres, S, d, L, prob_blob, feature,
                        seg_idx, n_seg, G, cdf_int);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// The same function for a BATCH of whole clouds with the tiles of every cloud dealt over the chip (opt-in: Codec(prob_path="tiles"),
+// DESIGN.md section 4.5): the three region kernels above with the cloud taken from blockIdx.y and without the list.
+// prob_forward_kernel gives a cloud to ONE workgroup, which is right for 1024 clouds of 64 centres and leaves 255 CUs idle for one
+// cloud of 8192.  Three launches in stream order: no cooperative launch, no flag, no spin.
+//   prob_tiled_partial_kernel, grid (nwg, B): prob_feature_partial_kernel's body on cloud blockIdx.y; its 256 maxima go to
+//       partial[b][wg][256].  A wave that gets no tile leaves -INFINITY, which no fmaxf keeps (every cloud has a tile).
+//   prob_tiled_reduce_kernel, grid (B): the maximum over the cloud's nwg partials, pass 1b, 512 floats to feature[b][512].
+//   prob_tiled_rows_kernel, grid (ceil(S/64), B): prob_rows_kernel's body with compact row r = row r of cloud blockIdx.y and all
+//       three outputs.  All four waves walk every chunk; a wave past the last tile walks the last tile and stores nothing.
+// The existing kernels keep their own text: nothing above this line changed, so their register allocation did not either.
+// ------------------------------------------------------------------------------------------
+#define PRB_TILED_MAX_B 65535                             // gridDim.y
+
+__global__ __launch_bounds__(256, 2) void prob_tiled_partial_kernel(const float *__restrict__ centres, int S,
+                                                                    const float *__restrict__ blob, float *__restrict__ partial)
+{
+    __shared__ float smax[4][256];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int g = lane >> 4, n = lane & 15;
+    const int ntiles = S >> 4;
+    const float *cp = centres + (size_t)blockIdx.y * S * 3;
+    f32x4 run[16];
+#pragma unroll
+    for (int mt = 0; mt < 16; ++mt) run[mt][0] = run[mt][1] = run[mt][2] = run[mt][3] = -INFINITY;
+    for (int tile = blockIdx.x * 4 + w; tile < ntiles; tile += 4 * gridDim.x) {
+        const float *bl = opaque_uniform(blob);
+        prob_pn_tile(bl, cp + 3 * (tile * 16 + n), g, lane, run);
+    }
+    if (n == 0)
+#pragma unroll
+        for (int mt = 0; mt < 16; ++mt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) smax[w][16 * mt + 4 * g + r] = run[mt][r];
+    __syncthreads();
+    partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid] =
+        fmaxf(fmaxf(smax[0][tid], smax[1][tid]), fmaxf(smax[2][tid], smax[3][tid]));
+}
+
+__global__ __launch_bounds__(256, 2) void prob_tiled_reduce_kernel(const float *__restrict__ partial, int nwg,
+                                                                   const float *__restrict__ blob, float *__restrict__ feature)
+{
+    __shared__ __attribute__((aligned(16))) float sfeat[256];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int g = lane >> 4, n = lane & 15;
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    const float *pp = partial + (size_t)blockIdx.x * nwg * 256;
+    float m = pp[tid];
+    for (int j = 1; j < nwg; ++j) m = fmaxf(m, pp[(size_t)j * 256 + tid]);
+    sfeat[tid] = m;
+    __syncthreads();
+    prob_feature_u(opaque_uniform(blob), sfeat, feature + (size_t)blockIdx.x * 512, lane, g, n, wu);
+}
+
+__global__ __launch_bounds__(256, 2) void prob_tiled_rows_kernel(const float *__restrict__ centres, int S, int d, int L,
+                                                                 const float *__restrict__ blob, const float *__restrict__ feature,
+                                                                 float *__restrict__ pmf, float *__restrict__ cdf,
+                                                                 int32_t *__restrict__ cdf_int)
+{
+    __shared__ __attribute__((aligned(16))) f32x4 swt[4 * PRB_WS_CHUNK * 64];   // 32 KiB weight ring, four chunks deep
+    __shared__ __attribute__((aligned(16))) float su[512];
+    __shared__ __attribute__((aligned(16))) float slog[4][16][128];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int wu = __builtin_amdgcn_readfirstlane(w);
+    const int ntiles = S >> 4;
+    const size_t b = blockIdx.y;
+    WStreamT<PRB_WS_CHUNK, 4, 4> ws{blob + PRB_STREAM, swt, PRB_STREAM_CHUNKS, lane, wu, false};   // one pass: nothing is issued past it
+    ws.prologue();
+    if (tid < 128) *(f32x4 *)(su + 4 * tid) = *(const f32x4 *)(feature + b * 512 + 4 * tid);
+    __syncthreads();
+
+    const int tile = blockIdx.x * 4 + w;
+    {
+        const float *bl = opaque_uniform(blob);
+        ws.g = bl + PRB_STREAM;
+        // lane indices from a laundered lane id, as in prob_forward_kernel
+        int lane2 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        asm volatile("" : "+v"(lane2));
+        const int g = lane2 >> 4, n = lane2 & 15;
+        ws.lane = lane2;
+        const int c = (tile < ntiles ? tile : ntiles - 1) * 16 + n;     // S % 16 == 0: no ragged tile; always inside the cloud
+        f32x4 a2[1][8];
+        prob_mlp_tile(ws, bl, su, centres + (b * S + c) * 3, g, a2);
+        if (tile < ntiles)
+#pragma unroll
+            for (int mt = 0; mt < 8; ++mt) *(f32x4 *)(&slog[w][n][16 * mt + 4 * g]) = a2[0][mt];
+    }
+    __syncthreads();
+    if (tile < ntiles) prob_tables_tile(slog[w], lane, 16, d, L, b * S + (size_t)tile * 16, pmf, cdf, cdf_int);
+    ws.drain();                                           // no DMA may land after the workgroup retires
+}
+
+extern "C" size_t pccx_prob_forward_tiled_workspace_floats(int B, int S)
+{
+    if (B < 1 || S < 16) return 0;
+    return (size_t)B * ((size_t)prob_feature_workgroups(S) * 256 + 512);      // the partial maxima, then 512 floats per cloud
+}
+
+extern "C" int pccx_prob_forward_tiled(const float *centres, int B, int S, int d, int L, const float *prob_blob, float *pmf,
+                                       float *cdf, int32_t *cdf_int, float *workspace, void *stream)
+{
+    if (B == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
+    PCCX_CHECK_ARG(centres && prob_blob && workspace, "pccx_prob_forward_tiled: null pointer");
+    PCCX_CHECK_ARG(pmf || cdf || cdf_int, "pccx_prob_forward_tiled: no output requested");
+    PCCX_CHECK_ARG(B >= 0 && B <= PRB_TILED_MAX_B, "pccx_prob_forward_tiled: need 0 <= B <= %d, the grid's second dimension (B=%d)",
+                   PRB_TILED_MAX_B, B);
+    PCCX_CHECK_ARG(S >= 16 && S % 16 == 0, "pccx_prob_forward_tiled: need S %% 16 == 0 (S=%d)", S);
+    PCCX_CHECK_ARG(d >= 1 && d <= 16 && L >= 1 && L <= 15 && d * L <= 128, "pccx_prob_forward_tiled: unsupported d=%d L=%d", d, L);
+    PCCX_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "pccx_prob_forward_tiled: workspace must be 16-byte aligned");
+    const int nwg = prob_feature_workgroups(S);
+    float *feature = workspace + (size_t)B * nwg * 256;   // a multiple of 256 floats past a 16-byte-aligned base
+    const int ntiles = S >> 4;
+    hipLaunchKernelGGL(prob_tiled_partial_kernel, dim3(nwg, B), dim3(256), 0, (hipStream_t)stream, centres, S, prob_blob, workspace);
+    PCCX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(prob_tiled_reduce_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, workspace, nwg, prob_blob, feature);
+    PCCX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(prob_tiled_rows_kernel, dim3((ntiles + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, centres, S, d, L,
+                       prob_blob, feature, pmf, cdf, cdf_int);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }

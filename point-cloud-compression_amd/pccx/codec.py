@@ -212,7 +212,7 @@ OCTREE_WIDE_MAX_S = 8192       # ... and their wide forms (pccx_octree_encode_wi
 class Codec:
     def __init__(self, ae, prob, K=256, ALPHA=2, N0=1024, octree_mode="reference", margin=0.01, matmul=None,
                  decoder_matmul=None, sa_matmul=None, pn_matmul=None, group_duplicates=True, knn_search="auto",
-                 max_centres=OCTREE_MAX_S, p_split=None, p_index=None, centres="fps", fps_block=8192):
+                 max_centres=OCTREE_MAX_S, p_split=None, p_index=None, centres="fps", fps_block=8192, prob_path="cloud"):
         """matmul: how the three transforms (SetAbstraction, PointNet, decoder) form their fp32 products --
         "f32" = v_mfma_f32_16x16x4_f32 (bit-for-bit a k-ordered fmaf chain), "bf16x3" = each fp32 operand split exactly into
         three bf16 pieces, six products per pair on the bf16 matrix cores, fp32 accumulate (fp32-level error, 2.6x the
@@ -245,7 +245,17 @@ class Codec:
         octree of whatever S points it was given): the three files are ones any decoder of this codec reads -- decompress,
         build_index, decompress_region and the reference's decompress.py, none of which takes this argument.  The choice does change
         the centres, hence the bytes and the quality (DESIGN.md section 4.5 has the measured cost).  A cloud of one block
-        (N <= fps_block) gets the exact indices and the same files as "fps"."""
+        (N <= fps_block) gets the exact indices and the same files as "fps".
+        prob_path: how compress, decompress and build_index evaluate the probability model.  "cloud" (the default) is the kernel that
+        gives each cloud to one workgroup, call for call as before: right for many clouds of 64 centres.  "tiles" deals the 16-centre
+        tiles of every cloud over the chip (ConditionalProbabilityModel.run(tiles=True)): for a whole room's 8192 centres, where one
+        workgroup would walk 512 tiles alone.  The integer CDF is the same function of the same centres bit
+        for bit, so the files are the same bytes and the two sides need NOT agree on it.  decompress(reuse_cdf=True) evaluates
+        nothing, and decompress_region's own path is tiled already: neither reads this argument."""
+        if prob_path not in ("cloud", "tiles"):
+            raise ValueError(f"prob_path must be 'cloud' or 'tiles', got {prob_path!r}")
+        self.prob_path = prob_path
+        self._prob_kw = {"tiles": True} if prob_path == "tiles" else {}      # "cloud": the former call, argument for argument
         from . import DEFAULT_MATMUL
         matmul = matmul or DEFAULT_MATMUL
         self.ae, self.prob = ae, prob
@@ -337,7 +347,7 @@ class Codec:
         patches = nn.knn.view(B * S, self.K, 3)
         raw, latent, q = self.ae.encode(patches, sa_matmul=self.sa_matmul, pn_matmul=self.pn_matmul, groups=groups)                      # compress.py:113-127
         with stage("prob"):
-            cdf_int = self.prob.run(rec, ("cdf_int",), distinct=self._distinct())["cdf_int"]                    # compress.py:131-134
+            cdf_int = self.prob.run(rec, ("cdf_int",), distinct=self._distinct(), **self._prob_kw)["cdf_int"]                    # compress.py:131-134
         with stage("range_encode"):
             if self.p_index is not None:
                 comp.p_index = models.range_encode_indexed(cdf_int, q.view(B, S * d), L, self.p_index * d, out=comp.p_bytes, nb=comp.p_nbytes)[2]
@@ -367,7 +377,7 @@ class Codec:
         cdf_int = getattr(comp, "_cdf_int", None) if reuse_cdf else None
         if cdf_int is None or cdf_int.shape[0] != B or cdf_int.shape[1] != S:
             with stage("prob"):
-                cdf_int = self.prob.run(rec, ("cdf_int",), distinct=self._distinct())["cdf_int"]                     # decompress.py:88-92
+                cdf_int = self.prob.run(rec, ("cdf_int",), distinct=self._distinct(), **self._prob_kw)["cdf_int"]                     # decompress.py:88-92
         with stage("range_decode"):
             if self.p_index is not None and comp.p_index is not None:
                 q = models.range_decode_indexed(cdf_int, comp.p_bytes, comp.p_nbytes, comp.p_index, L, self.p_index * d,
@@ -393,7 +403,7 @@ class Codec:
         with stage("octree_decode"):
             rec, _ = ops.octree_decode(comp.s_bytes, comp.s_nbytes, self.octree_mode, S)
         with stage("prob"):
-            cdf_int = self.prob.run(rec, ("cdf_int",), distinct=self._distinct())["cdf_int"]
+            cdf_int = self.prob.run(rec, ("cdf_int",), distinct=self._distinct(), **self._prob_kw)["cdf_int"]
         with stage("build_index"):
             comp.p_index = models.range_index_build(cdf_int, comp.p_bytes, comp.p_nbytes, self.ae.L, self.p_index * self.ae.d)
         comp.p_index_nbytes = None

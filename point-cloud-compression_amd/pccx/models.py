@@ -541,10 +541,13 @@ class ConditionalProbabilityModel(nn.Module):
         self._blob = blob.to(device)
         return self
 
-    def run(self, sampled_xyz, want=("pmf",), distinct=False):
+    def run(self, sampled_xyz, want=("pmf",), distinct=False, tiles=False):
         """sampled_xyz (B,S,3) -> dict with any of pmf (B,S,d,L), cdf (B,S,d,L+1), cdf_int (int32).
         distinct=True (clouds whose centres repeat, octree_mode "reference"): the fused kernel that evaluates each distinct centre of a
-        cloud once, for S <= 64 -- the same outputs bit for bit; other shapes take the usual path."""
+        cloud once, for S <= 64 -- the same outputs bit for bit; other shapes take the usual path.
+        tiles=True (opt-in; few clouds of many centres, a whole room's 8192): pccx_prob_forward_tiled, the 16-centre tiles of every
+        cloud dealt over the chip in three launches where the usual kernel gives a cloud to one workgroup -- the same outputs bit for
+        bit, so `distinct` is ignored under it.  Shapes outside the fused kernel's take the generic layers either way."""
         x = _f32c(sampled_xyz, "ConditionalProbabilityModel")
         B, S, _ = x.shape
         if not self.fused_ok(S):
@@ -552,6 +555,10 @@ class ConditionalProbabilityModel(nn.Module):
         if self._blob is None or self._blob.device != x.device:
             self.pack(x.device)
         r, ptrs = self._outputs(want, B, S, x.device)
+        if tiles:
+            ws = workspace("prob_tiled", max(int(_lib.load().pccx_prob_forward_tiled_workspace_floats(B, S)), 4), x.device)
+            _lib.call("pccx_prob_forward_tiled", x.data_ptr(), B, S, self.d, self.L, self._blob.data_ptr(), *ptrs, ws.data_ptr(), _stream())
+            return r
         fn = "pccx_prob_forward_distinct" if distinct and S <= 64 else "pccx_prob_forward"
         _lib.call(fn, x.data_ptr(), B, S, self.d, self.L, self._blob.data_ptr(), *ptrs, _stream())
         return r

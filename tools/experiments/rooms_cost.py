@@ -13,7 +13,18 @@ ceil(N / 16384), twice and four times that, up to 64 (fps_coop@G).  --codec N: a
 Codec(max_centres=8192): codec_whole and codec_blocks, ms per cloud, StageTimer's per-stage totals, bits per point, D1.
 --p-split G[,G...]: after codec_whole of every size, codec_whole_split@G = the same codec with Codec(p_split=G) on the same cloud with
 the same weights, the two layouts taking turns; a second table lists the range_encode / range_decode stages and the bits per point of
-every whole-cloud row.  --skip-blocks leaves codec_blocks out."""
+every whole-cloud row.  --skip-blocks leaves codec_blocks out.
+
+    python tools/experiments/rooms_cost.py --codec 65536,262144,524288,1048576 --p-split 64 --prob cloud,tiles --centres fps,blocks \
+        --prob-headline 1024x64 --out profiles/rooms_prob_tiles.jsonl
+
+--prob cloud,tiles (needs --p-split): the contenders become codec_whole_split@G[+blocks][+tiles] -- Codec(p_split=G) with
+centres="blocks" and / or prob_path="tiles" -- for every --centres (fps, blocks; default fps) and every --prob value, taking turns on
+the same cloud with the same weights; a third table lists ms per cloud, the `prob` stage (both sides of the codec), bpp and D1 of
+every row, and under it the two ratios of the condition stated for prob_path="tiles": the prob stage under tiles over the one under
+cloud, and the saving in ms per cloud over the saving in the prob stage, per size, centres and round.
+--prob-headline BxS: ConditionalProbabilityModel.run alone on B clouds of S centres, 8 distinct rows each as octree_mode "reference"
+leaves them (the headline batch is 1024x64): prob_cloud, prob_distinct and prob_tiles, integer CDF only, in the same rounds."""
 import argparse
 import json
 import os
@@ -56,7 +67,9 @@ def child_codec(case, what):
     prob = models.ConditionalProbabilityModel(L, d)
     prob.load_state_dict(ref_model.seeded_state_dict(prob, 4, gain=2.0))
     name, _, g = what.partition("@")
-    cd = codec.Codec(ae.pack("cuda"), prob.pack("cuda"), K=K, octree_mode="full", max_centres=codec.OCTREE_WIDE_MAX_S, p_split=int(g) if g else None)
+    g, *opts = g.split("+")
+    cd = codec.Codec(ae.pack("cuda"), prob.pack("cuda"), K=K, octree_mode="full", max_centres=codec.OCTREE_WIDE_MAX_S, p_split=int(g) if g else None,
+                     centres="blocks" if "blocks" in opts else "fps", prob_path="tiles" if "tiles" in opts else "cloud")
     pc = torch.from_numpy(synth.cad_batch(900, 1, N)).cuda()
     res = {}
     if name in ("codec_whole", "codec_whole_split"):
@@ -80,6 +93,24 @@ def child_codec(case, what):
                           d1_psnr=round(float(codec.d1_psnr(pc, res["out"].reshape(1, -1, 3), search="grid")[0]), 3), stages=stages)))
 
 
+def child_prob(case, what):
+    sys.path[:0] = [ROOT, PKG]
+    import torch
+    from oracle import ref_model
+    from pccx import models
+    B, S = (int(v) for v in case.split("x"))
+    prob = models.ConditionalProbabilityModel(7, 16)
+    prob.load_state_dict(ref_model.seeded_state_dict(prob, 4, gain=2.0))
+    prob.pack("cuda")
+    gen = torch.Generator().manual_seed(5)
+    rows = torch.randint(0, 256, (B, 8, 3), generator=gen).float() / 256                      # 8 distinct centres per cloud, on a grid
+    x = rows[:, torch.arange(S) % 8].contiguous().cuda()
+    kw = {"prob_cloud": {}, "prob_distinct": {"distinct": True}, "prob_tiles": {"tiles": True}}[what]
+    settle()
+    ms, reps = timed(lambda: prob.run(x, ("cdf_int",), **kw))
+    print(json.dumps(dict(case=case, what=what, ms=ms, reps=reps)))
+
+
 def run(mode, case, what, limit_s):
     cmd = ["timeout", "-k", "10", str(int(limit_s)), sys.executable, os.path.abspath(__file__), "--child", case, "--what", what, "--mode", mode]
     p = subprocess.run(cmd, capture_output=True, text=True)
@@ -95,24 +126,33 @@ def main():
     ap.add_argument("--codec", default="")
     ap.add_argument("--p-split", default="")
     ap.add_argument("--skip-blocks", action="store_true")
+    ap.add_argument("--prob", default="")
+    ap.add_argument("--centres", default="fps")
+    ap.add_argument("--prob-headline", default="")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None)
     ap.add_argument("--what", default=None)
     ap.add_argument("--mode", default=None)
     a = ap.parse_args()
     if a.child:
-        return {"fps": child_fps, "codec": child_codec}[a.mode](a.child, a.what)
+        return {"fps": child_fps, "codec": child_codec, "prob": child_prob}[a.mode](a.child, a.what)
     out = open(a.out, "a") if a.out else None
-    table, coder = {}, {}
+    table, coder, probs = {}, {}, {}
     codec_whats = ["codec_whole"] + [f"codec_whole_split@{int(g)}" for g in a.p_split.split(",") if g] + ([] if a.skip_blocks else ["codec_blocks"])
+    if a.prob:
+        if not a.p_split:
+            raise SystemExit("--prob needs --p-split G")
+        codec_whats = [f"codec_whole_split@{int(g)}" + ("+blocks" if c == "blocks" else "") + ("+tiles" if p == "tiles" else "")
+                       for g in a.p_split.split(",") if g for c in a.centres.split(",") if c for p in a.prob.split(",") if p]
     for r in range(a.rounds):
-        for mode, cases in (("fps", a.fps), ("codec", a.codec)):
+        for mode, cases in (("fps", a.fps), ("codec", a.codec), ("prob", a.prob_headline)):
             for case in [c for c in cases.split(",") if c]:
-                for what in (fps_whats(int(case)) if mode == "fps" else codec_whats):
+                for what in (fps_whats(int(case)) if mode == "fps" else ["prob_cloud", "prob_distinct", "prob_tiles"] if mode == "prob" else codec_whats):
                     rec = dict(run(mode, case, what, 300), round=r)
                     table.setdefault(f"{mode} {case}", {}).setdefault(what, []).append(rec["ms"])
                     if what.startswith("codec_whole"):
                         coder.setdefault((case, what), []).append((rec["stages"].get("range_encode", 0.0), rec["stages"].get("range_decode", 0.0), rec["bpp"]))
+                        probs.setdefault((case, what), []).append((rec["ms"], rec["stages"].get("prob", 0.0), rec["bpp"], rec["d1_psnr"]))
                     print(json.dumps(rec), flush=True)
                     if out:
                         out.write(json.dumps(rec) + "\n")
@@ -125,6 +165,16 @@ def main():
         lines += ["", "| points | figure | range_encode ms, each round | range_decode ms, each round | bpp |", "|---|---|---|---|---|"]
         for (case, what), v in coder.items():
             lines.append(f"| {case} | {what} | {', '.join(f'{e:.3f}' for e, _, _ in v)} | {', '.join(f'{d_:.3f}' for _, d_, _ in v)} | {v[0][2]:.4f} |")
+    if a.prob:
+        lines += ["", "| points | figure | ms per cloud, each round | prob ms, each round | bpp, each round | D1 dB, each round |", "|---|---|---|---|---|---|"]
+        for (case, what), v in probs.items():
+            lines.append(f"| {case} | {what} | " + " | ".join(", ".join(f"{row[i]:.{n}f}" for row in v) for i, n in ((0, 3), (1, 3), (2, 4), (3, 3))) + " |")
+        lines += ["", "| points | cloud -> tiles | prob tiles / prob cloud, each round | (ms cloud - ms tiles) / (prob cloud - prob tiles), each round |", "|---|---|---|---|"]
+        for (case, what), v in probs.items():
+            t = probs.get((case, what + "+tiles"))
+            if t is not None and not what.endswith("+tiles"):
+                lines.append(f"| {case} | {what} | {', '.join(f'{y[1] / x[1]:.4f}' for x, y in zip(v, t))} | "
+                             f"{', '.join(f'{(x[0] - y[0]) / (x[1] - y[1]):.3f}' for x, y in zip(v, t))} |")
     print("\n" + "\n".join(lines))
     if out:
         out.write("\n".join(lines) + "\n")
