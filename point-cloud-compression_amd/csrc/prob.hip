@@ -17,8 +17,8 @@
 #include "common.h"
 #include "mfma_chain.h"
 
-// ---- the stages of prob_forward_kernel as functions, for the region kernels (pccx_prob_feature, pccx_prob_rows) and the
-// tiled whole-cloud kernels (pccx_prob_forward_tiled) at the end of this file: the same statements in the same order, so a centre's chain is prob_forward_kernel's k-tile for k-tile (a column of
+// ---- the stages of prob_forward_kernel as functions, for the tiled kernels (pccx_prob_feature, pccx_prob_rows,
+// pccx_prob_forward_tiled) at the end of this file: the same statements in the same order, so a centre's chain is prob_forward_kernel's k-tile for k-tile (a column of
 // an MFMA tile depends on nothing but its own input column).  prob_forward_kernel itself keeps its own text below: calling these
 // from it moved its register allocation (93 against 95 SGPRs, another instruction order), and that kernel is the headline's.
 // tests/test_region.py pins the two against each other bit for bit.  bl = the laundered blob pointer of the caller (opaque_uniform).
@@ -572,156 +572,30 @@ extern "C" int pccx_prob_forward_distinct(const float *centres, int B, int S, in
 }
 
 // ------------------------------------------------------------------------------------------
-// The same function for a LIST of rows of one cloud (region decode): prob_forward_kernel cut at the one
-// quantity that couples a cloud's centres, pass 1's maximum.
-//   prob_feature_partial_kernel: pass 1 with the cloud's 16-centre tiles dealt over up to 64 workgroups x 4 waves; each workgroup
-//       leaves its 256 maxima (over its four waves) in the workspace.  fmaxf is exact in any grouping, so the maximum over the
-//       partials is prob_forward_kernel's sfeat[] bit for bit (the -INFINITY start and the fmaxf(., 0) stay as there).
-//   prob_feature_reduce_kernel: one workgroup takes that maximum and runs pass 1b with prob_forward_kernel's own call and wave
-//       split; the 512 numbers su[] go to HBM.  Two launches in stream order: no cooperative launch, no flag, no spin.
-//   prob_rows_kernel: pass 2 + softmax + integer CDF for compact rows: compact row r stands for row seg_idx[r / G] * G + r % G of
-//       the cloud (clamped into [0, S - 1]: the rows past S of a ragged last segment are computed on row S - 1 and never read).  A wave
-//       takes 16 compact rows, a workgroup four tiles in ONE pass over the weight ring; all four waves walk every chunk, an idle
-//       wave of the last workgroup on a clamped tile whose result it drops, and ws.drain() runs before the workgroup retires.
+// The same function cut at the one quantity that couples a cloud's centres, pass 1's maximum, so that a cloud's tiles are dealt
+// over the chip.  prob_forward_kernel gives a cloud to ONE workgroup, which is right for 1024 clouds of 64
+// centres and leaves 255 CUs idle for one cloud of 8192.  Two users: region decode (pccx_prob_feature + pccx_prob_rows: one cloud,
+// a LIST of its rows) and the opt-in whole-cloud path Codec(prob_path="tiles") (pccx_prob_forward_tiled: a batch, every row).
+// The cloud is blockIdx.y in all three kernels; launches follow in stream order: no cooperative launch, no flag, no spin.
+//   prob_feature_partial_kernel, grid (nwg, B): pass 1 with the cloud's 16-centre tiles dealt over up to 64 workgroups x 4 waves;
+//       each workgroup leaves its 256 maxima (over its four waves) in partial[b][wg][256].  fmaxf is exact in any grouping, so the
+//       maximum over the partials is prob_forward_kernel's sfeat[] bit for bit (the -INFINITY start and the fmaxf(., 0) stay as
+//       there).  A wave that gets no tile leaves -INFINITY, which no fmaxf keeps (every cloud has a tile).
+//   prob_feature_reduce_kernel, grid (1, B): one workgroup takes that maximum and runs pass 1b with prob_forward_kernel's own call
+//       and wave split; the 512 numbers su[] go to feature[b][512] in HBM.
+//   prob_rows_kernel<LIST>, grid (ceil(rows / 64), B): pass 2 + softmax + tables.  A wave takes 16 rows, a workgroup four tiles in
+//       ONE pass over the weight ring; all four waves walk every chunk, an idle wave of the last workgroup on a clamped tile whose
+//       result it drops, and ws.drain() runs before the workgroup retires.
+//       LIST = false: row r is centre r of the cloud (S % 16 == 0: no ragged tile), all three outputs.
+//       LIST = true : compact row r stands for row seg_idx[r / G] * G + r % G of the cloud (clamped into [0, S - 1]: the rows past S
+//       of a ragged last segment are computed on row S - 1 and never read); cdf_int alone, compact.  A compile-time branch: it sits
+//       in the wave's address computation in front of a 220-VGPR body.
 // ------------------------------------------------------------------------------------------
 #define PRB_FEATURE_MAX_WG 64
+#define PRB_TILED_MAX_B 65535                             // gridDim.y
 
 __global__ __launch_bounds__(256, 2) void prob_feature_partial_kernel(const float *__restrict__ centres, int S,
                                                                       const float *__restrict__ blob, float *__restrict__ partial)
-{
-    __shared__ float smax[4][256];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int g = lane >> 4, n = lane & 15;
-    const int ntiles = S >> 4;
-    f32x4 run[16];
-#pragma unroll
-    for (int mt = 0; mt < 16; ++mt) run[mt][0] = run[mt][1] = run[mt][2] = run[mt][3] = -INFINITY;
-    for (int tile = blockIdx.x * 4 + w; tile < ntiles; tile += 4 * gridDim.x) {
-        const float *bl = opaque_uniform(blob);
-        prob_pn_tile(bl, centres + 3 * (tile * 16 + n), g, lane, run);
-    }
-    if (n == 0)
-#pragma unroll
-        for (int mt = 0; mt < 16; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) smax[w][16 * mt + 4 * g + r] = run[mt][r];
-    __syncthreads();
-    partial[(size_t)blockIdx.x * 256 + tid] = fmaxf(fmaxf(smax[0][tid], smax[1][tid]), fmaxf(smax[2][tid], smax[3][tid]));
-}
-
-__global__ __launch_bounds__(256, 2) void prob_feature_reduce_kernel(const float *__restrict__ partial, int nwg,
-                                                                     const float *__restrict__ blob, float *__restrict__ feature)
-{
-    __shared__ __attribute__((aligned(16))) float sfeat[256];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int g = lane >> 4, n = lane & 15;
-    const int wu = __builtin_amdgcn_readfirstlane(w);
-    float m = partial[tid];
-    for (int j = 1; j < nwg; ++j) m = fmaxf(m, partial[(size_t)j * 256 + tid]);
-    sfeat[tid] = m;
-    __syncthreads();
-    prob_feature_u(opaque_uniform(blob), sfeat, feature, lane, g, n, wu);
-}
-
-__global__ __launch_bounds__(256, 2) void prob_rows_kernel(const float *__restrict__ centres, int S, int d, int L,
-                                                           const float *__restrict__ blob, const float *__restrict__ feature,
-                                                           const int32_t *__restrict__ seg_idx, int n_seg, int G,
-                                                           int32_t *__restrict__ cdf_int)
-{
-    __shared__ __attribute__((aligned(16))) f32x4 swt[4 * PRB_WS_CHUNK * 64];   // 32 KiB weight ring, four chunks deep
-    __shared__ __attribute__((aligned(16))) float su[512];
-    __shared__ __attribute__((aligned(16))) float slog[4][16][128];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wu = __builtin_amdgcn_readfirstlane(w);
-    const int nrows = n_seg * G, ntiles = (nrows + 15) >> 4;
-    WStreamT<PRB_WS_CHUNK, 4, 4> ws{blob + PRB_STREAM, swt, PRB_STREAM_CHUNKS, lane, wu, false};   // one pass: nothing is issued past it
-    ws.prologue();
-    if (tid < 128) *(f32x4 *)(su + 4 * tid) = *(const f32x4 *)(feature + 4 * tid);
-    __syncthreads();
-
-    const int tile = blockIdx.x * 4 + w;
-    {
-        const float *bl = opaque_uniform(blob);
-        ws.g = bl + PRB_STREAM;
-        // lane indices from a laundered lane id, as in prob_forward_kernel
-        int lane2 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        asm volatile("" : "+v"(lane2));
-        const int g = lane2 >> 4, n = lane2 & 15;
-        ws.lane = lane2;
-        int r = (tile < ntiles ? tile : ntiles - 1) * 16 + n;
-        r = r < nrows ? r : nrows - 1;                        // the ragged last tile: walked on its last row, not stored
-        int c = seg_idx[r / G] * G + r % G;
-        c = c < 0 ? 0 : (c < S ? c : S - 1);                  // whatever the list holds, the address stays inside the cloud
-        f32x4 a2[1][8];
-        prob_mlp_tile(ws, bl, su, centres + 3 * c, g, a2);
-        if (tile < ntiles)
-#pragma unroll
-            for (int mt = 0; mt < 8; ++mt) *(f32x4 *)(&slog[w][n][16 * mt + 4 * g]) = a2[0][mt];
-    }
-    __syncthreads();
-    if (tile < ntiles) {
-        const int left = nrows - tile * 16;
-        prob_tables_tile(slog[w], lane, left < 16 ? left : 16, d, L, (size_t)tile * 16, nullptr, nullptr, cdf_int);
-    }
-    ws.drain();                                           // no DMA may land after the workgroup retires
-}
-
-static int prob_feature_workgroups(int S)
-{
-    const int rounds = ((S >> 4) + 3) / 4;                // workgroup rounds of four tiles
-    return rounds < 1 ? 1 : (rounds > PRB_FEATURE_MAX_WG ? PRB_FEATURE_MAX_WG : rounds);
-}
-
-extern "C" size_t pccx_prob_feature_workspace_floats(int S)
-{
-    return S < 16 ? 0 : (size_t)prob_feature_workgroups(S) * 256;
-}
-
-extern "C" int pccx_prob_feature(const float *centres, int S, const float *prob_blob, float *workspace, float *feature, void *stream)
-{
-    PCCX_CHECK_ARG(centres && prob_blob && workspace && feature, "pccx_prob_feature: null pointer");
-    PCCX_CHECK_ARG(S >= 16 && S % 16 == 0, "pccx_prob_feature: need S %% 16 == 0 (S=%d)", S);
-    PCCX_CHECK_ARG(((uintptr_t)feature & 15) == 0, "pccx_prob_feature: feature must be 16-byte aligned");
-    const int nwg = prob_feature_workgroups(S);
-    hipLaunchKernelGGL(prob_feature_partial_kernel, dim3(nwg), dim3(256), 0, (hipStream_t)stream, centres, S, prob_blob, workspace);
-    PCCX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(prob_feature_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, workspace, nwg, prob_blob, feature);
-    PCCX_CHECK_LAUNCH();
-    return PCCX_OK;
-}
-
-extern "C" int pccx_prob_rows(const float *centres, int S, int d, int L, const float *prob_blob, const float *feature,
-                              const int32_t *seg_idx, int n_seg, int G, int32_t *cdf_int, void *stream)
-{
-    if (n_seg == 0) return PCCX_OK;   // empty list: nothing to do, pointers may be null
-    PCCX_CHECK_ARG(centres && prob_blob && feature && seg_idx && cdf_int, "pccx_prob_rows: null pointer");
-    PCCX_CHECK_ARG(S >= 16 && S % 16 == 0, "pccx_prob_rows: need S %% 16 == 0 (S=%d)", S);
-    PCCX_CHECK_ARG(d >= 1 && d <= 16 && L >= 1 && L <= 15 && d * L <= 128, "pccx_prob_rows: unsupported d=%d L=%d", d, L);
-    PCCX_CHECK_ARG(G >= 1 && n_seg >= 0 && n_seg <= (S + G - 1) / G, "pccx_prob_rows: %d segments of G=%d patches listed for S=%d", n_seg, G, S);
-    PCCX_CHECK_ARG(((uintptr_t)feature & 15) == 0, "pccx_prob_rows: feature must be 16-byte aligned");
-    const int ntiles = (int)(((int64_t)n_seg * G + 15) >> 4);
-    hipLaunchKernelGGL(prob_rows_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, centres, S, d, L, prob_blob, feature,
-                       seg_idx, n_seg, G, cdf_int);
-    PCCX_CHECK_LAUNCH();
-    return PCCX_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// The same function for a BATCH of whole clouds with the tiles of every cloud dealt over the chip (opt-in: Codec(prob_path="tiles"),
-// DESIGN.md section 4.5): the three region kernels above with the cloud taken from blockIdx.y and without the list.
-// prob_forward_kernel gives a cloud to ONE workgroup, which is right for 1024 clouds of 64 centres and leaves 255 CUs idle for one
-// cloud of 8192.  Three launches in stream order: no cooperative launch, no flag, no spin.
-//   prob_tiled_partial_kernel, grid (nwg, B): prob_feature_partial_kernel's body on cloud blockIdx.y; its 256 maxima go to
-//       partial[b][wg][256].  A wave that gets no tile leaves -INFINITY, which no fmaxf keeps (every cloud has a tile).
-//   prob_tiled_reduce_kernel, grid (B): the maximum over the cloud's nwg partials, pass 1b, 512 floats to feature[b][512].
-//   prob_tiled_rows_kernel, grid (ceil(S/64), B): prob_rows_kernel's body with compact row r = row r of cloud blockIdx.y and all
-//       three outputs.  All four waves walk every chunk; a wave past the last tile walks the last tile and stores nothing.
-// The existing kernels keep their own text: nothing above this line changed, so their register allocation did not either.
-// ------------------------------------------------------------------------------------------
-#define PRB_TILED_MAX_B 65535                             // gridDim.y
-
-__global__ __launch_bounds__(256, 2) void prob_tiled_partial_kernel(const float *__restrict__ centres, int S,
-                                                                    const float *__restrict__ blob, float *__restrict__ partial)
 {
     __shared__ float smax[4][256];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -745,32 +619,34 @@ __global__ __launch_bounds__(256, 2) void prob_tiled_partial_kernel(const float 
         fmaxf(fmaxf(smax[0][tid], smax[1][tid]), fmaxf(smax[2][tid], smax[3][tid]));
 }
 
-__global__ __launch_bounds__(256, 2) void prob_tiled_reduce_kernel(const float *__restrict__ partial, int nwg,
-                                                                   const float *__restrict__ blob, float *__restrict__ feature)
+__global__ __launch_bounds__(256, 2) void prob_feature_reduce_kernel(const float *__restrict__ partial, int nwg,
+                                                                     const float *__restrict__ blob, float *__restrict__ feature)
 {
     __shared__ __attribute__((aligned(16))) float sfeat[256];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int g = lane >> 4, n = lane & 15;
     const int wu = __builtin_amdgcn_readfirstlane(w);
-    const float *pp = partial + (size_t)blockIdx.x * nwg * 256;
+    const float *pp = partial + (size_t)blockIdx.y * nwg * 256;
     float m = pp[tid];
     for (int j = 1; j < nwg; ++j) m = fmaxf(m, pp[(size_t)j * 256 + tid]);
     sfeat[tid] = m;
     __syncthreads();
-    prob_feature_u(opaque_uniform(blob), sfeat, feature + (size_t)blockIdx.x * 512, lane, g, n, wu);
+    prob_feature_u(opaque_uniform(blob), sfeat, feature + (size_t)blockIdx.y * 512, lane, g, n, wu);
 }
 
-__global__ __launch_bounds__(256, 2) void prob_tiled_rows_kernel(const float *__restrict__ centres, int S, int d, int L,
-                                                                 const float *__restrict__ blob, const float *__restrict__ feature,
-                                                                 float *__restrict__ pmf, float *__restrict__ cdf,
-                                                                 int32_t *__restrict__ cdf_int)
+template <bool LIST>
+__global__ __launch_bounds__(256, 2) void prob_rows_kernel(const float *__restrict__ centres, int S, int d, int L,
+                                                           const float *__restrict__ blob, const float *__restrict__ feature,
+                                                           const int32_t *__restrict__ seg_idx, int n_seg, int G,
+                                                           float *__restrict__ pmf, float *__restrict__ cdf,
+                                                           int32_t *__restrict__ cdf_int)
 {
     __shared__ __attribute__((aligned(16))) f32x4 swt[4 * PRB_WS_CHUNK * 64];   // 32 KiB weight ring, four chunks deep
     __shared__ __attribute__((aligned(16))) float su[512];
     __shared__ __attribute__((aligned(16))) float slog[4][16][128];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wu = __builtin_amdgcn_readfirstlane(w);
-    const int ntiles = S >> 4;
+    const int nrows = LIST ? n_seg * G : S, ntiles = (nrows + 15) >> 4;
     const size_t b = blockIdx.y;
     WStreamT<PRB_WS_CHUNK, 4, 4> ws{blob + PRB_STREAM, swt, PRB_STREAM_CHUNKS, lane, wu, false};   // one pass: nothing is issued past it
     ws.prologue();
@@ -786,7 +662,12 @@ __global__ __launch_bounds__(256, 2) void prob_tiled_rows_kernel(const float *__
         asm volatile("" : "+v"(lane2));
         const int g = lane2 >> 4, n = lane2 & 15;
         ws.lane = lane2;
-        const int c = (tile < ntiles ? tile : ntiles - 1) * 16 + n;     // S % 16 == 0: no ragged tile; always inside the cloud
+        int c = (tile < ntiles ? tile : ntiles - 1) * 16 + n;
+        if (LIST) {
+            const int r = c < nrows ? c : nrows - 1;              // the ragged last tile: walked on its last row, not stored
+            c = seg_idx[r / G] * G + r % G;
+            c = c < 0 ? 0 : (c < S ? c : S - 1);                  // whatever the list holds, the address stays inside the cloud
+        }
         f32x4 a2[1][8];
         prob_mlp_tile(ws, bl, su, centres + (b * S + c) * 3, g, a2);
         if (tile < ntiles)
@@ -794,8 +675,58 @@ __global__ __launch_bounds__(256, 2) void prob_tiled_rows_kernel(const float *__
             for (int mt = 0; mt < 8; ++mt) *(f32x4 *)(&slog[w][n][16 * mt + 4 * g]) = a2[0][mt];
     }
     __syncthreads();
-    if (tile < ntiles) prob_tables_tile(slog[w], lane, 16, d, L, b * S + (size_t)tile * 16, pmf, cdf, cdf_int);
+    if (tile < ntiles) {
+        const int left = nrows - tile * 16;
+        prob_tables_tile(slog[w], lane, LIST && left < 16 ? left : 16, d, L, (LIST ? 0 : b * S) + (size_t)tile * 16,
+                         LIST ? nullptr : pmf, LIST ? nullptr : cdf, cdf_int);
+    }
     ws.drain();                                           // no DMA may land after the workgroup retires
+}
+
+static int prob_feature_workgroups(int S)
+{
+    const int rounds = ((S >> 4) + 3) / 4;                // workgroup rounds of four tiles
+    return rounds < 1 ? 1 : (rounds > PRB_FEATURE_MAX_WG ? PRB_FEATURE_MAX_WG : rounds);
+}
+
+// pass 1 + 1b of B clouds: partial[B][nwg][256] -> feature[B][512]
+static int prob_feature_launch(const float *centres, int B, int S, const float *prob_blob, float *partial, float *feature, hipStream_t stream)
+{
+    const int nwg = prob_feature_workgroups(S);
+    hipLaunchKernelGGL(prob_feature_partial_kernel, dim3(nwg, B), dim3(256), 0, stream, centres, S, prob_blob, partial);
+    PCCX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(prob_feature_reduce_kernel, dim3(1, B), dim3(256), 0, stream, partial, nwg, prob_blob, feature);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+extern "C" size_t pccx_prob_feature_workspace_floats(int S)
+{
+    return S < 16 ? 0 : (size_t)prob_feature_workgroups(S) * 256;
+}
+
+extern "C" int pccx_prob_feature(const float *centres, int S, const float *prob_blob, float *workspace, float *feature, void *stream)
+{
+    PCCX_CHECK_ARG(centres && prob_blob && workspace && feature, "pccx_prob_feature: null pointer");
+    PCCX_CHECK_ARG(S >= 16 && S % 16 == 0, "pccx_prob_feature: need S %% 16 == 0 (S=%d)", S);
+    PCCX_CHECK_ARG(((uintptr_t)feature & 15) == 0, "pccx_prob_feature: feature must be 16-byte aligned");
+    return prob_feature_launch(centres, 1, S, prob_blob, workspace, feature, (hipStream_t)stream);
+}
+
+extern "C" int pccx_prob_rows(const float *centres, int S, int d, int L, const float *prob_blob, const float *feature,
+                              const int32_t *seg_idx, int n_seg, int G, int32_t *cdf_int, void *stream)
+{
+    if (n_seg == 0) return PCCX_OK;   // empty list: nothing to do, pointers may be null
+    PCCX_CHECK_ARG(centres && prob_blob && feature && seg_idx && cdf_int, "pccx_prob_rows: null pointer");
+    PCCX_CHECK_ARG(S >= 16 && S % 16 == 0, "pccx_prob_rows: need S %% 16 == 0 (S=%d)", S);
+    PCCX_CHECK_ARG(d >= 1 && d <= 16 && L >= 1 && L <= 15 && d * L <= 128, "pccx_prob_rows: unsupported d=%d L=%d", d, L);
+    PCCX_CHECK_ARG(G >= 1 && n_seg >= 0 && n_seg <= (S + G - 1) / G, "pccx_prob_rows: %d segments of G=%d patches listed for S=%d", n_seg, G, S);
+    PCCX_CHECK_ARG(((uintptr_t)feature & 15) == 0, "pccx_prob_rows: feature must be 16-byte aligned");
+    const int ntiles = (int)(((int64_t)n_seg * G + 15) >> 4);
+    hipLaunchKernelGGL(prob_rows_kernel<true>, dim3((ntiles + 3) / 4), dim3(256), 0, (hipStream_t)stream, centres, S, d, L, prob_blob,
+                       feature, seg_idx, n_seg, G, (float *)nullptr, (float *)nullptr, cdf_int);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
 }
 
 extern "C" size_t pccx_prob_forward_tiled_workspace_floats(int B, int S)
@@ -815,15 +746,11 @@ extern "C" int pccx_prob_forward_tiled(const float *centres, int B, int S, int d
     PCCX_CHECK_ARG(S >= 16 && S % 16 == 0, "pccx_prob_forward_tiled: need S %% 16 == 0 (S=%d)", S);
     PCCX_CHECK_ARG(d >= 1 && d <= 16 && L >= 1 && L <= 15 && d * L <= 128, "pccx_prob_forward_tiled: unsupported d=%d L=%d", d, L);
     PCCX_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "pccx_prob_forward_tiled: workspace must be 16-byte aligned");
-    const int nwg = prob_feature_workgroups(S);
-    float *feature = workspace + (size_t)B * nwg * 256;   // a multiple of 256 floats past a 16-byte-aligned base
-    const int ntiles = S >> 4;
-    hipLaunchKernelGGL(prob_tiled_partial_kernel, dim3(nwg, B), dim3(256), 0, (hipStream_t)stream, centres, S, prob_blob, workspace);
-    PCCX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(prob_tiled_reduce_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, workspace, nwg, prob_blob, feature);
-    PCCX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(prob_tiled_rows_kernel, dim3((ntiles + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, centres, S, d, L,
-                       prob_blob, feature, pmf, cdf, cdf_int);
+    float *feature = workspace + (size_t)B * prob_feature_workgroups(S) * 256;   // a multiple of 256 floats past a 16-byte-aligned base
+    const int rc = prob_feature_launch(centres, B, S, prob_blob, workspace, feature, (hipStream_t)stream);
+    if (rc != PCCX_OK) return rc;
+    hipLaunchKernelGGL(prob_rows_kernel<false>, dim3(((S >> 4) + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, centres, S, d, L,
+                       prob_blob, feature, (const int32_t *)nullptr, 0, 0, pmf, cdf, cdf_int);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }

@@ -44,6 +44,9 @@ struct BitWriter {
     }
 };
 
+// A row's byte count as the decoders take it: cut to the row before anything is read; the encoder's overflow mark (negative) reads as 0.
+__device__ __forceinline__ int rc_row_bytes(int count, int stride) { return count < 0 ? 0 : (count > stride ? stride : count); }
+
 // The entry of the index (entry_index.h) a coder is at: its interval, the bits behind it (emitted plus pending on the encoder,
 // shifted in beyond the first 32 on the decoder -- the same number) and whether an underflow run is pending.  One 12-byte store.
 // Outside the coder's contract -- a table with a zero-width symbol can drive high below low (see `fix` in rc_encode_wave) -- the state
@@ -157,7 +160,7 @@ __device__ __forceinline__ void rc_decode_lane(const int32_t *__restrict__ cdf_i
         entry += PCCX_INDEX_HEADER_BYTES / 4;
     }
     const uint8_t *buf = in + (size_t)b * stride;
-    const int nb = nbytes[b] < 0 ? 0 : (nbytes[b] > stride ? stride : nbytes[b]);
+    const int nb = rc_row_bytes(nbytes[b], stride);
     int pos = 0, cached = 0;
     unsigned cache = 0;
     unsigned low = 0u, high = 0xFFFFFFFFu, value = 0u;
@@ -477,7 +480,7 @@ __global__ __launch_bounds__(64) void range_decode_wave_kernel(const int32_t *__
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
     const int b = blockIdx.x;
-    const int nb = nbytes[b] < 0 ? 0 : (nbytes[b] > stride ? stride : nbytes[b]);
+    const int nb = rc_row_bytes(nbytes[b], stride);
     rc_decode_wave(rc_smem, cdf_int + (size_t)b * nsym * Lp, in + (size_t)b * stride, stride, nb, nsym, Lp, sym_offset,
                    latent_q + (size_t)b * nsym);
 }
@@ -661,27 +664,79 @@ __global__ __launch_bounds__(64) void range_split_check_kernel(const uint8_t *__
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     // a count beyond the row is cut to the row before anything is read: such a file then fails its own length sum (status 3)
-    const int nb = nbytes[b] < 0 ? 0 : (nbytes[b] > stride ? stride : nbytes[b]);
+    const int nb = rc_row_bytes(nbytes[b], stride);
     status[b] = pccx_split_stream_check(in + (size_t)b * stride, nb, nsym, seg_sym, segcap, offsets + (size_t)b * (P + 1));
 }
 
+// The segment a wave of the per-segment decoders (grid (waves, B)) takes: which one of cloud blockIdx.y (p), its symbol count (n: the
+// last segment may be ragged) and its first table / output row.  Two cases:
+//   LIST = false (whole batch) : wave blockIdx.x takes segment blockIdx.x, rows in place at b * nsym + p * seg_sym;
+//   LIST = true (region decode): wave j takes segment seg_idx[j], cut into [0, P), of ONE cloud (B = 1), rows compact at j * seg_sym.
+// Either way only that segment's bytes are read, so no byte of an unlisted segment is touched.  LIST is a template argument and
+// seg_idx the kernels' last argument, so that the whole-batch kernels keep their instructions and the place of their decode loop: a
+// run-time test of seg_idx in front of it cost the indexed decoder 5 us of 280 (128 segments of 1024 symbols).
+struct RcSegment {
+    int p, n, first;                                                   // first = p * seg_sym, the segment's first symbol of its cloud
+};
+template <bool LIST>
+__device__ __forceinline__ RcSegment rc_segment(const int32_t *__restrict__ seg_idx, int nsym, int seg_sym, int P)
+{
+    RcSegment s;
+    s.p = blockIdx.x;
+    if (LIST) {
+        const int p = (int)rc_uni((unsigned)seg_idx[blockIdx.x]);
+        s.p = p < 0 ? 0 : (p > P - 1 ? P - 1 : p);
+    }
+    s.first = s.p * seg_sym;                                           // < nsym: p < P
+    s.n = nsym - s.first < seg_sym ? nsym - s.first : seg_sym;
+    return s;
+}
+// its rows of an array of `width` words per symbol (the tables: L + 1, the output: 1), formed where they are addressed
+template <bool LIST, class T>
+__device__ __forceinline__ T *rc_segment_rows(T *base, const RcSegment &s, int nsym, int seg_sym, int width)
+{
+    const int j = blockIdx.x, b = blockIdx.y;
+    return LIST ? base + (size_t)j * seg_sym * width : base + ((size_t)b * nsym + s.first) * width;
+}
+
+template <bool LIST>
 __global__ __launch_bounds__(64) void range_decode_split_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in, int stride,
                                                                 const int32_t *__restrict__ offsets, int nsym, int seg_sym, int P, int Lp,
-                                                                int sym_offset, int segcap, float *__restrict__ latent_q)
+                                                                int sym_offset, int segcap, float *__restrict__ latent_q,
+                                                                const int32_t *__restrict__ seg_idx)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
-    const int p = blockIdx.x, b = blockIdx.y;
-    const int first = p * seg_sym;
-    const int n = nsym - first < seg_sym ? nsym - first : seg_sym;
-    const int32_t *off = offsets + (size_t)b * (P + 1) + p;
+    const int b = blockIdx.y;
+    const RcSegment s = rc_segment<LIST>(seg_idx, nsym, seg_sym, P);
+    const int32_t *off = offsets + (size_t)b * (P + 1) + s.p;
     // the check kernel's offsets: 0 <= off[0] <= off[1] <= min(nbytes, stride), lengths <= segcap on status 0 and 0 otherwise; the
     // clamps restate that here, where the addresses are formed
     int at = (int)rc_uni((unsigned)off[0]), end = (int)rc_uni((unsigned)off[1]);
     at = at < 0 ? 0 : (at > stride ? stride : at);
     end = end < at ? at : (end > stride ? stride : end);
     const int nb = end - at > segcap ? segcap : end - at;
-    rc_decode_wave(rc_smem, cdf_int + ((size_t)b * nsym + first) * Lp, in + (size_t)b * stride + at, segcap, nb, n, Lp, sym_offset,
-                   latent_q + (size_t)b * nsym + first);
+    rc_decode_wave(rc_smem, rc_segment_rows<LIST>(cdf_int, s, nsym, seg_sym, Lp), in + (size_t)b * stride + at, segcap, nb, s.n, Lp, sym_offset,
+                   rc_segment_rows<LIST>(latent_q, s, nsym, seg_sym, 1));
+}
+
+// Both split decoders: the check kernel (status per cloud, offsets in workspace), then one wave per segment; seg_idx null: whole batch.
+static int rc_decode_split_launch(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes, int B, int nsym, int seg_sym,
+                                  int L, const int32_t *seg_idx, int n_waves, float *latent_q, int32_t *status, void *workspace,
+                                  hipStream_t stream)
+{
+    const int P = (int)pccx_split_segments(nsym, seg_sym), segcap = rc_split_segcap(seg_sym);
+    int32_t *offsets = (int32_t *)workspace;
+    hipLaunchKernelGGL(range_split_check_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, in, stride, nbytes, B, nsym, seg_sym, P, segcap,
+                       status, offsets);
+    PCCX_CHECK_LAUNCH();
+    if (n_waves > 0) {
+        const auto kernel = seg_idx ? range_decode_split_kernel<true> : range_decode_split_kernel<false>;
+        hipLaunchKernelGGL(kernel, dim3(n_waves, B), dim3(64),
+                           rc_decode_lds(seg_sym, L, segcap), stream, cdf_int, in, stride, offsets, nsym, seg_sym, P, L + 1, L / 2, segcap,
+                           latent_q, seg_idx);
+        PCCX_CHECK_LAUNCH();
+    }
+    return PCCX_OK;
 }
 
 static int rc_split_check_args(const char *who, int B, int nsym, int seg_sym, int L)
@@ -725,41 +780,10 @@ extern "C" int pccx_range_decode_split(const int32_t *cdf_int, const uint8_t *in
     if (B == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
     const int rc = rc_split_check_args("pccx_range_decode_split", B, nsym, seg_sym, L);
     if (rc != PCCX_OK) return rc;
-    const int P = (int)pccx_split_segments(nsym, seg_sym), segcap = rc_split_segcap(seg_sym);
     PCCX_CHECK_ARG(in && nbytes && status && workspace && (nsym == 0 || (cdf_int && latent_q)), "pccx_range_decode_split: null pointer");
     PCCX_CHECK_ARG(stride >= 1, "pccx_range_decode_split: bad shape (stride=%d)", stride);
-    int32_t *offsets = (int32_t *)workspace;
-    hipLaunchKernelGGL(range_split_check_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, in, stride, nbytes, B, nsym, seg_sym, P,
-                       segcap, status, offsets);
-    PCCX_CHECK_LAUNCH();
-    if (P > 0) {
-        hipLaunchKernelGGL(range_decode_split_kernel, dim3(P, B), dim3(64), rc_decode_lds(seg_sym, L, segcap), (hipStream_t)stream, cdf_int, in,
-                           stride, offsets, nsym, seg_sym, P, L + 1, L / 2, segcap, latent_q);
-        PCCX_CHECK_LAUNCH();
-    }
-    return PCCX_OK;
-}
-
-// The listed form (region decode): wave j decodes segment seg_idx[j] of ONE cloud's file with table rows and output rows
-// j * seg_sym ..., both compact.  A thin caller of rc_decode_wave like the kernel above; the bytes it reads are the directory's
-// offsets of that segment alone, so no byte of an unlisted segment is touched.  An index outside [0, P) is cut into it.
-__global__ __launch_bounds__(64) void range_decode_split_list_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in,
-                                                                     int stride, const int32_t *__restrict__ offsets,
-                                                                     const int32_t *__restrict__ seg_idx, int nsym, int seg_sym, int P,
-                                                                     int Lp, int sym_offset, int segcap, float *__restrict__ latent_q)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
-    const int j = blockIdx.x;
-    int p = (int)rc_uni((unsigned)seg_idx[j]);
-    p = p < 0 ? 0 : (p > P - 1 ? P - 1 : p);
-    const int first = p * seg_sym;
-    const int n = nsym - first < seg_sym ? nsym - first : seg_sym;     // the ragged last segment, as range_decode_split_kernel
-    const int32_t *off = offsets + p;
-    int at = (int)rc_uni((unsigned)off[0]), end = (int)rc_uni((unsigned)off[1]);
-    at = at < 0 ? 0 : (at > stride ? stride : at);
-    end = end < at ? at : (end > stride ? stride : end);
-    const int nb = end - at > segcap ? segcap : end - at;
-    rc_decode_wave(rc_smem, cdf_int + (size_t)j * seg_sym * Lp, in + at, segcap, nb, n, Lp, sym_offset, latent_q + (size_t)j * seg_sym);
+    return rc_decode_split_launch(cdf_int, in, stride, nbytes, B, nsym, seg_sym, L, nullptr, (int)pccx_split_segments(nsym, seg_sym), latent_q,
+                                  status, workspace, (hipStream_t)stream);
 }
 
 extern "C" int pccx_range_decode_split_list(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes, int nsym,
@@ -768,21 +792,13 @@ extern "C" int pccx_range_decode_split_list(const int32_t *cdf_int, const uint8_
 {
     const int rc = rc_split_check_args("pccx_range_decode_split_list", 1, nsym, seg_sym, L);
     if (rc != PCCX_OK) return rc;
-    const int P = (int)pccx_split_segments(nsym, seg_sym), segcap = rc_split_segcap(seg_sym);
+    const int P = (int)pccx_split_segments(nsym, seg_sym);
     PCCX_CHECK_ARG(n_list >= 0 && n_list <= P, "pccx_range_decode_split_list: %d segments listed of %d", n_list, P);
     PCCX_CHECK_ARG(in && nbytes && status && workspace && (n_list == 0 || (cdf_int && latent_q && seg_idx)),
                    "pccx_range_decode_split_list: null pointer");
     PCCX_CHECK_ARG(stride >= 1, "pccx_range_decode_split_list: bad shape (stride=%d)", stride);
-    int32_t *offsets = (int32_t *)workspace;
-    hipLaunchKernelGGL(range_split_check_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, in, stride, nbytes, 1, nsym, seg_sym, P, segcap,
-                       status, offsets);
-    PCCX_CHECK_LAUNCH();
-    if (n_list > 0) {
-        hipLaunchKernelGGL(range_decode_split_list_kernel, dim3(n_list), dim3(64), rc_decode_lds(seg_sym, L, segcap), (hipStream_t)stream,
-                           cdf_int, in, stride, offsets, seg_idx, nsym, seg_sym, P, L + 1, L / 2, segcap, latent_q);
-        PCCX_CHECK_LAUNCH();
-    }
-    return PCCX_OK;
+    return rc_decode_split_launch(cdf_int, in, stride, nbytes, 1, nsym, seg_sym, L, seg_idx, n_list, latent_q, status, workspace,
+                                  (hipStream_t)stream);
 }
 
 // ---- entry-point index: any number of waves enter the ONE stream of a cloud side by side -------------------------------------
@@ -833,7 +849,7 @@ __global__ __launch_bounds__(64) void range_index_build_wave_kernel(const int32_
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
     const int b = blockIdx.x;
-    const int nb = nbytes[b] < 0 ? 0 : (nbytes[b] > stride ? stride : nbytes[b]);
+    const int nb = rc_row_bytes(nbytes[b], stride);
     uint32_t *side = (uint32_t *)(index + (size_t)b * idx_stride);
     if (threadIdx.x == 0) rc_index_header(side, nsym, seg_sym);
     rc_decode_wave<false, true>(rc_smem, cdf_int + (size_t)b * nsym * Lp, in + (size_t)b * stride, stride, nb, nsym, Lp, sym_offset,
@@ -848,8 +864,8 @@ __global__ __launch_bounds__(64) void range_index_check_kernel(const uint8_t *__
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     // counts beyond their rows are cut to the rows before anything is read
-    const int nb = nbytes[b] < 0 ? 0 : (nbytes[b] > stride ? stride : nbytes[b]);
-    const int ni = !idx_nbytes ? idx_stride : (idx_nbytes[b] < 0 ? 0 : (idx_nbytes[b] > idx_stride ? idx_stride : idx_nbytes[b]));
+    const int nb = rc_row_bytes(nbytes[b], stride);
+    const int ni = !idx_nbytes ? idx_stride : rc_row_bytes(idx_nbytes[b], idx_stride);
     status[b] = pccx_entry_index_check(index + (size_t)b * idx_stride, ni, nb, nsym, seg_sym, maxspan, seg + (size_t)b * P * PCCX_INDEX_SEG_WORDS);
 }
 
@@ -871,40 +887,40 @@ __device__ __forceinline__ void rc_decode_entry(unsigned char *smem, const int32
     rc_decode_wave<true>(smem, c, in + at, stage, nb, n, Lp, sym_offset, q, low, high, (int)(pos & 7u), (pf & PCCX_INDEX_FLAG) != 0u);
 }
 
+template <bool LIST>
 __global__ __launch_bounds__(64) void range_decode_indexed_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in, int stride,
                                                                   const int32_t *__restrict__ nbytes, const uint32_t *__restrict__ seg,
                                                                   int nsym, int seg_sym, int P, int Lp, int sym_offset, int stage,
-                                                                  float *__restrict__ latent_q)
+                                                                  float *__restrict__ latent_q, const int32_t *__restrict__ seg_idx)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
-    const int p = blockIdx.x, b = blockIdx.y;
-    const int first = p * seg_sym;                                     // < nsym: p < P
-    const int n = nsym - first < seg_sym ? nsym - first : seg_sym;     // ragged last segment
-    const int nbr = (int)rc_uni((unsigned)nbytes[b]);
-    const int nbrow = nbr < 0 ? 0 : (nbr > stride ? stride : nbr);
-    rc_decode_entry(rc_smem, cdf_int + ((size_t)b * nsym + first) * Lp, in + (size_t)b * stride, nbrow,
-                    seg + ((size_t)b * P + p) * PCCX_INDEX_SEG_WORDS, stage, n, Lp, sym_offset, latent_q + (size_t)b * nsym + first);
+    const int b = blockIdx.y;
+    const RcSegment s = rc_segment<LIST>(seg_idx, nsym, seg_sym, P);
+    const int nbrow = rc_row_bytes((int)rc_uni((unsigned)nbytes[b]), stride);
+    rc_decode_entry(rc_smem, rc_segment_rows<LIST>(cdf_int, s, nsym, seg_sym, Lp), in + (size_t)b * stride, nbrow,
+                    seg + ((size_t)b * P + s.p) * PCCX_INDEX_SEG_WORDS, stage, s.n, Lp, sym_offset,
+                    rc_segment_rows<LIST>(latent_q, s, nsym, seg_sym, 1));
 }
 
-// The listed form (region decode): wave j decodes segment seg_idx[j] of ONE cloud with table rows and output rows j * seg_sym ...,
-// both compact, as range_decode_split_list_kernel.  It stages the bytes of that segment's span alone.  An index outside [0, P) is cut
-// into it.
-__global__ __launch_bounds__(64) void range_decode_indexed_list_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in,
-                                                                       int stride, const int32_t *__restrict__ nbytes,
-                                                                       const uint32_t *__restrict__ seg, const int32_t *__restrict__ seg_idx,
-                                                                       int nsym, int seg_sym, int P, int Lp, int sym_offset, int stage,
-                                                                       float *__restrict__ latent_q)
+// Both indexed decoders: the check kernel (status per cloud, four words per segment in workspace), then one wave per segment.
+// idx_nbytes null: every sidecar is idx_stride bytes.  seg_idx null: the whole batch.
+static int rc_decode_indexed_launch(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes, const uint8_t *index,
+                                    int idx_stride, const int32_t *idx_nbytes, int B, int nsym, int seg_sym, int L, const int32_t *seg_idx,
+                                    int n_waves, float *latent_q, int32_t *status, void *workspace, hipStream_t stream)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
-    const int j = blockIdx.x;
-    int p = (int)rc_uni((unsigned)seg_idx[j]);
-    p = p < 0 ? 0 : (p > P - 1 ? P - 1 : p);
-    const int first = p * seg_sym;
-    const int n = nsym - first < seg_sym ? nsym - first : seg_sym;
-    const int nbr = (int)rc_uni((unsigned)nbytes[0]);
-    const int nbrow = nbr < 0 ? 0 : (nbr > stride ? stride : nbr);
-    rc_decode_entry(rc_smem, cdf_int + (size_t)j * seg_sym * Lp, in, nbrow, seg + (size_t)p * PCCX_INDEX_SEG_WORDS, stage, n, Lp, sym_offset,
-                    latent_q + (size_t)j * seg_sym);
+    const int P = (int)pccx_index_segments(nsym, seg_sym), stage = rc_index_stage(seg_sym);
+    uint32_t *seg = (uint32_t *)workspace;
+    hipLaunchKernelGGL(range_index_check_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, index, idx_stride, idx_nbytes, stride, nbytes, B,
+                       nsym, seg_sym, P, rc_index_maxspan(seg_sym), status, seg);
+    PCCX_CHECK_LAUNCH();
+    if (n_waves > 0) {
+        const auto kernel = seg_idx ? range_decode_indexed_kernel<true> : range_decode_indexed_kernel<false>;
+        hipLaunchKernelGGL(kernel, dim3(n_waves, B), dim3(64),
+                           rc_decode_lds(seg_sym, L, stage), stream, cdf_int, in, stride, nbytes, seg, nsym, seg_sym, P, L + 1, L / 2, stage,
+                           latent_q, seg_idx);
+        PCCX_CHECK_LAUNCH();
+    }
+    return PCCX_OK;
 }
 
 // The shapes every indexed entry point takes: those of the split path, and a stream whose bit positions fit the 31 bits of an entry.
@@ -966,19 +982,10 @@ extern "C" int pccx_range_decode_indexed(const int32_t *cdf_int, const uint8_t *
     if (B == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
     const int rc = rc_index_check_args("pccx_range_decode_indexed", B, nsym, seg_sym, L, stride);
     if (rc != PCCX_OK) return rc;
-    const int P = (int)pccx_index_segments(nsym, seg_sym), stage = rc_index_stage(seg_sym);
     PCCX_CHECK_ARG(in && nbytes && index && status && workspace && (nsym == 0 || (cdf_int && latent_q)), "pccx_range_decode_indexed: null pointer");
     PCCX_CHECK_ARG(idx_stride >= 0, "pccx_range_decode_indexed: bad shape (idx_stride=%d)", idx_stride);
-    uint32_t *seg = (uint32_t *)workspace;
-    hipLaunchKernelGGL(range_index_check_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, index, idx_stride, idx_nbytes, stride,
-                       nbytes, B, nsym, seg_sym, P, rc_index_maxspan(seg_sym), status, seg);
-    PCCX_CHECK_LAUNCH();
-    if (P > 0) {
-        hipLaunchKernelGGL(range_decode_indexed_kernel, dim3(P, B), dim3(64), rc_decode_lds(seg_sym, L, stage), (hipStream_t)stream, cdf_int, in,
-                           stride, nbytes, seg, nsym, seg_sym, P, L + 1, L / 2, stage, latent_q);
-        PCCX_CHECK_LAUNCH();
-    }
-    return PCCX_OK;
+    return rc_decode_indexed_launch(cdf_int, in, stride, nbytes, index, idx_stride, idx_nbytes, B, nsym, seg_sym, L, nullptr,
+                                    (int)pccx_index_segments(nsym, seg_sym), latent_q, status, workspace, (hipStream_t)stream);
 }
 
 extern "C" int pccx_range_decode_indexed_list(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes,
@@ -987,21 +994,13 @@ extern "C" int pccx_range_decode_indexed_list(const int32_t *cdf_int, const uint
 {
     const int rc = rc_index_check_args("pccx_range_decode_indexed_list", 1, nsym, seg_sym, L, stride);
     if (rc != PCCX_OK) return rc;
-    const int P = (int)pccx_index_segments(nsym, seg_sym), stage = rc_index_stage(seg_sym);
+    const int P = (int)pccx_index_segments(nsym, seg_sym);
     PCCX_CHECK_ARG(n_list >= 0 && n_list <= P, "pccx_range_decode_indexed_list: %d segments listed of %d", n_list, P);
     PCCX_CHECK_ARG(in && nbytes && index && status && workspace && (n_list == 0 || (cdf_int && latent_q && seg_idx)),
                    "pccx_range_decode_indexed_list: null pointer");
     PCCX_CHECK_ARG(idx_bytes >= 0, "pccx_range_decode_indexed_list: bad shape (idx_bytes=%d)", idx_bytes);
-    uint32_t *seg = (uint32_t *)workspace;
-    hipLaunchKernelGGL(range_index_check_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, index, idx_bytes, (const int32_t *)nullptr, stride,
-                       nbytes, 1, nsym, seg_sym, P, rc_index_maxspan(seg_sym), status, seg);
-    PCCX_CHECK_LAUNCH();
-    if (n_list > 0) {
-        hipLaunchKernelGGL(range_decode_indexed_list_kernel, dim3(n_list), dim3(64), rc_decode_lds(seg_sym, L, stage), (hipStream_t)stream,
-                           cdf_int, in, stride, nbytes, seg, seg_idx, nsym, seg_sym, P, L + 1, L / 2, stage, latent_q);
-        PCCX_CHECK_LAUNCH();
-    }
-    return PCCX_OK;
+    return rc_decode_indexed_launch(cdf_int, in, stride, nbytes, index, idx_bytes, nullptr, 1, nsym, seg_sym, L, seg_idx, n_list, latent_q,
+                                    status, workspace, (hipStream_t)stream);
 }
 
 // torchac's float -> 16-bit CDF conversion (torchac 0.9.3 _convert_to_int_and_normalize, needs_normalization=True; the

@@ -10,6 +10,7 @@ right-aligned), ``.p.bin`` = range-coder bytes of the S*d latent symbols, ``.c.b
 [cx, cy, cz, longest].
 """
 import dataclasses
+import functools
 import os
 
 import numpy as np
@@ -209,6 +210,15 @@ OCTREE_MAX_S = 1024            # centres per cloud pccx_octree_encode, pccx_patc
 OCTREE_WIDE_MAX_S = 8192       # ... and their wide forms (pccx_octree_encode_wide, pccx_octree_decode above 1024, pccx_patch_groups_wide)
 
 
+def _check_patches(ae, name, G, unit):
+    if G is None:
+        return
+    g_max = models.split_max_seg_sym(ae.L) // ae.d
+    if isinstance(G, bool) or not isinstance(G, int) or not 1 <= G <= g_max:
+        raise ValueError(f"{name} must be None or an int in 1..{g_max} patches per {unit} (a segment of {name}*d symbols is staged in "
+                         f"LDS by one wave, d={ae.d}, L={ae.L}; L must be in 2..63), got {G!r}")
+
+
 class Codec:
     def __init__(self, ae, prob, K=256, ALPHA=2, N0=1024, octree_mode="reference", margin=0.01, matmul=None,
                  decoder_matmul=None, sa_matmul=None, pn_matmul=None, group_duplicates=True, knn_search="auto",
@@ -274,20 +284,11 @@ class Codec:
         if isinstance(max_centres, bool) or not isinstance(max_centres, int) or not 1 <= max_centres <= OCTREE_WIDE_MAX_S:
             raise ValueError(f"max_centres must be an int in 1..{OCTREE_WIDE_MAX_S} (the wide octree coder's limit), got {max_centres!r}")
         self.max_centres = max_centres
-        if p_split is not None:
-            g_max = models.split_max_seg_sym(ae.L) // ae.d
-            if isinstance(p_split, bool) or not isinstance(p_split, int) or not 1 <= p_split <= g_max:
-                raise ValueError(f"p_split must be None or an int in 1..{g_max} patches per segment (a segment of p_split*d symbols is staged in "
-                                 f"LDS by one wave, d={ae.d}, L={ae.L}; L must be in 2..63), got {p_split!r}")
-        self.p_split = p_split
-        if p_index is not None:
-            if p_split is not None:
-                raise ValueError("p_index and p_split exclude each other: the index enters the single stream, the split form has no single stream")
-            g_max = models.split_max_seg_sym(ae.L) // ae.d
-            if isinstance(p_index, bool) or not isinstance(p_index, int) or not 1 <= p_index <= g_max:
-                raise ValueError(f"p_index must be None or an int in 1..{g_max} patches per entry (a segment of p_index*d symbols is staged in "
-                                 f"LDS by one wave, d={ae.d}, L={ae.L}; L must be in 2..63), got {p_index!r}")
-        self.p_index = p_index
+        _check_patches(ae, "p_split", p_split, "segment")
+        if p_index is not None and p_split is not None:
+            raise ValueError("p_index and p_split exclude each other: the index enters the single stream, the split form has no single stream")
+        _check_patches(ae, "p_index", p_index, "entry")
+        self.p_split, self.p_index = p_split, p_index
         if centres not in ("fps", "blocks"):
             raise ValueError(f"centres must be 'fps' or 'blocks', got {centres!r}")
         self.centres, self.fps_block = centres, ops.check_fps_block(fps_block)
@@ -446,16 +447,17 @@ class Codec:
             if comp.p_index_nbytes is not None:              # from a file: the sidecar is as long as the file was (read_files keeps the
                 host_n = getattr(comp, "_p_index_nbytes_host", None)     # counts on the host too, so this is no synchronisation)
                 side = side[:max(int(host_n[0] if host_n is not None else comp.p_index_nbytes[0]), 1)]
+        # the listed decoder of this stream form and the cloud's stream as it takes it; an empty list runs the stream's check alone
+        decode_list = functools.partial(models.range_decode_indexed_list, index=side) if indexed else models.range_decode_split_list
+        stream = dict(bytes_=comp.p_bytes[0], nbytes=comp.p_nbytes, L=L, seg_sym=G * d, nsym=S * d)
         fast = self.prob.fused_ok(S) and self.ae.fused_d
         with stage("octree_decode"):
             rec, _ = ops.octree_decode(comp.s_bytes, comp.s_nbytes, self.octree_mode, S)
         head = torch.zeros(3, device=rec.device, dtype=torch.int32)           # n_sel, n_seg, status of the stream's header
         with stage("region_select"):
             sel = ops.region_select(rec[0], comp.c[0], box, G, halo, self.margin, counts=head[:2])
-            if fast and indexed:
-                models.range_decode_indexed_list(None, comp.p_bytes[0], comp.p_nbytes, side, L, G * d, S * d, None, 0, status=head[2:])
-            elif fast:
-                models.range_decode_split_list(None, comp.p_bytes[0], comp.p_nbytes, L, G * d, S * d, None, 0, status=head[2:])
+            if fast:
+                decode_list(None, seg_idx=None, n_list=0, status=head[2:], **stream)
             n_sel, n_seg, status = (int(v) for v in head.cpu())               # THE synchronisation
         err = (models.index_status_error if indexed else models.split_status_error)("decompress_region", [status])
         if err is not None:
@@ -469,10 +471,7 @@ class Codec:
         with stage("prob"):
             cdf_int = self.prob.run_segments(rec[0], sel.seg_idx, n_seg, G)
         with stage("range_decode"):
-            if indexed:
-                q, _ = models.range_decode_indexed_list(cdf_int, comp.p_bytes[0], comp.p_nbytes, side, L, G * d, S * d, sel.seg_idx, n_seg)
-            else:
-                q, _ = models.range_decode_split_list(cdf_int, comp.p_bytes[0], comp.p_nbytes, L, G * d, S * d, sel.seg_idx, n_seg)
+            q, _ = decode_list(cdf_int, seg_idx=sel.seg_idx, n_list=n_seg, **stream)
         with stage("gather"):
             q_sel = ops.index_points(q.view(1, n_seg * G, d), sel.rows[:n_sel].view(1, n_sel))
             c_sel = ops.index_points(rec, patch_idx.view(1, n_sel))

@@ -620,34 +620,87 @@ def range_cap(nsym):
     return int(nsym) * 2 + 16
 
 
+def _encoder_args(who, cdf_int, latent_q, L, out, nb, cap):
+    """What the three encoders take from cdf_int (B,nsym,L+1) / latent_q (B,nsym) -> (B, nsym, q, out, nb): the f32 symbols and
+    dense destinations, the caller's or new ones (out of cap(nsym) bytes per cloud)."""
+    B = cdf_int.shape[0]
+    nsym = cdf_int[0].numel() // (L + 1) if B else 0
+    q = _f32c(latent_q.reshape(B, nsym), who)
+    if out is None:
+        out = torch.empty(B, cap(nsym), device=q.device, dtype=torch.uint8)
+    if nb is None:
+        nb = torch.empty(B, device=q.device, dtype=torch.int32)
+    if (out.dim() != 2 or out.shape[0] != B or out.dtype != torch.uint8 or not out.is_contiguous() or tuple(nb.shape) != (B,)
+            or nb.dtype != torch.int32 or not nb.is_contiguous()):
+        raise _lib.PccxError(f"{who}: out must be dense (B,cap) u8 and nb dense (B,) i32")
+    return B, nsym, q, out, nb
+
+
+def _decoder_args(cdf_int, bytes_, nbytes, L, latent=True, status=False):
+    """What the whole-batch decoders take from cdf_int (B,nsym,L+1) and the streams -> (B, nsym, dense bytes_, i32 nbytes,
+    latent_q (B,nsym) f32 to fill or None, cleared status (B,) i32 or None)."""
+    B = cdf_int.shape[0]
+    nsym = cdf_int[0].numel() // (L + 1) if B else 0
+    bytes_ = bytes_.contiguous()
+    return (B, nsym, bytes_, nbytes.to(torch.int32).contiguous(),
+            torch.empty(B, nsym, device=bytes_.device, dtype=torch.float32) if latent else None,
+            torch.zeros(B, device=bytes_.device, dtype=torch.int32) if status else None)
+
+
+def _list_decoder_args(cdf_int, bytes_, nbytes, seg_sym, seg_idx, n_list, status):
+    """The same for the listed segments of ONE cloud -> (table pointer, flat bytes_, i32 nbytes, list pointer, compact latent_q
+    (n_list*seg_sym,) f32, its pointer, status (1,) i32: the caller's or a cleared one).  Pointers are None for an empty list."""
+    bytes_ = bytes_.contiguous().reshape(-1)
+    q = torch.empty(n_list * seg_sym, device=bytes_.device, dtype=torch.float32)
+    if status is None:
+        status = torch.zeros(1, device=bytes_.device, dtype=torch.int32)
+    return (cdf_int.contiguous().data_ptr() if n_list else None, bytes_, nbytes.to(torch.int32).contiguous(),
+            seg_idx.contiguous().data_ptr() if n_list else None, q, q.data_ptr() if n_list else None, status)
+
+
+def _status_error(who, st, table):
+    """The PccxError for per-cloud status words ``st`` (a host sequence) explained by ``table``, or None when all are 0."""
+    import numpy as np
+    st = np.asarray(st).reshape(-1)
+    if not st.any():
+        return None
+    return _lib.PccxError(f"{who}: " + "; ".join(
+        f"clouds {[int(b) for b in (st == code).nonzero()[0]]}: {why}" for code, why in table.items() if (st == code).any()))
+
+
+def _checked(who, q, status, table, check):
+    """check=True: read the status once and raise what it says, else latent_q; check=False: (latent_q, status), no synchronisation."""
+    if not check:
+        return q, status
+    err = _status_error(who, status.cpu().numpy(), table)
+    if err is not None:
+        raise err
+    return q
+
+
+def _host_check(fn_name, data, *ints):
+    """One of the library's host-side format checks on a bytes-like object (no GPU call) -> its status word."""
+    import ctypes
+    data = bytes(data)
+    buf = ctypes.create_string_buffer(data, max(len(data), 1))
+    return int(getattr(_lib.load(), fn_name)(ctypes.addressof(buf), len(data), *(int(v) for v in ints)))
+
+
 def range_encode(cdf_int, latent_q, L, cap=None, out=None, nb=None):
     """torchac.encode_float_cdf on device: cdf_int (B,nsym,L+1) int32, latent_q (B,nsym) -> (bytes (B,cap) u8, nbytes (B)).
     A cloud whose stream does not fit ``cap`` bytes comes back with a NEGATIVE nbytes; codec.Compressed.to_host() raises on it
     (unreachable with the default cap).  out / nb: caller-provided dense destinations."""
-    B = cdf_int.shape[0]
-    nsym = cdf_int[0].numel() // (L + 1)
-    q = _f32c(latent_q.reshape(B, nsym), "range_encode")
-    if out is None:
-        out = torch.empty(B, cap or range_cap(nsym), device=q.device, dtype=torch.uint8)
-    if nb is None:
-        nb = torch.empty(B, device=q.device, dtype=torch.int32)
-    cap = out.shape[1]
-    if (out.shape[0] != B or out.dtype != torch.uint8 or not out.is_contiguous() or tuple(nb.shape) != (B,)
-            or nb.dtype != torch.int32 or not nb.is_contiguous()):
-        raise _lib.PccxError("range_encode: out must be dense (B,cap) u8 and nb dense (B,) i32")
-    _lib.call("pccx_range_encode", cdf_int.contiguous().data_ptr(), q.data_ptr(), B, nsym, int(L), out.data_ptr(), cap,
+    B, nsym, q, out, nb = _encoder_args("range_encode", cdf_int, latent_q, L, out, nb, lambda n: cap or range_cap(n))
+    _lib.call("pccx_range_encode", cdf_int.contiguous().data_ptr(), q.data_ptr(), B, nsym, int(L), out.data_ptr(), out.shape[1],
               nb.data_ptr(), _stream())
     return out, nb
 
 
 def range_decode(cdf_int, bytes_, nbytes, L):
     """torchac.decode_float_cdf on device -> latent_q (B,nsym) f32 (already minus L//2)."""
-    B = cdf_int.shape[0]
-    nsym = cdf_int[0].numel() // (L + 1)
-    bytes_ = bytes_.contiguous()
-    q = torch.empty(B, nsym, device=bytes_.device, dtype=torch.float32)
-    _lib.call("pccx_range_decode", cdf_int.contiguous().data_ptr(), bytes_.data_ptr(), bytes_.shape[1],
-              nbytes.to(torch.int32).contiguous().data_ptr(), B, nsym, int(L), q.data_ptr(), _stream())
+    B, nsym, bytes_, nbytes, q, _ = _decoder_args(cdf_int, bytes_, nbytes, L)
+    _lib.call("pccx_range_decode", cdf_int.contiguous().data_ptr(), bytes_.data_ptr(), bytes_.shape[1], nbytes.data_ptr(), B, nsym, int(L),
+              q.data_ptr(), _stream())
     return q
 
 
@@ -684,17 +737,8 @@ def _split_workspace(B, nsym, seg_sym, device):
 def range_encode_split(cdf_int, latent_q, L, seg_sym, out=None, nb=None):
     """The split stream of every cloud: cdf_int (B,nsym,L+1) int32, latent_q (B,nsym) -> (bytes (B,cap) u8, nbytes (B)); segment p
     codes symbols [p*seg_sym, (p+1)*seg_sym) as range_encode codes a stream of that length.  nbytes < 0: `cap` too small, as there."""
-    B = cdf_int.shape[0]
-    nsym = cdf_int[0].numel() // (L + 1) if B else 0
     seg_sym = int(seg_sym)
-    q = _f32c(latent_q.reshape(B, nsym), "range_encode_split")
-    if out is None:
-        out = torch.empty(B, split_cap(nsym, max(seg_sym, 1)), device=q.device, dtype=torch.uint8)
-    if nb is None:
-        nb = torch.empty(B, device=q.device, dtype=torch.int32)
-    if (out.dim() != 2 or out.shape[0] != B or out.dtype != torch.uint8 or not out.is_contiguous() or tuple(nb.shape) != (B,)
-            or nb.dtype != torch.int32 or not nb.is_contiguous()):
-        raise _lib.PccxError("range_encode_split: out must be dense (B,cap) u8 and nb dense (B,) i32")
+    B, nsym, q, out, nb = _encoder_args("range_encode_split", cdf_int, latent_q, L, out, nb, lambda n: split_cap(n, max(seg_sym, 1)))
     ws = _split_workspace(B, nsym, seg_sym, q.device)
     _lib.call("pccx_range_encode_split", cdf_int.contiguous().data_ptr(), q.data_ptr(), B, nsym, seg_sym, int(L), out.data_ptr(),
               out.shape[1], nb.data_ptr(), ws.data_ptr(), _stream())
@@ -705,32 +749,17 @@ def range_decode_split(cdf_int, bytes_, nbytes, L, seg_sym, check=True):
     """The inverse -> latent_q (B,nsym) f32.  check=True reads the per-cloud status once and raises PccxError naming the clouds whose
     header is refused (SPLIT_STATUS); check=False returns (latent_q, status (B,) i32 on the device) without a synchronisation -- a
     refused cloud's symbols are those of an empty stream."""
-    B = cdf_int.shape[0]
-    nsym = cdf_int[0].numel() // (L + 1) if B else 0
     seg_sym = int(seg_sym)
-    bytes_ = bytes_.contiguous()
-    q = torch.empty(B, nsym, device=bytes_.device, dtype=torch.float32)
-    status = torch.zeros(B, device=bytes_.device, dtype=torch.int32)
+    B, nsym, bytes_, nbytes, q, status = _decoder_args(cdf_int, bytes_, nbytes, L, status=True)
     ws = _split_workspace(B, nsym, seg_sym, bytes_.device)
-    _lib.call("pccx_range_decode_split", cdf_int.contiguous().data_ptr(), bytes_.data_ptr(), bytes_.shape[1],
-              nbytes.to(torch.int32).contiguous().data_ptr(), B, nsym, seg_sym, int(L), q.data_ptr(), status.data_ptr(), ws.data_ptr(),
-              _stream())
-    if not check:
-        return q, status
-    err = split_status_error("range_decode_split", status.cpu().numpy())
-    if err is not None:
-        raise err
-    return q
+    _lib.call("pccx_range_decode_split", cdf_int.contiguous().data_ptr(), bytes_.data_ptr(), bytes_.shape[1], nbytes.data_ptr(), B, nsym,
+              seg_sym, int(L), q.data_ptr(), status.data_ptr(), ws.data_ptr(), _stream())
+    return _checked("range_decode_split", q, status, SPLIT_STATUS, check)
 
 
 def split_status_error(who, st):
     """The PccxError range_decode_split raises for per-cloud status words ``st`` (a host sequence), or None when all are 0."""
-    import numpy as np
-    st = np.asarray(st).reshape(-1)
-    if not st.any():
-        return None
-    return _lib.PccxError(f"{who}: " + "; ".join(
-        f"clouds {[int(b) for b in (st == code).nonzero()[0]]}: {why}" for code, why in SPLIT_STATUS.items() if (st == code).any()))
+    return _status_error(who, st, SPLIT_STATUS)
 
 
 def range_decode_split_list(cdf_int, bytes_, nbytes, L, seg_sym, nsym, seg_idx, n_list, status=None):
@@ -739,24 +768,17 @@ def range_decode_split_list(cdf_int, bytes_, nbytes, L, seg_sym, nsym, seg_idx, 
     seg_idx i32 on the device (the first n_list entries, ascending segment numbers), n_list a host int ->
     (latent_q (n_list*seg_sym,) f32 compact, status (1,) i32 on the device, as range_decode_split(check=False) gives it).  No byte of
     an unlisted segment is read.  n_list = 0 runs the header check alone.  status: an int32 device tensor to write instead of a new one."""
-    bytes_ = bytes_.contiguous().reshape(-1)
     n_list, seg_sym, nsym = int(n_list), int(seg_sym), int(nsym)
-    q = torch.empty(n_list * seg_sym, device=bytes_.device, dtype=torch.float32)
-    if status is None:
-        status = torch.zeros(1, device=bytes_.device, dtype=torch.int32)
+    cdf_p, bytes_, nbytes, idx_p, q, q_p, status = _list_decoder_args(cdf_int, bytes_, nbytes, seg_sym, seg_idx, n_list, status)
     ws = _split_workspace(1, nsym, seg_sym, bytes_.device)
-    _lib.call("pccx_range_decode_split_list", cdf_int.contiguous().data_ptr() if n_list else None, bytes_.data_ptr(), bytes_.numel(),
-              nbytes.to(torch.int32).contiguous().data_ptr(), nsym, seg_sym, int(L), seg_idx.contiguous().data_ptr() if n_list else None,
-              n_list, q.data_ptr() if n_list else None, status.data_ptr(), ws.data_ptr(), _stream())
+    _lib.call("pccx_range_decode_split_list", cdf_p, bytes_.data_ptr(), bytes_.numel(), nbytes.data_ptr(), nsym, seg_sym, int(L), idx_p,
+              n_list, q_p, status.data_ptr(), ws.data_ptr(), _stream())
     return q, status
 
 
 def split_stream_status(data, nsym, seg_sym):
     """pccx_split_stream_check_host on a bytes-like object (no GPU call): 0, or a key of SPLIT_STATUS."""
-    import ctypes
-    data = bytes(data)
-    buf = ctypes.create_string_buffer(data, max(len(data), 1))
-    return int(_lib.load().pccx_split_stream_check_host(ctypes.addressof(buf), len(data), int(nsym), int(seg_sym), range_cap(seg_sym)))
+    return _host_check("pccx_split_stream_check_host", data, nsym, seg_sym, range_cap(seg_sym))
 
 
 # ---- entry-point index of the single stream (include/pccx.h: "PXI1" | nsym | seg_sym | P | {low, high, pos}[P]) -----------------
@@ -793,17 +815,8 @@ def _index_rows(index, B, who):
 def range_encode_indexed(cdf_int, latent_q, L, seg_sym, cap=None, out=None, nb=None):
     """range_encode that also writes the entry-point index: -> (bytes (B,cap) u8, nbytes (B), index (B, index_bytes(nsym, seg_sym)) u8).
     The bytes and counts are range_encode's; index row b is the file <name>.p.idx of cloud b."""
-    B = cdf_int.shape[0]
-    nsym = cdf_int[0].numel() // (L + 1) if B else 0
     seg_sym = int(seg_sym)
-    q = _f32c(latent_q.reshape(B, nsym), "range_encode_indexed")
-    if out is None:
-        out = torch.empty(B, cap or range_cap(nsym), device=q.device, dtype=torch.uint8)
-    if nb is None:
-        nb = torch.empty(B, device=q.device, dtype=torch.int32)
-    if (out.dim() != 2 or out.shape[0] != B or out.dtype != torch.uint8 or not out.is_contiguous() or tuple(nb.shape) != (B,)
-            or nb.dtype != torch.int32 or not nb.is_contiguous()):
-        raise _lib.PccxError("range_encode_indexed: out must be dense (B,cap) u8 and nb dense (B,) i32")
+    B, nsym, q, out, nb = _encoder_args("range_encode_indexed", cdf_int, latent_q, L, out, nb, lambda n: cap or range_cap(n))
     index = torch.empty(B, index_bytes(nsym, max(seg_sym, 1)), device=q.device, dtype=torch.uint8)
     _lib.call("pccx_range_encode_indexed", cdf_int.contiguous().data_ptr(), q.data_ptr(), B, nsym, seg_sym, int(L), out.data_ptr(),
               out.shape[1], nb.data_ptr(), index.data_ptr(), _stream())
@@ -814,15 +827,11 @@ def range_index_build(cdf_int, bytes_, nbytes, L, seg_sym, return_latent=False):
     """The index of existing streams (files written without one, the reference's included): the sequential decoder run once ->
     index (B, index_bytes) u8, bit for bit what range_encode_indexed writes for the same stream; with return_latent also the
     symbols it decoded on the way, (index, latent_q (B,nsym) f32)."""
-    B = cdf_int.shape[0]
-    nsym = cdf_int[0].numel() // (L + 1) if B else 0
     seg_sym = int(seg_sym)
-    bytes_ = bytes_.contiguous()
+    B, nsym, bytes_, nbytes, q, _ = _decoder_args(cdf_int, bytes_, nbytes, L, latent=return_latent)
     index = torch.empty(B, index_bytes(nsym, max(seg_sym, 1)), device=bytes_.device, dtype=torch.uint8)
-    q = torch.empty(B, nsym, device=bytes_.device, dtype=torch.float32) if return_latent else None
-    _lib.call("pccx_range_index_build", cdf_int.contiguous().data_ptr(), bytes_.data_ptr(), bytes_.shape[1],
-              nbytes.to(torch.int32).contiguous().data_ptr(), B, nsym, seg_sym, int(L), index.data_ptr(),
-              q.data_ptr() if return_latent else None, _stream())
+    _lib.call("pccx_range_index_build", cdf_int.contiguous().data_ptr(), bytes_.data_ptr(), bytes_.shape[1], nbytes.data_ptr(), B, nsym,
+              seg_sym, int(L), index.data_ptr(), q.data_ptr() if return_latent else None, _stream())
     return (index, q) if return_latent else index
 
 
@@ -832,34 +841,21 @@ def range_decode_indexed(cdf_int, bytes_, nbytes, index, L, seg_sym, index_nbyte
     than their rows (files).  check=True reads the per-cloud status once and raises PccxError naming the clouds whose sidecar is
     refused (INDEX_STATUS); check=False returns (latent_q, status (B,) i32 on the device) without a synchronisation -- a refused
     cloud's symbols are those of empty segments."""
-    B = cdf_int.shape[0]
-    nsym = cdf_int[0].numel() // (L + 1) if B else 0
     seg_sym = int(seg_sym)
-    bytes_ = bytes_.contiguous()
-    index = _index_rows(index, B, "range_decode_indexed")
-    q = torch.empty(B, nsym, device=bytes_.device, dtype=torch.float32)
-    status = torch.zeros(B, device=bytes_.device, dtype=torch.int32)
+    index = _index_rows(index, cdf_int.shape[0], "range_decode_indexed")
+    B, nsym, bytes_, nbytes, q, status = _decoder_args(cdf_int, bytes_, nbytes, L, status=True)
+    if index_nbytes is not None:
+        index_nbytes = index_nbytes.to(torch.int32).contiguous()
     ws = _index_workspace(B, nsym, seg_sym, bytes_.device)
-    _lib.call("pccx_range_decode_indexed", cdf_int.contiguous().data_ptr(), bytes_.data_ptr(), bytes_.shape[1],
-              nbytes.to(torch.int32).contiguous().data_ptr(), index.data_ptr(), index.shape[1],
-              index_nbytes.to(torch.int32).contiguous().data_ptr() if index_nbytes is not None else None, B, nsym, seg_sym, int(L),
+    _lib.call("pccx_range_decode_indexed", cdf_int.contiguous().data_ptr(), bytes_.data_ptr(), bytes_.shape[1], nbytes.data_ptr(),
+              index.data_ptr(), index.shape[1], index_nbytes.data_ptr() if index_nbytes is not None else None, B, nsym, seg_sym, int(L),
               q.data_ptr(), status.data_ptr(), ws.data_ptr(), _stream())
-    if not check:
-        return q, status
-    err = index_status_error("range_decode_indexed", status.cpu().numpy())
-    if err is not None:
-        raise err
-    return q
+    return _checked("range_decode_indexed", q, status, INDEX_STATUS, check)
 
 
 def index_status_error(who, st):
     """The PccxError range_decode_indexed raises for per-cloud status words ``st`` (a host sequence), or None when all are 0."""
-    import numpy as np
-    st = np.asarray(st).reshape(-1)
-    if not st.any():
-        return None
-    return _lib.PccxError(f"{who}: " + "; ".join(
-        f"clouds {[int(b) for b in (st == code).nonzero()[0]]}: {why}" for code, why in INDEX_STATUS.items() if (st == code).any()))
+    return _status_error(who, st, INDEX_STATUS)
 
 
 def range_decode_indexed_list(cdf_int, bytes_, nbytes, index, L, seg_sym, nsym, seg_idx, n_list, status=None):
@@ -867,25 +863,17 @@ def range_decode_indexed_list(cdf_int, bytes_, nbytes, index, L, seg_sym, nsym, 
     (n_list*seg_sym, L+1) i32 compact table rows, bytes_ the cloud's .p.bin, nbytes (1,) i32, index the idx bytes of its sidecar
     (a 1-d u8 tensor: its length is the sidecar's), seg_idx i32 on the device, n_list a host int -> (latent_q (n_list*seg_sym,) f32
     compact, status (1,) i32 on the device).  Only the bytes of the listed segments' spans are read.  n_list = 0 runs the check alone."""
-    bytes_ = bytes_.contiguous().reshape(-1)
     index = index.contiguous().reshape(-1)
     if index.dtype != torch.uint8:
         raise _lib.PccxError("range_decode_indexed_list: index must be u8")
     n_list, seg_sym, nsym = int(n_list), int(seg_sym), int(nsym)
-    q = torch.empty(n_list * seg_sym, device=bytes_.device, dtype=torch.float32)
-    if status is None:
-        status = torch.zeros(1, device=bytes_.device, dtype=torch.int32)
+    cdf_p, bytes_, nbytes, idx_p, q, q_p, status = _list_decoder_args(cdf_int, bytes_, nbytes, seg_sym, seg_idx, n_list, status)
     ws = _index_workspace(1, nsym, seg_sym, bytes_.device)
-    _lib.call("pccx_range_decode_indexed_list", cdf_int.contiguous().data_ptr() if n_list else None, bytes_.data_ptr(), bytes_.numel(),
-              nbytes.to(torch.int32).contiguous().data_ptr(), index.data_ptr(), index.numel(), nsym, seg_sym, int(L),
-              seg_idx.contiguous().data_ptr() if n_list else None, n_list, q.data_ptr() if n_list else None, status.data_ptr(),
-              ws.data_ptr(), _stream())
+    _lib.call("pccx_range_decode_indexed_list", cdf_p, bytes_.data_ptr(), bytes_.numel(), nbytes.data_ptr(), index.data_ptr(),
+              index.numel(), nsym, seg_sym, int(L), idx_p, n_list, q_p, status.data_ptr(), ws.data_ptr(), _stream())
     return q, status
 
 
 def index_status(data, stream_bytes, nsym, seg_sym):
     """pccx_entry_index_check_host on a bytes-like sidecar for a .p.bin of stream_bytes bytes (no GPU call): 0, or a key of INDEX_STATUS."""
-    import ctypes
-    data = bytes(data)
-    buf = ctypes.create_string_buffer(data, max(len(data), 1))
-    return int(_lib.load().pccx_entry_index_check_host(ctypes.addressof(buf), len(data), int(stream_bytes), int(nsym), int(seg_sym)))
+    return _host_check("pccx_entry_index_check_host", data, stream_bytes, nsym, seg_sym)

@@ -163,6 +163,10 @@ def test_probability_rows_of_listed_segments(request, nets, name, segs):
     assert torch.equal(got[valid], full[orig[valid]])
     assert torch.equal(prob.run_segments(case.rec[0], seg_idx, len(segs), G), got)
     assert prob.run_segments(case.rec[0], seg_idx, 0, G).shape == (0, D, L + 1)
+    # the listed and the whole-cloud tiled entry points share their kernels: every segment listed gives the tiled path's rows
+    P = -(-S // G)
+    every = prob.run_segments(case.rec[0], torch.arange(P, device="cuda", dtype=torch.int32), P, G)
+    assert torch.equal(every[:S], prob.run(case.rec[:1], ("cdf_int",), tiles=True)["cdf_int"][0])
 
 
 def _flip_unlisted(p_bytes, nbytes, P, listed):
