@@ -892,10 +892,11 @@ PCCX_API int pccx_quantize_st_backward(const float *x, const float *d_ydeq, int6
 PCCX_API int pccx_rate_from_logits(const float *logits, const float *y_q, int B, int bins, int ld_yq,
                                    float *out, void *stream);
 /* clip_grad_norm_ + torch.optim.Adam: accumulate sum g^2 over all tensors into acc (zeroed by the caller),
- * then one pccx_adam_step per tensor reads the norm on the device (gnorm_sq may be NULL = no clipping). */
+ * then one pccx_adam_step per tensor reads the norm on the device (gnorm_sq may be NULL = no clipping).  The betas are doubles:
+ * 1 - beta and 1 - beta^step are formed in double and rounded to float once, as torch.optim.Adam forms them. */
 PCCX_API int pccx_sumsq_accumulate(const float *g, int64_t n, double *acc, void *stream);
 PCCX_API int pccx_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
-                            const double *gnorm_sq, float max_norm, float lr, float beta1, float beta2,
+                            const double *gnorm_sq, float max_norm, float lr, double beta1, double beta2,
                             float eps, int step, void *stream);
 /* The same two steps over ALL parameter tensors in one launch each.  table_dev: ntensors rows of six int64 in device memory,
  * {param, grad, exp_avg, exp_avg_sq (device pointers), n (elements), first_block}; a workgroup handles 1024 consecutive elements
@@ -903,7 +904,7 @@ PCCX_API int pccx_adam_step(float *param, const float *grad, float *exp_avg, flo
  * (the device state below) replaces lr / step when not NULL.  Element for element the arithmetic of pccx_adam_step. */
 PCCX_API int pccx_sumsq_multi(const int64_t *table_dev, int ntensors, int64_t total_blocks, double *acc, void *stream);
 PCCX_API int pccx_adam_multi(const int64_t *table_dev, int ntensors, int64_t total_blocks, const double *gnorm_sq,
-                             float max_norm, const float *hyper_dev, float lr, int step, float beta1, float beta2,
+                             float max_norm, const float *hyper_dev, float lr, int step, double beta1, double beta2,
                              float eps, void *stream);
 /* Adam's per-step scalars kept on the device (torch.optim.Adam's `step` / bias_correction1/2, train_pppe_pcd_ae.py:216,220 via
  * optimizer.step()): a 32-byte, 8-byte aligned state
@@ -914,7 +915,7 @@ PCCX_API int pccx_adam_advance_dev(float *hyper, double beta1, double beta2, voi
 /* pccx_adam_step with lr and the bias corrections read from that device state (its first three floats).
  * No per-step launch argument, so the training step can be captured as a hipGraph (pccx.train.GraphedTrainStep). */
 PCCX_API int pccx_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
-                                const double *gnorm_sq, float max_norm, const float *hyper, float beta1, float beta2,
+                                const double *gnorm_sq, float max_norm, const float *hyper, double beta1, double beta2,
                                 float eps, void *stream);
 
 /* ---- 11b. The deterministic mode of the training step (pccx.train.step_scope(deterministic=True)): every accumulation of a

@@ -1098,10 +1098,12 @@ extern "C" int pccx_sumsq_accumulate(const float *g, int64_t n, double *acc, voi
 }
 
 // torch.optim.Adam (no weight decay, no amsgrad); the clip factor min(1, max_norm/(norm+1e-6)) is read from the
-// device-side squared norm so no host sync sits inside the step.
+// device-side squared norm so no host sync sits inside the step.  omb1 / omb2 = 1 - beta and bc1 / bc2 = 1 - beta^t arrive as floats
+// rounded ONCE from double (torch forms them in Python floats): 1.f - 0.999f is 1.3e-5 off 0.001, which put every increment of
+// exp_avg_sq 218 units of 2^-24 off where torch's own float32 Adam is within 3 (tests/test_optimizer.py).
 __global__ void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v, long n,
-                            const double *__restrict__ gnorm_sq, float max_norm, float lr, float b1, float b2, float eps, float bc1,
-                            float bc2)
+                            const double *__restrict__ gnorm_sq, float max_norm, float lr, float b1, float omb1, float b2, float omb2,
+                            float eps, float bc1, float bc2)
 {
     float clip = 1.f;
     if (gnorm_sq) {
@@ -1110,8 +1112,8 @@ __global__ void adam_kernel(float *__restrict__ p, const float *__restrict__ g, 
     }
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const float gi = g[i] * clip;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        const float mi = b1 * m[i] + omb1 * gi;
+        const float vi = b2 * v[i] + omb2 * gi * gi;
         m[i] = mi; v[i] = vi;
         const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
         p[i] = p[i] - (lr / bc1) * (mi / denom);
@@ -1121,8 +1123,8 @@ __global__ void adam_kernel(float *__restrict__ p, const float *__restrict__ g, 
 // The same update with lr and the two bias corrections read from DEVICE memory (hyper = {lr, 1 - beta1^t, 1 - beta2^t}): nothing
 // that changes from step to step is a launch argument, so the whole training step can be captured once as a hipGraph and replayed.
 __global__ void adam_dev_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v, long n,
-                                const double *__restrict__ gnorm_sq, float max_norm, const float *__restrict__ hyper, float b1, float b2,
-                                float eps)
+                                const double *__restrict__ gnorm_sq, float max_norm, const float *__restrict__ hyper, float b1, float omb1,
+                                float b2, float omb2, float eps)
 {
     const float lr = hyper[0], bc1 = hyper[1], bc2 = hyper[2];
     float clip = 1.f;
@@ -1132,8 +1134,8 @@ __global__ void adam_dev_kernel(float *__restrict__ p, const float *__restrict__
     }
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const float gi = g[i] * clip;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        const float mi = b1 * m[i] + omb1 * gi;
+        const float vi = b2 * v[i] + omb2 * gi * gi;
         m[i] = mi; v[i] = vi;
         const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
         p[i] = p[i] - (lr / bc1) * (mi / denom);
@@ -1179,8 +1181,8 @@ __global__ __launch_bounds__(256) void sumsq_multi_kernel(const MtRow *__restric
 }
 
 __global__ __launch_bounds__(256) void adam_multi_kernel(const MtRow *__restrict__ tab, int T, const double *__restrict__ gnorm_sq, float max_norm,
-                                                        const float *__restrict__ hyper, float lr, float bc1, float bc2, float b1, float b2,
-                                                        float eps)
+                                                        const float *__restrict__ hyper, float lr, float bc1, float bc2, float b1, float omb1,
+                                                        float b2, float omb2, float eps)
 {
     if (hyper) { lr = hyper[0]; bc1 = hyper[1]; bc2 = hyper[2]; }
     float clip = 1.f;
@@ -1195,8 +1197,8 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const MtRow *__restrict
         const long i = base + u * 256 + threadIdx.x;
         if (i >= row.n) break;
         const float gi = row.g[i] * clip;                              // the arithmetic of adam_kernel, element for element
-        const float mi = b1 * row.m[i] + (1.f - b1) * gi;
-        const float vi = b2 * row.v[i] + (1.f - b2) * gi * gi;
+        const float mi = b1 * row.m[i] + omb1 * gi;
+        const float vi = b2 * row.v[i] + omb2 * gi * gi;
         row.m[i] = mi; row.v[i] = vi;
         const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
         row.p[i] = row.p[i] - (lr / bc1) * (mi / denom);
@@ -1214,14 +1216,15 @@ extern "C" int pccx_sumsq_multi(const int64_t *table_dev, int ntensors, int64_t 
 }
 
 extern "C" int pccx_adam_multi(const int64_t *table_dev, int ntensors, int64_t total_blocks, const double *gnorm_sq, float max_norm,
-                               const float *hyper_dev, float lr, int step, float beta1, float beta2, float eps, void *stream)
+                               const float *hyper_dev, float lr, int step, double beta1, double beta2, float eps, void *stream)
 {
     if (ntensors == 0 || total_blocks == 0) return PCCX_OK;
     PCCX_CHECK_ARG(table_dev && ntensors >= 1 && total_blocks >= 1 && total_blocks <= 0x7fffffffLL && (hyper_dev || step >= 1),
                    "pccx_adam_multi: bad arguments");
-    const float bc1 = hyper_dev ? 1.f : 1.f - powf(beta1, (float)step), bc2 = hyper_dev ? 1.f : 1.f - powf(beta2, (float)step);
+    // the corrections in double, rounded once: the floats pccx_adam_advance_dev keeps in the device state
+    const float bc1 = hyper_dev ? 1.f : (float)(1.0 - pow(beta1, (double)step)), bc2 = hyper_dev ? 1.f : (float)(1.0 - pow(beta2, (double)step));
     hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, (const MtRow *)table_dev, ntensors,
-                       gnorm_sq, max_norm, hyper_dev, lr, bc1, bc2, beta1, beta2, eps);
+                       gnorm_sq, max_norm, hyper_dev, lr, bc1, bc2, (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }
@@ -1250,28 +1253,28 @@ extern "C" int pccx_adam_advance_dev(float *hyper, double beta1, double beta2, v
 }
 
 extern "C" int pccx_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const double *gnorm_sq,
-                                  float max_norm, const float *hyper, float beta1, float beta2, float eps, void *stream)
+                                  float max_norm, const float *hyper, double beta1, double beta2, float eps, void *stream)
 {
     if (n == 0) return PCCX_OK;
     PCCX_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && hyper, "pccx_adam_step_dev: bad arguments");
     long blocks = (n + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(adam_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, (long)n,
-                       gnorm_sq, max_norm, hyper, beta1, beta2, eps);
+                       gnorm_sq, max_norm, hyper, (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }
 
 extern "C" int pccx_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const double *gnorm_sq,
-                              float max_norm, float lr, float beta1, float beta2, float eps, int step, void *stream)
+                              float max_norm, float lr, double beta1, double beta2, float eps, int step, void *stream)
 {
     if (n == 0) return PCCX_OK;
     PCCX_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && step >= 1, "pccx_adam_step: bad arguments");
     long blocks = (n + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+    const float bc1 = (float)(1.0 - pow(beta1, (double)step)), bc2 = (float)(1.0 - pow(beta2, (double)step));
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, (long)n,
-                       gnorm_sq, max_norm, lr, beta1, beta2, eps, bc1, bc2);
+                       gnorm_sq, max_norm, lr, (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps, bc1, bc2);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }

@@ -684,6 +684,11 @@ class Adam:
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
         self.params = [p for p in params]
+        for i, p in enumerate(self.params):
+            # the kernels walk p, m and v by flat index against a contiguous copy of the gradient: on a dense but permuted parameter
+            # (a transposed view) the gradient would land on the wrong elements, silently
+            if not p.is_contiguous():
+                raise _lib.PccxError(f"Adam: parameter {i} (shape {tuple(p.shape)}, strides {p.stride()}) is not contiguous")
         self.lr, self.betas, self.eps, self.t = lr, betas, eps, 0
         self.m = [torch.zeros_like(p) for p in self.params]
         self.v = [torch.zeros_like(p) for p in self.params]
