@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """train.py with the reference's command line (train.py:22-50), on the MI355X path: ``--model AE`` (the IPDAE autoencoder) trains through
 pccx.train_ipdae; checkpoints carry the reference's names (ae_step{N}.pkl, prob_step{N}.pkl, optimizer_step{N}.pkl, global_step{N}.pkl,
-train.py:103-108) and the reference's state_dict keys, so compress.py / decompress.py load them unchanged."""
+train.py:103-108) and the reference's state_dict keys, so compress.py / decompress.py load them unchanged.  Two flags are this
+path's own: --octree-mode (the spelling of compress.py / decompress.py; 'full' trains on the centres those decode in that mode, the
+mode is not stored in the .pkl files) and --val_glob (the real codec's bpp and D1 on held-out files at every step window)."""
 import argparse
 import os
 from glob import glob
@@ -10,7 +12,7 @@ import numpy as np
 
 import _common  # noqa: F401
 import torch
-from pccx import models, plyio, train_ipdae
+from pccx import _lib, models, plyio, train_ipdae
 
 torch.manual_seed(11)                                                                  # train.py:17-19
 np.random.seed(11)
@@ -38,7 +40,14 @@ parser.add_argument('--device', default='cuda', help='AE Model Device (cuda)')
 parser.add_argument('--reset', action='store_true', help='Reset training and start from scratch (ignore saved model).')
 parser.add_argument('--autocast', action='store_true', help='bf16 operands on the matrix cores (the reference wraps its CUDA step in autocast, train.py:175).')
 parser.add_argument('--eager', action='store_true', help='launch every kernel of every step from Python instead of replaying the captured step.')
+parser.add_argument('--octree-mode', choices=['reference', 'full'], default='reference',
+                    help="the patch centres a step trains on: 'reference' = octree_np.decode as written (S must be 64); 'full' = the level-by-level "
+                         "decode, the centres compress.py / decompress.py --octree-mode full use (any S = N*ALPHA/K in 1..1024, at every --K of the table).")
+parser.add_argument('--val_glob', default=None, help='Point clouds glob pattern (files of --N points) run through the real codec at every --step_window.')
 parser.add_argument('--deterministic', action='store_true', help='every reduction of a step in a fixed order: the same inputs give the same bits, run after run (one GPU).')
+
+
+VAL_CHUNK = 16                         # clouds per codec batch of a --val_glob pass: the validation set's size does not bound the codec's buffers
 
 
 def latest(folder, prefix):
@@ -87,16 +96,34 @@ def main():
     print(f"Training {args.model} on {args.device}")
     print(f"N={N}, K={K}, S={args.S}, d={args.d}, L={args.L}")
     print(f"deterministic={args.deterministic}, autocast={args.autocast}, eager={args.eager}")
+    if args.octree_mode == 'full':
+        # the mode is NOT stored in the reference-named .pkl files: both sides of the codec have to be told
+        print("octree_mode=full: these checkpoints are for compress.py/decompress.py --octree-mode full")
+        try:
+            train_ipdae.check_selection(args.S, K, args.octree_mode)                   # any S in range, before anything is read or allocated
+        except _lib.PccxError as e:
+            raise SystemExit(str(e))
     os.makedirs(args.model_save_folder, exist_ok=True)
     files = sorted(glob(args.train_glob, recursive=True))
     points = np.stack([plyio.read_point_cloud(f) for f in files]).astype(np.float32)   # pn_kit.read_point_clouds (pn_kit.py:36-42)
     print(f"Loaded {points.shape} points, range: [{points.min()}, {points.max()}]")
     data = torch.from_numpy(points).to(args.device)                                    # the whole training set lives in HBM
+    val = None
+    if args.val_glob:
+        val_files = sorted(glob(args.val_glob, recursive=True))
+        val_points = [plyio.read_point_cloud(f) for f in val_files]                    # read once
+        bad = [f for f, p in zip(val_files, val_points) if p.shape[0] != N]
+        if bad or not val_files:
+            raise SystemExit(f"--val_glob: {'no file matches' if not val_files else f'files without --N = {N} points: {bad}'}")
+        val = torch.from_numpy(np.stack(val_points).astype(np.float32)).to(args.device)
+        val_starts = torch.zeros(len(val_files), dtype=torch.long)                     # the same patches at every window
+        print(f"Loaded {tuple(val.shape)} validation points")
     ae = models.AE(K=K, k=args.k, d=args.d, L=args.L).to(args.device)
     prob = models.ConditionalProbabilityModel(args.L, args.d).to(args.device)
     tr = train_ipdae.IpdaeTrainer(ae, prob, N=N, N0=args.N0, ALPHA=args.ALPHA, K=K, lr=args.lr, lamda=args.lamda,
                                   rate_loss_enable_step=args.rate_loss_enable_step, lr_decay=args.lr_decay,
-                                  lr_decay_steps=args.lr_decay_steps, autocast=args.autocast, deterministic=args.deterministic)
+                                  lr_decay_steps=args.lr_decay_steps, autocast=args.autocast, deterministic=args.deterministic,
+                                  octree_mode=args.octree_mode)
     if not args.reset:
         tr.global_step = load_checkpoints(tr, args.model_save_folder)                  # :137-144
         print(f"Resuming from step {tr.global_step}")
@@ -125,6 +152,12 @@ def main():
                       f"Loss: {np.mean(losses):.5f}")
                 losses, fbpps, bpps = [], [], []
                 dump_checkpoints(tr, args.model_save_folder, tr.global_step)
+                if val is not None:
+                    # the real codec on the current weights (validate repacks them), VAL_CHUNK clouds at a time: means weighted by v['n']
+                    vs = [tr.validate(val[i:i + VAL_CHUNK], val_starts[i:i + VAL_CHUNK]) for i in range(0, len(val), VAL_CHUNK)]
+                    n = sum(v['n'] for v in vs)
+                    print(f"[Epoch {epoch}] Step {tr.global_step} | Val bpp: {sum(v['bpp'] * v['n'] for v in vs) / n:.5f} | "
+                          f"Val D1: {sum(v['d1_psnr'] * v['n'] for v in vs) / n:.3f} dB ({n} clouds)")
             if tr.lr != lr_before:
                 print(f"LR decayed to {tr.lr} at step {tr.global_step}")               # :254
         if tr.global_step > args.max_steps:

@@ -292,6 +292,8 @@ class AE(nn.Module):
         self._dec_blob = _pack("pccx_pack_ae_decoder", lib.pccx_ae_decoder_blob_floats(self.k), self._dec_tensors(),
                                [self.k, self.d]).to(device) if self.fused_d else None
         self._derived_blobs.clear()
+        for m in (self.sa, self.pn, self.inv_pool, self.inv_mlp):         # the generic path's packed copies: rebuilt on their next use
+            m._layers = None
         return self
 
     def _enc_tensors(self):
@@ -527,8 +529,9 @@ class ConditionalProbabilityModel(nn.Module):
         return self.d <= 16 and self.L <= 15 and self.d * self.L <= 128 and S % 16 == 0 and S >= 16
 
     def pack(self, device="cuda"):
+        self._layers = self.model_pn._layers = None                   # the generic path's packed copies: rebuilt on their next use
         if not self.fused_ok():
-            self._blob = self._layers = None
+            self._blob = None
             return self
         sd = self.state_dict()
         w = lambda key: sd[key].reshape(sd[key].shape[0], -1)

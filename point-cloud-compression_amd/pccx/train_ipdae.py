@@ -17,10 +17,14 @@ Adam is pccx.train.Adam (two launches over all tensors).  The models are pccx.mo
 are the reference's state_dict, and the checkpoints this trainer writes load into the codec (compress.py:58) unchanged.
 fp32 by default (the reference's CPU branch, contextlib.nullcontext at :175); autocast=True is the bf16 form of pccx.train.
 AE.py has no BatchNorm on this path (bn=False at AE.py:16-27).  ``--model PPPF-AE`` (train-mode BatchNorm over GROUPED rows) is not built.
+octree_mode="full" (select_patches, forward_loss, IpdaeTrainer; train.py --octree-mode full) replaces :184 by the intended decode and
+normalises every cloud by its own box: the trainer then selects, bit for bit, the patches ``compress.py --octree-mode full`` codes, for
+any S = N * ALPHA / K up to 1024 (clouds above 32768 points through the grid's wide-K walk, as the codec), and IpdaeTrainer.validate runs the current weights through that codec.
 """
 import torch
 
 from . import _lib, ops, train
+from .codec import KNN_BRUTE_MAX_N
 from .train import GroupMaxFn, LinearFn, ReluFn
 
 OCTREE_BPP_DICT = {1024: 0.07, 512: 0.125, 256: 0.25, 128: 0.5, 64: 1.0}      # pn_kit.py:17-23
@@ -133,35 +137,58 @@ def estimate_bits_from_pmf(pmf, sym):
     return torch.sum(-torch.log2(p.clamp(min=1e-3)))
 
 
-def select_patches(batch_x, S, K, N, N0, starts):
-    """train.py:171-199 -- everything in front of the networks: depends on the data and the FPS start indices only.
-    -> (batch_x normalised (B,N,3), rec_sampled_xyz (B,S,3), x_patches (B*S,K,3) scaled, sampled_bits (device scalar), scale)
-    Nothing here reads a result on the host: the whole step can be captured into a hipGraph (GraphedIpdaeStep)."""
-    B = batch_x.shape[0]
-    if S != 64:
+OCTREE_MODES = ("reference", "full")                                           # the spelling of compress.py / decompress.py --octree-mode
+
+
+def check_selection(S, K, octree_mode="reference"):
+    """The limits of select_patches, on the host and before any launch: ValueError for an unknown mode, PccxError naming the limit."""
+    if octree_mode not in OCTREE_MODES:
+        raise ValueError(f"train_ipdae: octree_mode must be one of {OCTREE_MODES}, got {octree_mode!r}")
+    if octree_mode == "reference" and S != 64:
         raise _lib.PccxError(f"train_ipdae: octree_np.decode returns 64 centres whatever it is given (octree_np.py:100-111); S = N * ALPHA / K "
                              f"must be 64 (got {S})")
+    if not 1 <= S <= ops.PATCH_GROUPS_MAX_S:
+        raise _lib.PccxError(f"train_ipdae: octree_mode='full' trains on S = N * ALPHA / K patches in 1..{ops.PATCH_GROUPS_MAX_S} (the narrow octree "
+                             f"coder and decode and the one-workgroup FPS, which a captured step can hold), got S = {S}")
     if K not in OCTREE_BPP_DICT:
         raise _lib.PccxError(f"train_ipdae: --K must be one of {sorted(OCTREE_BPP_DICT)} (pn_kit.py:17-23), got {K}")
-    # :171 -- pn_kit.normalize reads the centre and the longest side from pc[0] ONLY (pn_kit.py:50-53: "one point cloud"; train.py:40 says
-    # the batch size must be 1) and applies them to whatever it is given: a batch is normalised by its FIRST cloud's box.  Reproduced.
-    x, c0, l0 = ops.normalize(batch_x[:1].contiguous(), margin=0.01)
-    if B > 1:
-        rest = ((batch_x[1:].float() - c0.view(1, 1, 3)) * (1 - 0.01)) / l0.view(1, 1, 1) + 0.5       # pn_kit.py:55-57, op for op
-        x = torch.cat([x, rest], dim=0).contiguous()
+
+
+def select_patches(batch_x, S, K, N, N0, starts, octree_mode="reference"):
+    """train.py:171-199 -- everything in front of the networks: depends on the data and the FPS start indices only.
+    -> (batch_x normalised (B,N,3), rec_sampled_xyz (B,S,3), x_patches (B*S,K,3) scaled, sampled_bits (device scalar), scale)
+    Nothing here reads a result on the host: the whole step can be captured into a hipGraph (GraphedIpdaeStep).
+    octree_mode="full": the centres are the level-by-level decode of the octree stream, the ones ``compress.py --octree-mode full``
+    centres its patches on, S anywhere in 1..ops.PATCH_GROUPS_MAX_S, and every cloud is normalised by its own box.  x, rec and patches are
+    then bit for bit the pcn, rec_sampled and patches of Codec(octree_mode="full", group_duplicates=False).compress(keep_extras=True)."""
+    B = batch_x.shape[0]
+    check_selection(S, K, octree_mode)
+    if octree_mode == "full":
+        x, _, _ = ops.normalize(batch_x, margin=0.01)                                 # compress.py:90, one box per cloud as Codec.compress
+    else:
+        # :171 -- pn_kit.normalize reads the centre and the longest side from pc[0] ONLY (pn_kit.py:50-53: "one point cloud"; train.py:40
+        # says the batch size must be 1) and applies them to whatever it is given: a batch is normalised by its FIRST cloud's box.  Reproduced.
+        x, c0, l0 = ops.normalize(batch_x[:1].contiguous(), margin=0.01)
+        if B > 1:
+            rest = ((batch_x[1:].float() - c0.view(1, 1, 3)) * (1 - 0.01)) / l0.view(1, 1, 1) + 0.5       # pn_kit.py:55-57, op for op
+            x = torch.cat([x, rest], dim=0).contiguous()
     sampled = ops.index_points(x, ops.farthest_point_sample_batch(x, S, starts))      # :178
     enc = ops.octree_encode(sampled, N, OCTREE_BPP_DICT[K])                           # :183
-    rec, _ = ops.octree_decode(enc["bytes"], enc["nbytes"], "reference", S)           # :184
+    rec, _ = ops.octree_decode(enc["bytes"], enc["nbytes"], octree_mode, S)           # :184 as written ("reference") or as intended ("full")
     sampled_bits = enc["nbits"].sum()                                                 # codebits: the streams' lengths in bits (device scalar)
     scale = float((N / N0) ** (1 / 3))
-    patches = ops.knn_points(rec, x, K, patch_scale=scale).knn.view(B * S, K, 3)      # :192-199
+    # :192-199.  The all-pairs kernels keep a cloud's keys in LDS and stop at KNN_BRUTE_MAX_N = 32768 points; above it (K >= 128 at the
+    # larger S of "full" mode) the grid's wide-K walk finds the same patches bit for bit, by Codec.compress's own rule (knn_search="auto").
+    # Both are stream-ordered launches without a read-back, so the captured step holds either.
+    patches = ops.knn_points(rec, x, K, patch_scale=scale, search="grid" if x.shape[1] > KNN_BRUTE_MAX_N else None).knn.view(B * S, K, 3)
     return x, rec, patches, sampled_bits, scale
 
 
-def forward_loss(ae, prob, batch_x, starts, lam, S, K, N, N0):
-    """the forward of train.py:171-222 -> (loss, fbpp, bpp) with the graph of loss recorded"""
+def forward_loss(ae, prob, batch_x, starts, lam, S, K, N, N0, octree_mode="reference"):
+    """the forward of train.py:171-222 -> (loss, fbpp, bpp) with the graph of loss recorded; octree_mode as select_patches takes it (the
+    loss arithmetic is the same in both modes)"""
     B = batch_x.shape[0]
-    x, rec, patches, sampled_bits, scale = select_patches(batch_x, S, K, N, N0, starts)
+    x, rec, patches, sampled_bits, scale = select_patches(batch_x, S, K, N, N0, starts, octree_mode)
     patches_pred, _, q = ae_forward_train(ae, patches)                                # :200
     patches_pred = patches_pred / scale                                               # :201
     pmf = prob_forward_train(prob, rec)                                               # :204
@@ -179,9 +206,13 @@ class IpdaeTrainer:
     rate term switched on at rate_loss_enable_step (:218-221) and the learning-rate decay (:250-254)."""
 
     def __init__(self, ae, prob, N=8192, N0=1024, ALPHA=2, K=256, lr=0.0005, lamda=1e-6, rate_loss_enable_step=40000, lr_decay=0.1,
-                 lr_decay_steps=60000, autocast=False, deterministic=False):
+                 lr_decay_steps=60000, autocast=False, deterministic=False, octree_mode="reference"):
         self.ae, self.prob = ae, prob
         self.N, self.N0, self.K, self.S = int(N), int(N0), int(K), int(N) * int(ALPHA) // int(K)
+        self.ALPHA = int(ALPHA)
+        if octree_mode != "reference":                                # "reference" keeps refusing at its first step, as before
+            check_selection(self.S, self.K, octree_mode)
+        self.octree_mode = octree_mode
         self.lamda, self.rate_loss_enable_step = float(lamda), int(rate_loss_enable_step)
         self.lr, self.lr_decay, self.lr_decay_steps = float(lr), float(lr_decay), int(lr_decay_steps)
         self.autocast, self.deterministic = bool(autocast), bool(deterministic)
@@ -199,7 +230,7 @@ class IpdaeTrainer:
             # device's running double product differ in the last bit, and the eager and the replayed step are to give the same bits
             self.opt.make_capturable(batch_x.device)
         with train.step_scope(batch_x.device, None, self.autocast, self.opt.params, deterministic=self.deterministic) as forward_done:     # :173 optimizer.zero_grad()
-            loss, fbpp, bpp = forward_loss(self.ae, self.prob, batch_x, starts, lam, self.S, self.K, self.N, self.N0)
+            loss, fbpp, bpp = forward_loss(self.ae, self.prob, batch_x, starts, lam, self.S, self.K, self.N, self.N0, self.octree_mode)
             forward_done()
             loss.backward()                                                           # :229
             self.opt.step(max_norm=None)                                              # :230
@@ -208,6 +239,32 @@ class IpdaeTrainer:
             self.lr *= self.lr_decay
             self.opt.set_lr(self.lr)
         return dict(loss=float(loss.detach()), fbpp=float(fbpp.detach()), bpp=float(bpp.detach()))
+
+    def validate(self, clouds, starts, **codec_kw):
+        """The current weights through the real codec: clouds (B, N, 3) on the device, starts the FPS start index per cloud ->
+        dict(bpp = the mean true rate, Compressed.bpp(): the bits of the three files, not the estimate of the loss; d1_psnr = the mean
+        codec.d1_psnr of decompress(compress(clouds)); n = B).  The codec is codec.Codec(ae, prob, K, ALPHA, N0, octree_mode of this
+        trainer, **codec_kw), run under torch.no_grad().
+
+        ae.pack() and prob.pack() come FIRST, and must: the codec reads the weights from packed blobs (AE._enc_blob / _dec_blob /
+        _derived_blobs, the probability model's _blob, the generic layers' packed copies) that only pack() and load_state_dict() drop,
+        while Adam moves the parameters in place -- without the two calls a codec built after a training step would still code with the
+        weights of the last pack.  Training itself never reads a blob, so nothing else needs the calls."""
+        from . import codec
+        comp, out = self.validation_pass(clouds, starts, **codec_kw)
+        return dict(bpp=float(comp.bpp().mean()), d1_psnr=float(codec.d1_psnr(clouds, out).mean()), n=int(clouds.shape[0]))
+
+    def validation_pass(self, clouds, starts, **codec_kw):
+        """validate's codec run itself -> (the Compressed, the decompressed clouds (B, S*k, 3)); repacks first, as validate explains"""
+        from . import codec
+        if clouds.dim() != 3 or clouds.shape[1] != self.N or clouds.shape[2] != 3:
+            raise _lib.PccxError(f"train_ipdae: validate takes (B, {self.N}, 3), got {tuple(clouds.shape)}")
+        with torch.no_grad():
+            self.ae.pack(clouds.device)
+            self.prob.pack(clouds.device)
+            cd = codec.Codec(self.ae, self.prob, self.K, self.ALPHA, self.N0, octree_mode=self.octree_mode, **codec_kw)
+            comp = cd.compress(clouds, starts)
+            return comp, cd.decompress(comp, S=self.S)
 
     def graphed(self, batch_x, starts, warmup=2, keep_graph=False):
         """-> GraphedIpdaeStep over this trainer's models and optimizer (the warm-up iterations are real steps on batch_x)"""
@@ -250,7 +307,7 @@ class GraphedIpdaeStep:
     def _body(self):
         tr = self.tr
         with train.step_scope(self.x.device, self.arena, tr.autocast, tr.opt.params, deterministic=tr.deterministic) as forward_done:
-            loss, fbpp, bpp = forward_loss(tr.ae, tr.prob, self.x, self.starts, self.lam, tr.S, tr.K, tr.N, tr.N0)
+            loss, fbpp, bpp = forward_loss(tr.ae, tr.prob, self.x, self.starts, self.lam, tr.S, tr.K, tr.N, tr.N0, tr.octree_mode)
             forward_done()
             loss.backward()
             tr.opt.step(max_norm=None)
