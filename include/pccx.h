@@ -785,6 +785,42 @@ PCCX_API int pccx_softmax_cdf(const float *logits, int64_t rows, int L, float *p
  * out (P*k, 3) = ((patch / scale) + centres[patch] - 0.5) * longest[b] / (1 - margin) + center[b], b = patch / S. */
 PCCX_API int pccx_reassemble(const float *patches, int64_t P, int k, float scale, const float *centres, const float *nrm_center,
                              const float *nrm_longest, int S, double margin, float *out, void *stream);
+
+/* ---- ragged batches: clouds of different sizes in one launch sequence (octree mode "full") ----------------
+ * Cloud b holds n[b] points in the first rows of its (N_max, 3) slab and S[b] = n[b]*ALPHA/K centres in the first rows of its
+ * (S_max, 3) slab; the rows behind them are padding whose contents never reach a result.  The per-cloud counts and scales are
+ * device arrays of B entries.  Each entry is its dense namesake with the count taken per cloud: the same operations in the same
+ * order, so what cloud b gets is bit for bit what the dense entry gives on the unpadded cloud alone.  A count outside its range is
+ * clamped into it by the kernels (they never index out of a slab); the host layer refuses such a batch before any launch.
+ *
+ * pccx_normalize_n: the box over the rows < n[b]; out rows from n[b] on are written as zeros.
+ * pccx_fps_n: cloud b runs npoint[b] <= npoint_max rounds over its n[b] points; idx_out (B, npoint_max), the entries from
+ *   npoint[b] on repeat the last selected index.  N_max <= 32768; workspace: B*N_max floats when N_max > 16384, else may be NULL.
+ * pccx_octree_encode_n: pccx_octree_encode with each cloud's own S[b] and N[b] in the depth search; rows >= S[b] are not read;
+ *   the strides of bits / bytes are those of pccx_octree_bits_capacity(S_max).  S_max <= 1024.
+ * pccx_knn_list_n: pccx_knn_list with N -> n[b] (K <= n[b]) and patch_scale -> scale[b]; the kernel is chosen by N_max.
+ * pccx_range_encode_n / pccx_range_decode_n: nsym is the row stride of cdf_int / latent_q in symbols; cloud b codes or decodes its
+ *   first nsym_of[b] <= nsym symbols from a fresh state and flushes as pccx_range_encode does: the bytes are that entry's on the
+ *   same table and symbols.  Decode writes zeros behind them; foreign bytes are taken as pccx_range_decode takes them.  The kernel
+ *   form is pccx_range_coder_form's for the row.
+ * pccx_reassemble_n: pccx_reassemble's formula with scale[b] on the patches < S[b] of cloud b; patches (B*S_max, k, 3) -> out
+ *   (B, S_max*k, 3), of which the rows from S[b]*k on are not written. */
+PCCX_API int pccx_normalize_n(const float *pc, int B, int N_max, const int32_t *n, double margin, float *out, float *center,
+                              float *longest, void *stream);
+PCCX_API int pccx_fps_n(const float *xyz, int B, int N_max, const int32_t *n, int npoint_max, const int32_t *npoint,
+                        const int32_t *start_idx, int64_t *idx_out, float *workspace, void *stream);
+PCCX_API int pccx_octree_encode_n(const float *centres, int B, int S_max, const int32_t *S, const int32_t *N, double min_bpp,
+                                  uint8_t *bits, int32_t *nbits, int32_t *depth, uint8_t *bytes, int32_t *nbytes, void *stream);
+PCCX_API int pccx_knn_list_n(const float *q, int B, int M, const float *ref, int N_max, const int32_t *n, int K, float *dists,
+                             int64_t *idx, float *nn, const float *scale, const int32_t *rep, void *stream);
+PCCX_API int pccx_range_encode_n(const int32_t *cdf_int, const float *latent_q, int B, int nsym, const int32_t *nsym_of, int L,
+                                 uint8_t *out, int cap, int32_t *nbytes, void *stream);
+PCCX_API int pccx_range_decode_n(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes, int B, int nsym,
+                                 const int32_t *nsym_of, int L, float *latent_q, void *stream);
+PCCX_API int pccx_reassemble_n(const float *patches, int B, int S_max, const int32_t *S, int k, const float *scale,
+                               const float *centres, const float *nrm_center, const float *nrm_longest, double margin, float *out,
+                               void *stream);
+
 /* out[r][c] = act(base[r / div][c] + sum_{k<Ks} x[(mod ? r % mod : r)][k] * w[c][k]), Ks <= 4, C % 4 == 0: the per-point part of a
  * layer whose input rows are [small per-point part | long per-patch part] (FoldingNet's [grid | latent] and [coarse | latent],
  * PPPF_AE.py:99-107); base = the per-patch part's Linear (bias included), one row per patch.  w is (C, Ks) row-major. */

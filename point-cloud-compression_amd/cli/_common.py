@@ -91,5 +91,13 @@ def add_codec_flags(parser):
                         help="Keep .p.bin the reference's single stream and write / read an entry-point index <name>.p.idx beside it: the "
                              "coder's state every G patches (12 bytes each), so that decompress.py decodes the one stream with one wave "
                              "per G patches and --region can enter it.  0 = no index.  Excludes --p-split.")
+    parser.add_argument('--ragged', action='store_true',
+                        help="Needs --octree-mode full.  Files of different point counts share a launch sequence (Codec.compress_ragged / "
+                             "decompress_ragged): up to --batch files per call, each of K..32768 points and at most 1024 patches; other files "
+                             "go the usual way, one point count per call, on both tools (they route file by file by the same rule on the "
+                             "patch count).  Excludes --p-split, --p-index, --knn-search grid and compress.py's block centres.  The file formats do not change, and a cloud whose patch count "
+                             "S = N*ALPHA/K is a multiple of 16 gets the very files written without this flag.  For every other S the "
+                             "probability tables are the fused kernel's on the centres padded to a multiple of 16, which may differ in the "
+                             "last unit from the tables used without the flag: such files must be written AND read with --ragged.")
     parser.add_argument('--batch', type=int, default=256, help='Clouds per launch sequence.')
     parser.add_argument('--seed', type=int, default=11, help='Seed of the per-file FPS start index.')

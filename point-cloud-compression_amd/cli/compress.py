@@ -29,6 +29,8 @@ parser.add_argument('--fps-block', type=int, default=8192, metavar='N',
 
 def main():
     args = parser.parse_args()
+    if args.ragged and (args.octree_mode != 'full' or args.p_split or args.p_index or args.centres != 'fps' or args.knn_search == 'grid'):
+        raise SystemExit("--ragged needs --octree-mode full and excludes --p-split, --p-index, --centres blocks and --knn-search grid")
     print(f"Processing on device (gpu/cpu): {args.device}")
     os.makedirs(args.compressed_path, exist_ok=True)
     files = sorted(glob(args.input_glob, recursive=True))
@@ -44,21 +46,29 @@ def main():
         while todo:
             clouds = [(i, f, plyio.read_point_cloud(f)) for i, f in todo[:args.batch]]          # outside the timed window
             n0 = clouds[0][2].shape[0]
-            batch = [c for c in clouds if c[2].shape[0] == n0]                                   # one launch = one N
+            # --ragged: every file of the chunk that is inside the ragged path's limits, whatever its point count, in one launch sequence
+            fits = [c for c in clouds if cd.ragged_refusal([c[2].shape[0]]) is None] if args.ragged else []
+            batch = fits or [c for c in clouds if c[2].shape[0] == n0]                           # otherwise one launch = one N
+            if args.ragged and not fits:                                                         # all of one N: one reason
+                print(f"{', '.join(os.path.split(c[1])[1] for c in batch)}: outside --ragged, compressed the usual way: {cd.ragged_refusal([n0])}")
             done = {c[0] for c in batch}
             todo = [t for t in todo if t[0] not in done]
-            pc = torch.from_numpy(np.stack([c[2] for c in batch])).to(args.device)
-            starts = [dist.fps_start_index(args.seed, c[0], n0) for c in batch]
+            sizes = [c[2].shape[0] for c in batch]
+            starts = [dist.fps_start_index(args.seed, c[0], n) for c, n in zip(batch, sizes)]
+            if fits:
+                pc = codec.pad_clouds([c[2] for c in batch])[0].to(args.device)
+            else:
+                pc = torch.from_numpy(np.stack([c[2] for c in batch])).to(args.device)
             torch.cuda.synchronize()
             t0 = time.time()                                                                     # compress.py:85
-            comp = cd.compress(pc, starts)
+            comp = cd.compress_ragged(pc, sizes, starts) if fits else cd.compress(pc, starts)
             # ONE D2H of the batch's packed streams, then the library's host threads cut the three files of every cloud out of it
             # (pccx_write_streams_host): <name>.p.bin / .s.bin / .c.bin, the bytes of compress.py:139-152; with --p-index also <name>.p.idx
             nbytes = comp.write_files(args.compressed_path, [os.path.split(f)[1] for _, f, _ in batch])
             times += [(time.time() - t0) / len(batch)] * len(batch)                              # compress.py:154
             bits += 8 * nbytes
             index_bits += int(comp.index_bits().sum())                                           # derived from the shape: no transfer
-            points += n0 * len(batch)
+            points += sum(sizes)
     # the six-slot vector of dist.SUMMARY_FIELDS; this tool has no PSNR to report, so slot 2 ("psnr_sum") carries the sidecars' bits.
     # Summed over ranks here, never passed to dist.reduce_summaries.
     g = dist.gather_summaries([bits, points, index_bits, 0.0, len(times), float(np.sum(times))], _common.summary_device(args))

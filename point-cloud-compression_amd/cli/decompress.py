@@ -44,6 +44,9 @@ def main():
         raise SystemExit("--crop / --region-halo need --region")
     if args.p_split and args.p_index:
         raise SystemExit("--p-index and --p-split exclude each other")
+    if args.ragged and (args.octree_mode != 'full' or args.region is not None or args.p_split or args.p_index or args.S is not None
+                        or args.knn_search == 'grid'):
+        raise SystemExit("--ragged needs --octree-mode full and excludes --region, --p-split, --p-index, --knn-search grid and --S")
     if args.build_index and not args.p_index:
         raise SystemExit("--build-index needs --p-index G")
     print(f"Processing on device (gpu/cpu): {args.device}")
@@ -141,8 +144,22 @@ def main():
                     print(f"{n}: {reg.patch_idx.numel()} patches from {reg.segments.numel()} of {reg.n_segments_total} segments")
                     clouds[j] = pts.cpu().numpy()
             else:
-                for S in sorted(set(S_of.tolist())):                                             # one launch sequence per S
-                    sel = torch.from_numpy(np.flatnonzero(S_of == S)).to(args.device)
+                usual = np.ones(len(chunk), dtype=bool)
+                if args.ragged:
+                    # file by file, by the rule compress.py --ragged routes by (Codec.ragged_patch_range): every file inside it in one
+                    # launch sequence whatever its S, the others the way they were written
+                    why = [cd.ragged_decode_refusal([int(S)]) for S in S_of.tolist()]
+                    usual = np.array([w is not None for w in why])
+                    for n, w in zip(chunk, why):
+                        if w is not None:
+                            print(f"{n}: outside --ragged, decompressed the usual way: {w}")
+                    if not usual.all():
+                        sel = torch.from_numpy(np.flatnonzero(~usual)).to(args.device)
+                        pcs = cd.decompress_ragged(codec.Compressed(s_b[sel], s_n[sel], p_b[sel], p_n[sel], c[sel], 0), S_of[~usual].tolist())
+                        for j, pts in zip(sel.cpu().tolist(), pcs):
+                            clouds[j] = pts.cpu().numpy()
+                for S in sorted(set(S_of[usual].tolist())):                                      # one launch sequence per S
+                    sel = torch.from_numpy(np.flatnonzero((S_of == S) & usual)).to(args.device)
                     comp = codec.Compressed(s_b[sel], s_n[sel], p_b[sel], p_n[sel], c[sel], 0)
                     if side is not None:
                         comp.p_index = side[int(S)][0]                                           # rows in the order of `sel`: ascending j

@@ -24,13 +24,12 @@ __device__ __forceinline__ float wave_max(float v)
     return v;
 }
 
-__global__ __launch_bounds__(1024) void normalize_kernel(const float *__restrict__ pc, int N, float one_minus_margin,
-                                                         float *__restrict__ out, float *__restrict__ center,
-                                                         float *__restrict__ longest)
+// One cloud by its 1024-thread workgroup: p / o = the cloud's N rows in and out, b = its slot in center / longest.
+__device__ __forceinline__ void normalize_cloud(const float *__restrict__ p, int N, float one_minus_margin, float *__restrict__ o,
+                                                float *__restrict__ center, float *__restrict__ longest, int b)
 {
     __shared__ float red[6][16];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const float *p = pc + (size_t)b * N * 3;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int i = tid; i < N; i += 1024) {
 #pragma unroll
@@ -56,7 +55,6 @@ __global__ __launch_bounds__(1024) void normalize_kernel(const float *__restrict
     }
     if (tid < 3) center[3 * b + tid] = c[tid];
     if (tid == 0) longest[b] = lg;
-    float *o = out + (size_t)b * N * 3;
     for (int i = tid; i < 3 * N; i += 1024) {
         const int a = i % 3;
         const float ca = a == 0 ? c[0] : (a == 1 ? c[1] : c[2]);
@@ -64,6 +62,31 @@ __global__ __launch_bounds__(1024) void normalize_kernel(const float *__restrict
         v = __fdiv_rn(__fmul_rn(v, one_minus_margin), lg);         // *(1-m)/longest   (:57)
         o[i] = __fadd_rn(v, 0.5f);                                 // + 0.5            (:58)
     }
+}
+
+__global__ __launch_bounds__(1024) void normalize_kernel(const float *__restrict__ pc, int N, float one_minus_margin,
+                                                         float *__restrict__ out, float *__restrict__ center,
+                                                         float *__restrict__ longest)
+{
+    const int b = blockIdx.x;
+    normalize_cloud(pc + (size_t)b * N * 3, N, one_minus_margin, out + (size_t)b * N * 3, center, longest, b);
+}
+
+// Ragged batch: cloud b holds n[b] points in rows of N_max; the rows from n[b] on are padding, never read, and come out as zeros.
+__device__ __forceinline__ int ragged_count(const int32_t *__restrict__ n, int b, int lo, int hi)
+{
+    const int v = n[b];
+    return v < lo ? lo : (v > hi ? hi : v);
+}
+
+__global__ __launch_bounds__(1024) void normalize_n_kernel(const float *__restrict__ pc, int N_max, const int32_t *__restrict__ n,
+                                                           float one_minus_margin, float *__restrict__ out,
+                                                           float *__restrict__ center, float *__restrict__ longest)
+{
+    const int b = blockIdx.x, nb = ragged_count(n, b, 1, N_max);
+    float *o = out + (size_t)b * N_max * 3;
+    normalize_cloud(pc + (size_t)b * N_max * 3, nb, one_minus_margin, o, center, longest, b);
+    for (int i = 3 * nb + threadIdx.x; i < 3 * N_max; i += 1024) o[i] = 0.f;
 }
 
 __global__ void denormalize_kernel(const float *__restrict__ pc, int N, float one_minus_margin,
@@ -86,6 +109,18 @@ extern "C" int pccx_normalize(const float *pc, int B, int N, double margin, floa
     PCCX_CHECK_ARG(pc && out && center && longest, "pccx_normalize: null pointer");
     PCCX_CHECK_ARG(B >= 0 && N >= 1, "pccx_normalize: bad shape B=%d N=%d", B, N);
     hipLaunchKernelGGL(normalize_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, pc, N, (float)(1.0 - margin), out,
+                       center, longest);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+extern "C" int pccx_normalize_n(const float *pc, int B, int N_max, const int32_t *n, double margin, float *out, float *center,
+                                float *longest, void *stream)
+{
+    if (B == 0) return PCCX_OK;
+    PCCX_CHECK_ARG(pc && n && out && center && longest, "pccx_normalize_n: null pointer");
+    PCCX_CHECK_ARG(B >= 0 && N_max >= 1, "pccx_normalize_n: bad shape B=%d N_max=%d", B, N_max);
+    hipLaunchKernelGGL(normalize_n_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, pc, N_max, n, (float)(1.0 - margin), out,
                        center, longest);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
@@ -240,14 +275,14 @@ __device__ __forceinline__ void wave_argmax(float &v, int &i)
 // out to be bound by the EXECUTION of its vector instructions (16 waves x ~100 instructions x 4 cycles on 4 SIMDs ~ 0.7 us of a 1.47 us
 // round), not by its latencies, so the second workgroup buys only the barrier waits.  Indices: the same arithmetic per point, the same
 // first-maximum rule (bit-identical).  The second template parameter is unused (kept for the instantiation names in the profiles).
-template <int PPT, bool USE_LDS>
-__global__ __launch_bounds__(1024) void fps_kernel(const float *__restrict__ xyz, int N, int npoint,
-                                                   const int32_t *__restrict__ start, int64_t *__restrict__ out)
+// fps_cloud: one cloud by its workgroup -- p = its N rows, far = its (checked) start index, out = its npoint indices.  Returns the last
+// index written (the ragged kernel repeats it in the rest of its row).
+template <int PPT>
+__device__ __forceinline__ int fps_cloud(const float *__restrict__ p, int N, int npoint, int far, int64_t *__restrict__ out)
 {
     __shared__ unsigned long long part_k[2][16];              // wave winners as 64-bit keys (argmax_key)
     __shared__ float part_c[2][16][4];                        // ... and their coordinates
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const float *p = xyz + (size_t)b * N * 3;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
 
     // Points live in registers in PAIRS (point tid + 2j*1024 and tid + (2j+1)*1024): the three differences, squares and the two adds
     // of a round run as packed fp32 (v_pk_add_f32 / v_pk_mul_f32, no contraction: -ffp-contract=off), i.e. the operation sequence
@@ -269,12 +304,11 @@ __global__ __launch_bounds__(1024) void fps_kernel(const float *__restrict__ xyz
             }
         }
 
-    int far = start ? start[b] : 0;
-    if (far < 0 || far >= N) far = 0;
     float cx = p[3 * far], cy = p[3 * far + 1], cz = p[3 * far + 2];     // the first centroid's coordinates: one read from memory
-    int par = 0;
+    int par = 0, last = far;
     for (int s = 0; s < npoint; ++s) {
-        if (tid == 0) out[(size_t)b * npoint + s] = far;             // centroids[:, i] = farthest (:324)
+        if (tid == 0) out[s] = far;                                  // centroids[:, i] = farthest (:324)
+        last = far;
         float best = -INFINITY, bx = 0.f, by = 0.f, bz = 0.f;
         int bi = 0x7fffffff;
 #pragma unroll
@@ -308,6 +342,34 @@ __global__ __launch_bounds__(1024) void fps_kernel(const float *__restrict__ xyz
         cx = part_c[par][ww][0]; cy = part_c[par][ww][1]; cz = part_c[par][ww][2];
         par ^= 1;
     }
+    return last;
+}
+
+__device__ __forceinline__ int fps_start(const int32_t *__restrict__ start, int b, int N)
+{
+    const int far = start ? start[b] : 0;
+    return far < 0 || far >= N ? 0 : far;
+}
+
+template <int PPT, bool USE_LDS>
+__global__ __launch_bounds__(1024) void fps_kernel(const float *__restrict__ xyz, int N, int npoint,
+                                                   const int32_t *__restrict__ start, int64_t *__restrict__ out)
+{
+    const int b = blockIdx.x;
+    fps_cloud<PPT>(xyz + (size_t)b * N * 3, N, npoint, fps_start(start, b, N), out + (size_t)b * npoint);
+}
+
+// Ragged batch: cloud b samples npoint[b] of its n[b] points (rows of N_max; the lanes of the points from n[b] on hold -inf and never
+// win a round); the entries of its row of npoint_max from npoint[b] on repeat the last index, so a gather over the row reads real points.
+template <int PPT>
+__global__ __launch_bounds__(1024) void fps_n_kernel(const float *__restrict__ xyz, int N_max, const int32_t *__restrict__ n,
+                                                     int npoint_max, const int32_t *__restrict__ npoint,
+                                                     const int32_t *__restrict__ start, int64_t *__restrict__ out)
+{
+    const int b = blockIdx.x, nb = ragged_count(n, b, 1, N_max), np = ragged_count(npoint, b, 0, npoint_max);
+    int64_t *o = out + (size_t)b * npoint_max;
+    const int last = fps_cloud<PPT>(xyz + (size_t)b * N_max * 3, nb, np, fps_start(start, b, nb), o);
+    for (int s = np + threadIdx.x; s < npoint_max; s += 1024) o[s] = last;
 }
 
 // Small clouds (N <= 512: the patches of the PointNet++ families, pointnet_sa_module.py:66-68): one WAVE per cloud, up to 8 points
@@ -377,21 +439,17 @@ static int launch_fps_wave(const float *xyz, int B, int N, int npoint, const int
 }
 
 // N > 16384: running min-distance lives in a global workspace (L2-resident), same selection rule.
-__global__ __launch_bounds__(1024) void fps_big_kernel(const float *__restrict__ xyz, int N, int npoint,
-                                                       const int32_t *__restrict__ start, int64_t *__restrict__ out,
-                                                       float *__restrict__ work)
+__device__ __forceinline__ int fps_big_cloud(const float *__restrict__ p, int N, int npoint, int far, int64_t *__restrict__ out,
+                                             float *__restrict__ md)
 {
     __shared__ float part_v[2][16];
     __shared__ int part_i[2][16];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const float *p = xyz + (size_t)b * N * 3;
-    float *md = work + (size_t)b * N;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     for (int i = tid; i < N; i += 1024) md[i] = 1e10f;
-    int far = start ? start[b] : 0;
-    if (far < 0 || far >= N) far = 0;
-    int par = 0;
+    int par = 0, last = far;
     for (int s = 0; s < npoint; ++s) {
-        if (tid == 0) out[(size_t)b * npoint + s] = far;
+        if (tid == 0) out[s] = far;
+        last = far;
         const float cx = p[3 * far], cy = p[3 * far + 1], cz = p[3 * far + 2];
         float best = -INFINITY;
         int bi = 0x7fffffff;
@@ -410,6 +468,26 @@ __global__ __launch_bounds__(1024) void fps_big_kernel(const float *__restrict__
         far = __builtin_amdgcn_readfirstlane(vi);
         par ^= 1;
     }
+    return last;
+}
+
+__global__ __launch_bounds__(1024) void fps_big_kernel(const float *__restrict__ xyz, int N, int npoint,
+                                                       const int32_t *__restrict__ start, int64_t *__restrict__ out,
+                                                       float *__restrict__ work)
+{
+    const int b = blockIdx.x;
+    fps_big_cloud(xyz + (size_t)b * N * 3, N, npoint, fps_start(start, b, N), out + (size_t)b * npoint, work + (size_t)b * N);
+}
+
+__global__ __launch_bounds__(1024) void fps_big_n_kernel(const float *__restrict__ xyz, int N_max, const int32_t *__restrict__ n,
+                                                         int npoint_max, const int32_t *__restrict__ npoint,
+                                                         const int32_t *__restrict__ start, int64_t *__restrict__ out,
+                                                         float *__restrict__ work)
+{
+    const int b = blockIdx.x, nb = ragged_count(n, b, 1, N_max), np = ragged_count(npoint, b, 0, npoint_max);
+    int64_t *o = out + (size_t)b * npoint_max;
+    const int last = fps_big_cloud(xyz + (size_t)b * N_max * 3, nb, np, fps_start(start, b, nb), o, work + (size_t)b * N_max);
+    for (int s = np + threadIdx.x; s < npoint_max; s += 1024) o[s] = last;
 }
 
 template <int PPT>
@@ -437,6 +515,36 @@ extern "C" int pccx_fps(const float *xyz, int B, int N, int npoint, const int32_
     if (N <= 16384) return launch_fps<16>(xyz, B, N, npoint, start_idx, idx_out, st);
     PCCX_CHECK_ARG(workspace, "pccx_fps: N=%d > 16384 needs a workspace of B*N floats", N);
     hipLaunchKernelGGL(fps_big_kernel, dim3(B), dim3(1024), 0, st, xyz, N, npoint, start_idx, idx_out, workspace);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+template <int PPT>
+static int launch_fps_n(const float *xyz, int B, int N_max, const int32_t *n, int npoint_max, const int32_t *npoint, const int32_t *start,
+                        int64_t *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(fps_n_kernel<PPT>, dim3(B), dim3(1024), 0, st, xyz, N_max, n, npoint_max, npoint, start, out);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+// The register kernel by N_max (every form of pccx_fps selects the same indices: same arithmetic per point, first maximum on ties; the
+// one-wave forms of the smallest clouds are not needed here), the global-memory one above 16384.
+extern "C" int pccx_fps_n(const float *xyz, int B, int N_max, const int32_t *n, int npoint_max, const int32_t *npoint,
+                          const int32_t *start_idx, int64_t *idx_out, float *workspace, void *stream)
+{
+    if (B == 0 || npoint_max == 0) return PCCX_OK;
+    PCCX_CHECK_ARG(xyz && n && npoint && idx_out, "pccx_fps_n: null pointer");
+    PCCX_CHECK_ARG(B >= 0 && N_max >= 1 && N_max <= 32768 && npoint_max >= 0, "pccx_fps_n: need 1 <= N_max <= 32768 (B=%d N_max=%d npoint_max=%d)",
+                   B, N_max, npoint_max);
+    hipStream_t st = (hipStream_t)stream;
+    if (N_max <= 1024) return launch_fps_n<1>(xyz, B, N_max, n, npoint_max, npoint, start_idx, idx_out, st);
+    if (N_max <= 2048) return launch_fps_n<2>(xyz, B, N_max, n, npoint_max, npoint, start_idx, idx_out, st);
+    if (N_max <= 4096) return launch_fps_n<4>(xyz, B, N_max, n, npoint_max, npoint, start_idx, idx_out, st);
+    if (N_max <= 8192) return launch_fps_n<8>(xyz, B, N_max, n, npoint_max, npoint, start_idx, idx_out, st);
+    if (N_max <= 16384) return launch_fps_n<16>(xyz, B, N_max, n, npoint_max, npoint, start_idx, idx_out, st);
+    PCCX_CHECK_ARG(workspace, "pccx_fps_n: N_max=%d > 16384 needs a workspace of B*N_max floats", N_max);
+    hipLaunchKernelGGL(fps_big_n_kernel, dim3(B), dim3(1024), 0, st, xyz, N_max, n, npoint_max, npoint, start_idx, idx_out, workspace);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }

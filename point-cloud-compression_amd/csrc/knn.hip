@@ -45,10 +45,10 @@ __device__ __forceinline__ int block_scan_find(int h, int remaining, int *s_wsum
     return 0;
 }
 
-__global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ q, int M, const float *__restrict__ ref,
-                                                  int N, int K, int Kp, float *__restrict__ dists,
-                                                  int64_t *__restrict__ idx, float *__restrict__ nn, float patch_scale,
-                                                  const int *__restrict__ rep)
+// one query (m of cloud b) by the workgroup: rp = the cloud's N keys
+__device__ __forceinline__ void knn_radix_query(const float *__restrict__ q, int M, const float *__restrict__ rp, int N, int K, int Kp,
+                                                float *__restrict__ dists, int64_t *__restrict__ idx, float *__restrict__ nn,
+                                                float patch_scale, int m, int b)
 {
     extern __shared__ unsigned char smem_raw[];
     unsigned long long *sel = (unsigned long long *)smem_raw;   // [Kp]
@@ -59,9 +59,6 @@ __global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ q, i
     int *s_cnt = s_found + 3;                                   // [1]
 
     const int tid = threadIdx.x;
-    const int m = blockIdx.x, b = blockIdx.y;
-    if (rep && rep[b * M + m] != b * M + m) return;             // a copy of an earlier query of this cloud: see knn_fast_kernel
-    const float *rp = ref + (size_t)b * N * 3;
     const float qx = q[((size_t)b * M + m) * 3], qy = q[((size_t)b * M + m) * 3 + 1], qz = q[((size_t)b * M + m) * 3 + 2];
 
     for (int i = tid; i < N; i += 256)
@@ -151,6 +148,29 @@ __global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ q, i
             nn[(ob + k) * 3] = x; nn[(ob + k) * 3 + 1] = y; nn[(ob + k) * 3 + 2] = z;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ q, int M, const float *__restrict__ ref,
+                                                  int N, int K, int Kp, float *__restrict__ dists,
+                                                  int64_t *__restrict__ idx, float *__restrict__ nn, float patch_scale,
+                                                  const int *__restrict__ rep)
+{
+    const int m = blockIdx.x, b = blockIdx.y;
+    if (rep && rep[b * M + m] != b * M + m) return;             // a copy of an earlier query of this cloud: see knn_fast_kernel
+    knn_radix_query(q, M, ref + (size_t)b * N * 3, N, K, Kp, dists, idx, nn, patch_scale, m, b);
+}
+
+// Ragged batch: cloud b holds n[b] keys in rows of N_max and scales its patches by scale[b]; the keys from n[b] on are never read.
+__global__ __launch_bounds__(256) void knn_n_kernel(const float *__restrict__ q, int M, const float *__restrict__ ref, int N_max,
+                                                    const int32_t *__restrict__ n, int K, int Kp, float *__restrict__ dists,
+                                                    int64_t *__restrict__ idx, float *__restrict__ nn, const float *__restrict__ scale,
+                                                    const int *__restrict__ rep)
+{
+    const int m = blockIdx.x, b = blockIdx.y;
+    if (rep && rep[b * M + m] != b * M + m) return;
+    int nb = n[b];
+    nb = nb < K ? K : (nb > N_max ? N_max : nb);                // K <= n[b] <= N_max is checked on the host; never index out of the row
+    knn_radix_query(q, M, ref + (size_t)b * N_max * 3, nb, K, Kp, dists, idx, nn, scale[b], m, b);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -244,14 +264,13 @@ __device__ __forceinline__ void knn_level(const unsigned (&key)[KNN_PPT], int *h
     cnt = s_found[2];
 }
 
-// one query (m of cloud b) by the workgroup; the shared arrays come from the kernel
-__device__ __forceinline__ void knn_fast_query(const float *__restrict__ q, int M, const float *__restrict__ ref, int N, int K,
+// one query (m of cloud b) by the workgroup: rp = the cloud's N keys; the shared arrays come from the kernel
+__device__ __forceinline__ void knn_fast_query(const float *__restrict__ q, int M, const float *__restrict__ rp, int N, int K,
                                                float *__restrict__ dists, int64_t *__restrict__ idx, float *__restrict__ nn, float patch_scale,
                                                int m, int b, int tid, int *hist, unsigned long long *selA, unsigned long long *selB,
                                                int *s_wsum, int *s_found, int *s_cnt)
 {
     const int lane = tid & 63, w = tid >> 6;
-    const float *rp = ref + (size_t)b * N * 3;
     const size_t qo = ((size_t)b * M + m) * 3;
     const float qx = q[qo], qy = q[qo + 1], qz = q[qo + 2];
     const size_t ob = ((size_t)b * M + m) * K;
@@ -383,7 +402,23 @@ __global__ __launch_bounds__(256, 4) void knn_fast_kernel(const float *__restric
     __shared__ int s_wsum[4], s_found[3], s_cnt[2];
     const int m = blockIdx.x, b = blockIdx.y;
     if (rep && rep[b * M + m] != b * M + m) return;                       // a copy of an earlier query of this cloud (patch_groups.hip): its rows stay unwritten
-    knn_fast_query(q, M, ref, N, K, dists, idx, nn, patch_scale, m, b, threadIdx.x, hist, selA, selB, s_wsum, s_found, s_cnt);
+    knn_fast_query(q, M, ref + (size_t)b * N * 3, N, K, dists, idx, nn, patch_scale, m, b, threadIdx.x, hist, selA, selB, s_wsum, s_found, s_cnt);
+}
+
+// Ragged batch: as knn_n_kernel
+__global__ __launch_bounds__(256, 4) void knn_fast_n_kernel(const float *__restrict__ q, int M, const float *__restrict__ ref, int N_max,
+                                                            const int32_t *__restrict__ n, int K, float *__restrict__ dists,
+                                                            int64_t *__restrict__ idx, float *__restrict__ nn,
+                                                            const float *__restrict__ scale, const int *__restrict__ rep)
+{
+    __shared__ int hist[KNN_BINS];
+    __shared__ unsigned long long selA[256], selB[KNN_CAPB];
+    __shared__ int s_wsum[4], s_found[3], s_cnt[2];
+    const int m = blockIdx.x, b = blockIdx.y;
+    if (rep && rep[b * M + m] != b * M + m) return;
+    int nb = n[b];
+    nb = nb < K ? K : (nb > N_max ? N_max : nb);
+    knn_fast_query(q, M, ref + (size_t)b * N_max * 3, nb, K, dists, idx, nn, scale[b], m, b, threadIdx.x, hist, selA, selB, s_wsum, s_found, s_cnt);
 }
 
 // the same over the queries uniq[0 .. *n_uniq) (patch_groups.hip; both on the device): the workgroups of a one-dimensional grid walk the list
@@ -402,7 +437,7 @@ __global__ __launch_bounds__(256, 4) void knn_fast_list_kernel(const float *__re
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         const int p = uniq[slot];
-        knn_fast_query(q, M, ref, N, K, dists, idx, nn, patch_scale, p % M, p / M, tid, hist, selA, selB, s_wsum, s_found, s_cnt);
+        knn_fast_query(q, M, ref + (size_t)(p / M) * N * 3, N, K, dists, idx, nn, patch_scale, p % M, p / M, tid, hist, selA, selB, s_wsum, s_found, s_cnt);
         __syncthreads();                                                  // the shared arrays serve the next query of the list
     }
 }
@@ -442,6 +477,30 @@ extern "C" int pccx_knn_list(const float *q, int B, int M, const float *ref, int
                              float *nn, float patch_scale, const int32_t *rep, void *stream)
 {
     return knn_launch(q, B, M, ref, N, K, dists, idx, nn, patch_scale, rep, nullptr, nullptr, stream);
+}
+
+// Ragged batches: pccx_knn_list with N -> n[b] (K <= n[b] <= N_max) and patch_scale -> scale[b], both on the device; the kernel is
+// chosen by N_max as above.
+extern "C" int pccx_knn_list_n(const float *q, int B, int M, const float *ref, int N_max, const int32_t *n, int K, float *dists,
+                               int64_t *idx, float *nn, const float *scale, const int32_t *rep, void *stream)
+{
+    if (B == 0 || M == 0) return PCCX_OK;
+    PCCX_CHECK_ARG(q && ref && n && scale && (dists || idx || nn), "pccx_knn_list_n: null pointer (q, ref, n, scale and at least one of dists / idx / nn are needed)");
+    PCCX_CHECK_ARG(B >= 0 && M >= 0 && N_max >= 1, "pccx_knn_list_n: bad shape B=%d M=%d N_max=%d", B, M, N_max);
+    PCCX_CHECK_ARG(K >= 1 && K <= N_max && K <= 1024, "pccx_knn_list_n: need 1 <= K <= min(N_max,1024), got K=%d N_max=%d", K, N_max);
+    PCCX_CHECK_ARG(N_max <= 32768, "pccx_knn_list_n: N_max=%d > 32768 unsupported", N_max);
+    PCCX_CHECK_ARG(B <= 65535, "pccx_knn_list_n: B=%d > 65535 unsupported", B);
+    if (N_max <= 256 * KNN_PPT && K <= 256)
+        hipLaunchKernelGGL(knn_fast_n_kernel, dim3(M, B), dim3(256), 0, (hipStream_t)stream, q, M, ref, N_max, n, K, dists, idx, nn, scale, rep);
+    else {
+        int Kp = 2;
+        while (Kp < K) Kp <<= 1;
+        const size_t shmem = (size_t)Kp * 8 + (size_t)N_max * 4 + (256 + 4 + 3 + 1) * 4;
+        PCCX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&knn_n_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipLaunchKernelGGL(knn_n_kernel, dim3(M, B), dim3(256), shmem, (hipStream_t)stream, q, M, ref, N_max, n, K, Kp, dists, idx, nn, scale, rep);
+    }
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
 }
 
 // uniq / n_uniq: null, or the representatives of pccx_patch_groups over the (B, M) queries and their count (both on the device): the

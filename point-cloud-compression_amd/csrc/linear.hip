@@ -603,6 +603,42 @@ extern "C" int pccx_reassemble(const float *patches, int64_t P, int k, float sca
     return PCCX_OK;
 }
 
+// Ragged batch: patches (B * S_max, k, 3), of which cloud b reassembles its first S[b] with its own scale[b] into its row of
+// S_max * k points; the rest of the row is not written.  The same operations in the same order.
+__global__ __launch_bounds__(256) void reassemble_n_kernel(const float *__restrict__ patches, int S_max, const int32_t *__restrict__ S, int k,
+                                                          const float *__restrict__ scale, const float *__restrict__ centres,
+                                                          const float *__restrict__ nrm_center, const float *__restrict__ nrm_longest,
+                                                          float one_minus_margin, float *__restrict__ out)
+{
+    const int b = blockIdx.y;
+    int Sb = S[b];
+    Sb = Sb < 0 ? 0 : (Sb > S_max ? S_max : Sb);
+    const long e0 = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e0 >= (long)Sb * k) return;
+    const long e = (long)b * S_max * k + e0, patch = e / k;
+    const float lg = nrm_longest[b], sc = scale[b];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float t = __fdiv_rn(patches[3 * e + a], sc);
+        t = __fadd_rn(t, centres[patch * 3 + a]);
+        t = __fsub_rn(t, 0.5f);
+        t = __fdiv_rn(__fmul_rn(t, lg), one_minus_margin);
+        out[3 * e + a] = __fadd_rn(t, nrm_center[3 * b + a]);
+    }
+}
+
+extern "C" int pccx_reassemble_n(const float *patches, int B, int S_max, const int32_t *S, int k, const float *scale, const float *centres,
+                                 const float *nrm_center, const float *nrm_longest, double margin, float *out, void *stream)
+{
+    if (B == 0) return PCCX_OK;
+    PCCX_CHECK_ARG(patches && S && scale && centres && nrm_center && nrm_longest && out, "pccx_reassemble_n: null pointer");
+    PCCX_CHECK_ARG(B > 0 && B <= 65535 && k >= 1 && S_max >= 1, "pccx_reassemble_n: bad arguments");
+    hipLaunchKernelGGL(reassemble_n_kernel, dim3((unsigned)(((long)S_max * k + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, patches, S_max, S,
+                       k, scale, centres, nrm_center, nrm_longest, (float)(1.0 - margin), out);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
 #define GM_THREADS 1024                    // 2 workgroups of 64 KB per CU = all 32 wave slots: the walk is a chain of dependent reads
 // the tail of cloud b's padded output rows (pccx_gather_max_rows): columns C .. C + 2 <- the centroids' coordinates, the rest <- 0
 __device__ __forceinline__ void gm_write_tail(float *__restrict__ out, const float *__restrict__ xyz, int b, int M, int C, int ldo, int tid)

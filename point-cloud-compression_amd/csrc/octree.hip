@@ -68,20 +68,20 @@ __device__ __forceinline__ int block_scan_flag(bool flag, int *s_w, int nwaves, 
     return incl + base;
 }
 
-__global__ __launch_bounds__(1024) void octree_encode_kernel(const float *__restrict__ centres, int S, int N, double min_bpp,
-                                                             uint8_t *__restrict__ bits_all, int cap,
-                                                             int32_t *__restrict__ nbits_out, int32_t *__restrict__ depth_out,
-                                                             uint8_t *__restrict__ bytes_all, int bytes_stride,
-                                                             int32_t *__restrict__ nbytes_out)
+// One cloud by its workgroup of T >= S threads (a power of two): centres = its S rows, bits / bytes = its rows of the two outputs,
+// b = its slot in the three count arrays.  The outputs do not depend on T: the keys past S sort last and are never counted.
+__device__ __forceinline__ void octree_encode_cloud(const float *__restrict__ centres, int S, int N, double min_bpp,
+                                                    uint8_t *__restrict__ bits, int32_t *__restrict__ nbits_out,
+                                                    int32_t *__restrict__ depth_out, uint8_t *__restrict__ bytes,
+                                                    int32_t *__restrict__ nbytes_out, int b)
 {
     extern __shared__ unsigned long long keys[];     // [T]
     __shared__ int s_w[17];
-    const int T = blockDim.x, tid = threadIdx.x, b = blockIdx.x, nwaves = T >> 6;
-    uint8_t *bits = bits_all + (size_t)b * cap;
+    const int T = blockDim.x, tid = threadIdx.x, nwaves = T >> 6;
 
     unsigned long long key = ~0ull;
     if (tid < S) {
-        const float *p = centres + ((size_t)b * S + tid) * 3;
+        const float *p = centres + (size_t)tid * 3;
         key = (spread3(quant16(p[0])) << 2) | (spread3(quant16(p[1])) << 1) | spread3(quant16(p[2]));
     }
     keys[tid] = key;
@@ -140,7 +140,6 @@ __global__ __launch_bounds__(1024) void octree_encode_kernel(const float *__rest
     __syncthreads();
     // pack (pn_kit.py:463-467): MSB-first; a final partial group is right-aligned in its byte.
     const int nby = (final_bits + 7) >> 3;
-    uint8_t *bytes = bytes_all + (size_t)b * bytes_stride;
     for (int j = tid; j < nby; j += T) {
         int lo = 8 * j, hi = lo + 8 < final_bits ? lo + 8 : final_bits;
         unsigned v = 0;
@@ -152,6 +151,34 @@ __global__ __launch_bounds__(1024) void octree_encode_kernel(const float *__rest
         depth_out[b] = final_depth;
         nbytes_out[b] = nby;
     }
+}
+
+__global__ __launch_bounds__(1024) void octree_encode_kernel(const float *__restrict__ centres, int S, int N, double min_bpp,
+                                                             uint8_t *__restrict__ bits_all, int cap,
+                                                             int32_t *__restrict__ nbits_out, int32_t *__restrict__ depth_out,
+                                                             uint8_t *__restrict__ bytes_all, int bytes_stride,
+                                                             int32_t *__restrict__ nbytes_out)
+{
+    const int b = blockIdx.x;
+    octree_encode_cloud(centres + (size_t)b * S * 3, S, N, min_bpp, bits_all + (size_t)b * cap, nbits_out, depth_out,
+                        bytes_all + (size_t)b * bytes_stride, nbytes_out, b);
+}
+
+// Ragged batch: cloud b codes its first S[b] centres (rows of S_max; the rest are never read) with its own point count N[b] in the
+// depth search.  cap / bytes_stride are those of S_max.
+__global__ __launch_bounds__(1024) void octree_encode_n_kernel(const float *__restrict__ centres, int S_max, const int32_t *__restrict__ S,
+                                                               const int32_t *__restrict__ N, double min_bpp,
+                                                               uint8_t *__restrict__ bits_all, int cap,
+                                                               int32_t *__restrict__ nbits_out, int32_t *__restrict__ depth_out,
+                                                               uint8_t *__restrict__ bytes_all, int bytes_stride,
+                                                               int32_t *__restrict__ nbytes_out)
+{
+    const int b = blockIdx.x;
+    int Sb = S[b], Nb = N[b];
+    Sb = Sb < 1 ? 1 : (Sb > S_max ? S_max : Sb);
+    Nb = Nb < 1 ? 1 : Nb;
+    octree_encode_cloud(centres + (size_t)b * S_max * 3, Sb, Nb, min_bpp, bits_all + (size_t)b * cap, nbits_out, depth_out,
+                        bytes_all + (size_t)b * bytes_stride, nbytes_out, b);
 }
 
 extern "C" int pccx_octree_bits_capacity(int S) { return 1 + 8 * S * OCT_MAX_DEPTH; }
@@ -166,6 +193,21 @@ extern "C" int pccx_octree_encode(const float *centres, int B, int S, int N, dou
     while (T < S) T <<= 1;
     const int cap = pccx_octree_bits_capacity(S);
     hipLaunchKernelGGL(octree_encode_kernel, dim3(B), dim3(T), (size_t)T * 8, (hipStream_t)stream, centres, S, N, min_bpp, bits,
+                       cap, nbits, depth, bytes, (cap + 7) / 8, nbytes);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+extern "C" int pccx_octree_encode_n(const float *centres, int B, int S_max, const int32_t *S, const int32_t *N, double min_bpp,
+                                    uint8_t *bits, int32_t *nbits, int32_t *depth, uint8_t *bytes, int32_t *nbytes, void *stream)
+{
+    if (B == 0) return PCCX_OK;
+    PCCX_CHECK_ARG(centres && S && N && bits && nbits && depth && bytes && nbytes, "pccx_octree_encode_n: null pointer");
+    PCCX_CHECK_ARG(B >= 0 && S_max >= 1 && S_max <= 1024, "pccx_octree_encode_n: need 1 <= S_max <= 1024 (S_max=%d)", S_max);
+    int T = 64;
+    while (T < S_max) T <<= 1;
+    const int cap = pccx_octree_bits_capacity(S_max);
+    hipLaunchKernelGGL(octree_encode_n_kernel, dim3(B), dim3(T), (size_t)T * 8, (hipStream_t)stream, centres, S_max, S, N, min_bpp, bits,
                        cap, nbits, depth, bytes, (cap + 7) / 8, nbytes);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;

@@ -69,13 +69,17 @@ __device__ __forceinline__ void rc_index_header(uint32_t *index, int nsym, int s
 
 // One lane per cloud.  REC: also write the cloud's sidecar of idx_stride bytes at index + b * idx_stride (the header and the entry at
 // every seg_sym boundary); the stream does not depend on it.
+// nsym_of (ragged batches; null otherwise): the rows of cdf_int / latent_q are nsym symbols apart and cloud b codes its first nsym_of[b].
 template <bool REC>
 __device__ __forceinline__ void rc_encode_lane(const int32_t *__restrict__ cdf_int, const float *__restrict__ latent_q, int B, int nsym,
                                                int Lp, int sym_offset, uint8_t *__restrict__ out, int cap, int32_t *__restrict__ nbytes,
-                                               int seg_sym, uint8_t *__restrict__ index, int idx_stride)
+                                               int seg_sym, uint8_t *__restrict__ index, int idx_stride,
+                                               const int32_t *__restrict__ nsym_of = nullptr)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
+    const int row = nsym;
+    if (nsym_of) nsym = rc_row_bytes(nsym_of[b], row);
     uint32_t *entry = nullptr;
     if (REC) {
         entry = (uint32_t *)(index + (size_t)b * idx_stride);
@@ -86,8 +90,8 @@ __device__ __forceinline__ void rc_encode_lane(const int32_t *__restrict__ cdf_i
     unsigned low = 0u, high = 0xFFFFFFFFu;
     unsigned long long pending = 0;
     const int max_symbol = Lp - 2;
-    const int32_t *c = cdf_int + (size_t)b * nsym * Lp;
-    const float *q = latent_q + (size_t)b * nsym;
+    const int32_t *c = cdf_int + (size_t)b * row * Lp;
+    const float *q = latent_q + (size_t)b * row;
     // Without REC one pass over all symbols; with it one pass per segment (seg_sym >= 1: P passes), the entry stored in front of
     // each, so that the symbol loop itself carries no test for a boundary.
     int i = 0, stop = REC ? 0 : nsym;
@@ -143,13 +147,20 @@ __global__ void range_encode_indexed_kernel(const int32_t *__restrict__ cdf_int,
 
 // One lane per cloud.  REC: write the cloud's sidecar as rc_encode_lane does (the decoder passes through the encoder's states), and
 // latent_q may then be null.
+// nsym_of: as rc_encode_lane; the latents of cloud b from nsym_of[b] on are written as zeros.
 template <bool REC>
 __device__ __forceinline__ void rc_decode_lane(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in, int stride,
                                                const int32_t *__restrict__ nbytes, int B, int nsym, int Lp, int sym_offset,
-                                               float *__restrict__ latent_q, int seg_sym, uint8_t *__restrict__ index, int idx_stride)
+                                               float *__restrict__ latent_q, int seg_sym, uint8_t *__restrict__ index, int idx_stride,
+                                               const int32_t *__restrict__ nsym_of = nullptr)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
+    const int row = nsym;
+    if (nsym_of) {
+        nsym = rc_row_bytes(nsym_of[b], row);
+        for (int i = nsym; i < row; ++i) latent_q[(size_t)b * row + i] = 0.f;
+    }
     uint32_t *entry = nullptr;
     int next = 0;
     unsigned long long shifted = 0;                           // REC: bits taken beyond the first 32; an underflow run is pending
@@ -174,7 +185,7 @@ __device__ __forceinline__ void rc_decode_lane(const int32_t *__restrict__ cdf_i
     };
     for (int i = 0; i < 32; ++i) get();
     const int max_symbol = Lp - 2;
-    const int32_t *c = cdf_int + (size_t)b * nsym * Lp;
+    const int32_t *c = cdf_int + (size_t)b * row * Lp;
     for (int i = 0; i < nsym; ++i, c += Lp) {
         if (REC && i == next) {
             rc_record(entry, low, high, shifted, under);
@@ -190,7 +201,7 @@ __device__ __forceinline__ void rc_decode_lane(const int32_t *__restrict__ cdf_i
             if (((unsigned)c[mid] & 0xFFFFu) <= count) left = mid; else right = mid;
         }
         const int s = left;
-        if (!REC || latent_q) latent_q[(size_t)b * nsym + i] = (float)(s - sym_offset);            // decode - L//2 (decompress.py:93)
+        if (!REC || latent_q) latent_q[(size_t)b * row + i] = (float)(s - sym_offset);            // decode - L//2 (decompress.py:93)
         const unsigned c_low = (unsigned)c[s] & 0xFFFFu;
         const unsigned c_high = s == max_symbol ? 0x10000u : ((unsigned)c[s + 1] & 0xFFFFu);
         high = (unsigned)((low - 1u) + (unsigned)((span * c_high) >> 16));
@@ -223,6 +234,20 @@ __global__ void range_index_build_kernel(const int32_t *__restrict__ cdf_int, co
                                          float *__restrict__ latent_q, int seg_sym, uint8_t *__restrict__ index, int idx_stride)
 {
     rc_decode_lane<true>(cdf_int, in, stride, nbytes, B, nsym, Lp, sym_offset, latent_q, seg_sym, index, idx_stride);
+}
+
+__global__ void range_encode_n_kernel(const int32_t *__restrict__ cdf_int, const float *__restrict__ latent_q, int B, int row,
+                                      const int32_t *__restrict__ nsym_of, int Lp, int sym_offset, uint8_t *__restrict__ out, int cap,
+                                      int32_t *__restrict__ nbytes)
+{
+    rc_encode_lane<false>(cdf_int, latent_q, B, row, Lp, sym_offset, out, cap, nbytes, 0, nullptr, 0, nsym_of);
+}
+
+__global__ void range_decode_n_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in, int stride,
+                                      const int32_t *__restrict__ nbytes, int B, int row, const int32_t *__restrict__ nsym_of, int Lp,
+                                      int sym_offset, float *__restrict__ latent_q)
+{
+    rc_decode_lane<false>(cdf_int, in, stride, nbytes, B, row, Lp, sym_offset, latent_q, 0, nullptr, 0, nsym_of);
 }
 
 #define RC_MAX_LDS_BYTES (60 * 1024)
@@ -366,6 +391,17 @@ __global__ __launch_bounds__(64) void range_encode_wave_kernel(const int32_t *__
                    nbytes + b);
 }
 
+// Ragged batch, one wave per cloud: rows of `row` symbols, of which cloud b codes its first nsym_of[b] (LDS sized for the row).
+__global__ __launch_bounds__(64) void range_encode_wave_n_kernel(const int32_t *__restrict__ cdf_int, const float *__restrict__ latent_q,
+                                                                 int row, const int32_t *__restrict__ nsym_of, int Lp, int sym_offset,
+                                                                 uint8_t *__restrict__ out, int cap, int32_t *__restrict__ nbytes)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
+    const int b = blockIdx.x;
+    rc_encode_wave(rc_smem, cdf_int + (size_t)b * row * Lp, latent_q + (size_t)b * row, rc_row_bytes(nsym_of[b], row), Lp, sym_offset,
+                   out + (size_t)b * cap, cap, nbytes + b);
+}
+
 // One stream, one wave: c = the stream's tables [nsym][Lp], in = its first byte, nb = its length already clamped to [0, stride]
 // (bytes from nb on are not read and count as zero), q = its nsym outputs.  The pointers and counts must be wave-uniform.  LDS:
 // rc_decode_lds(nsym, Lp - 1, stride) bytes at smem.
@@ -485,6 +521,20 @@ __global__ __launch_bounds__(64) void range_decode_wave_kernel(const int32_t *__
                    latent_q + (size_t)b * nsym);
 }
 
+// Ragged batch: as range_encode_wave_n_kernel; the latents from nsym_of[b] on are written as zeros.
+__global__ __launch_bounds__(64) void range_decode_wave_n_kernel(const int32_t *__restrict__ cdf_int, const uint8_t *__restrict__ in,
+                                                                 int stride, const int32_t *__restrict__ nbytes, int row,
+                                                                 const int32_t *__restrict__ nsym_of, int Lp, int sym_offset,
+                                                                 float *__restrict__ latent_q)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char rc_smem[];
+    const int b = blockIdx.x;
+    const int nb = rc_row_bytes(nbytes[b], stride), ns = rc_row_bytes(nsym_of[b], row);
+    float *q = latent_q + (size_t)b * row;
+    rc_decode_wave(rc_smem, cdf_int + (size_t)b * row * Lp, in + (size_t)b * stride, stride, nb, ns, Lp, sym_offset, q);
+    for (int i = ns + threadIdx.x; i < row; i += 64) q[i] = 0.f;
+}
+
 // LDS images of the two wave kernels: (c_low, c_high) per symbol + the output words; the 16-bit tables + the stream words +
 // one byte per decoded symbol.
 static size_t rc_encode_lds(int nsym, int cap) { return (size_t)nsym * 8 + (size_t)((cap + 3) / 4) * 4; }
@@ -536,6 +586,40 @@ extern "C" int pccx_range_decode(const int32_t *cdf_int, const uint8_t *in, int 
     }
     hipLaunchKernelGGL(range_decode_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, cdf_int, in, stride, nbytes,
                        B, nsym, L + 1, L / 2, latent_q);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+// Ragged batches: nsym = the row stride of cdf_int / latent_q in symbols, nsym_of[b] <= nsym the symbols cloud b codes from a fresh
+// state.  The form is chosen by the row as pccx_range_coder_form does; the bytes are pccx_range_encode's on the same table and symbols.
+extern "C" int pccx_range_encode_n(const int32_t *cdf_int, const float *latent_q, int B, int nsym, const int32_t *nsym_of, int L,
+                                   uint8_t *out, int cap, int32_t *nbytes, void *stream)
+{
+    if (B == 0) return PCCX_OK;
+    PCCX_CHECK_ARG(cdf_int && latent_q && nsym_of && out && nbytes, "pccx_range_encode_n: null pointer");
+    PCCX_CHECK_ARG(B >= 0 && nsym >= 0 && L >= 1 && cap >= 8, "pccx_range_encode_n: bad shape");
+    if (pccx_range_coder_form(0, nsym, L, cap) == 0)
+        hipLaunchKernelGGL(range_encode_wave_n_kernel, dim3(B), dim3(64), rc_encode_lds(nsym, cap), (hipStream_t)stream, cdf_int, latent_q,
+                           nsym, nsym_of, L + 1, L / 2, out, cap, nbytes);
+    else
+        hipLaunchKernelGGL(range_encode_n_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, cdf_int, latent_q, B, nsym,
+                           nsym_of, L + 1, L / 2, out, cap, nbytes);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+extern "C" int pccx_range_decode_n(const int32_t *cdf_int, const uint8_t *in, int stride, const int32_t *nbytes, int B, int nsym,
+                                   const int32_t *nsym_of, int L, float *latent_q, void *stream)
+{
+    if (B == 0) return PCCX_OK;
+    PCCX_CHECK_ARG(cdf_int && in && nbytes && nsym_of && latent_q, "pccx_range_decode_n: null pointer");
+    PCCX_CHECK_ARG(B >= 0 && nsym >= 0 && L >= 1 && stride >= 1, "pccx_range_decode_n: bad shape");
+    if (pccx_range_coder_form(1, nsym, L, stride) == 0)
+        hipLaunchKernelGGL(range_decode_wave_n_kernel, dim3(B), dim3(64), rc_decode_lds(nsym, L, stride), (hipStream_t)stream, cdf_int, in,
+                           stride, nbytes, nsym, nsym_of, L + 1, L / 2, latent_q);
+    else
+        hipLaunchKernelGGL(range_decode_n_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, cdf_int, in, stride, nbytes, B,
+                           nsym, nsym_of, L + 1, L / 2, latent_q);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }

@@ -9,6 +9,7 @@ Stream formats are the reference's: ``.s.bin`` = packed octr
 right-aligned), ``.p.bin`` = range-coder bytes of the S*d latent symbols, ``.c.bin`` = 4 x fp32
 [cx, cy, cz, longest].
 """
+import collections
 import dataclasses
 import functools
 import os
@@ -37,7 +38,7 @@ class Compressed:
     p_bytes: torch.Tensor     # (B, cap) u8     range-coded latents
     p_nbytes: torch.Tensor    # (B) i32
     c: torch.Tensor           # (B, 4) f32      centre xyz + longest side
-    n_points: int
+    n_points: int             # points per cloud; a (B,) int64 device tensor for a ragged batch (Codec.compress_ragged)
     extras: dict = None       # intermediates for tests / diagnostics
     packed: torch.Tensor = None   # the u8 buffer the five fields above are views of (packed_layout), when built by Codec
     p_index: torch.Tensor = None  # (B, 16 + 12*P) u8  entry-point index of p_bytes (<name>.p.idx), or None: no index
@@ -208,6 +209,40 @@ def stream_sizes(directory, names, threads=0):
 KNN_BRUTE_MAX_N = 32768        # pccx_knn / pccx_knn_list / pccx_knn_uniq keep a cloud's keys in LDS (csrc/knn.hip)
 OCTREE_MAX_S = 1024            # centres per cloud pccx_octree_encode, pccx_patch_groups and the narrow full decode take
 OCTREE_WIDE_MAX_S = 8192       # ... and their wide forms (pccx_octree_encode_wide, pccx_octree_decode above 1024, pccx_patch_groups_wide)
+
+
+RaggedPlan = collections.namedtuple("RaggedPlan", ["S", "S_pad", "scale_compress", "scale_decompress", "s_stride", "p_cap"])
+
+
+def ragged_plan(n_points, K=256, ALPHA=2, N0=1024, d=16):
+    """The shape arithmetic of a ragged batch (host only): per cloud S_b = n_b*ALPHA // K patches, the patch scale of compress
+    float((n_b / N0) ** (1/3)) and of decompress float((S_b*k / N0) ** (1/3)) with k = K // ALPHA -- each the very expression
+    Codec.compress / Codec.decompress evaluate for a dense batch of that size -- and for the batch S_pad = 16*ceil(max S_b / 16), the
+    row of the octree streams in bytes and the capacity of the range-coded rows, both those of S_pad."""
+    n = [int(v) for v in n_points]
+    S = [v * ALPHA // K for v in n]
+    S_pad = 16 * -(-max(S + [1]) // 16)
+    k = K // ALPHA
+    return RaggedPlan(S, S_pad, [float((v / N0) ** (1 / 3)) for v in n], [float((s * k / N0) ** (1 / 3)) for s in S],
+                      (1 + 8 * S_pad * 16 + 7) // 8, models.range_cap(S_pad * d))
+
+
+def pad_clouds(clouds, device=None):
+    """A list of (n_b, 3) arrays or tensors -> (pc (B, N_max, 3) f32, n_points list): every cloud in the first rows of its slab, the
+    rows behind it NaN -- no kernel of the ragged path lets them reach a result, and a NaN would show it.  device: where pc goes
+    (default: the first cloud's device for tensors, the host for arrays)."""
+    if not len(clouds):
+        raise ValueError("pad_clouds: at least one cloud is expected")
+    ts = [c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32)) for c in clouds]
+    for b, t in enumerate(ts):
+        if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+            raise ValueError(f"pad_clouds: cloud {b} must be (n, 3) with n >= 1, got {tuple(t.shape)}")
+    n = [int(t.shape[0]) for t in ts]
+    device = device if device is not None else ts[0].device
+    pc = torch.full((len(ts), max(n), 3), float("nan"), dtype=torch.float32, device=device)
+    for b, t in enumerate(ts):
+        pc[b, :n[b]] = t.to(device=device, dtype=torch.float32)
+    return pc, n
 
 
 def _check_patches(ae, name, G, unit):
@@ -393,6 +428,157 @@ class Codec:
             return self.ae.decode(q.view(B * S, d), rec.view(B * S, 3), comp.c[:, :3].contiguous(),
                                   comp.c[:, 3].contiguous(), S=S, scale=scale, margin=self.margin,
                                   matmul=self.decoder_matmul, group=self.group_duplicates, short_list=self._distinct())
+
+    _RAGGED_WAY_OUT = " Such clouds go through compress / decompress, one size per call."
+
+    def ragged_config_refusal(self):
+        """Why this Codec's configuration cannot run ragged batches at all, whatever the clouds: a message naming the setting and the
+        way out, or None.  Host only."""
+        out = self._RAGGED_WAY_OUT
+        if self.octree_mode != "full":
+            return f"ragged batches need octree_mode='full' (octree_mode='reference' is S = 64 by definition), got {self.octree_mode!r}." + out
+        if self.p_split is not None or self.p_index is not None or self.centres != "fps":
+            return ("ragged batches take the single .p.bin stream and whole-cloud FPS centres: p_split, p_index and centres='blocks' "
+                    "are not covered." + out)
+        if self.knn_search == "grid":
+            return "ragged batches use the all-pairs patch search: knn_search='grid' is not covered." + out
+        if not self.group_duplicates:
+            return "ragged batches need group_duplicates=True: the padded centres of a cloud are skipped as its duplicates." + out
+        if not self.prob.fused_ok(16):
+            return (f"ragged batches need the fused probability kernel (d <= 16, L <= 15, d*L <= 128), got d={self.prob.d}, "
+                    f"L={self.prob.L}." + out)
+        return None
+
+    def ragged_patch_range(self):
+        """(lo, hi): the patch counts S_b a cloud of a ragged batch may have, the ONE rule both sides route by.  lo = ALPHA is n_b = K;
+        hi is OCTREE_MAX_S or, where that comes first, the S of KNN_BRUTE_MAX_N points.  A decoder sees S_b only, so where clouds above
+        and below KNN_BRUTE_MAX_N points share that last S, and it is no multiple of 16 (the tables of the two paths differ there),
+        it is left to the one-cloud path on both sides.  No K that is a power of two is affected."""
+        s_lim = KNN_BRUTE_MAX_N * self.ALPHA // self.K
+        hi = min(OCTREE_MAX_S, s_lim)
+        if hi == s_lim and hi % 16 and ((hi + 1) * self.K - 1) // self.ALPHA > KNN_BRUTE_MAX_N:
+            hi -= 1
+        return self.ALPHA, hi
+
+    def _ragged_patch_refusal(self, S):
+        lo, hi = self.ragged_patch_range()
+        for b, v in enumerate(S):
+            if not lo <= int(v) <= hi:
+                return (f"cloud {b}: S={int(v)} patches; a ragged batch takes {lo} <= S_b <= {hi} at K={self.K}, ALPHA={self.ALPHA} "
+                        f"(n_b >= K points; OCTREE_MAX_S = {OCTREE_MAX_S} patches; KNN_BRUTE_MAX_N = {KNN_BRUTE_MAX_N} points)." + self._RAGGED_WAY_OUT)
+        return None
+
+    def ragged_refusal(self, n_points, N_max=None):
+        """Why compress_ragged cannot take a batch of these point counts (N_max: the rows of its slab, default the largest count): a
+        message naming the limit and the way out, or None.  Host only; compress_ragged raises it as ValueError before anything is
+        launched, and compress.py --ragged sends a refused file the existing way."""
+        why = self.ragged_config_refusal()
+        if why:
+            return why
+        n = [int(v) for v in n_points]
+        N_max = max(n) if N_max is None else int(N_max)
+        if N_max > KNN_BRUTE_MAX_N:
+            return f"a ragged batch holds clouds of at most KNN_BRUTE_MAX_N = {KNN_BRUTE_MAX_N} points, got N_max={N_max}." + self._RAGGED_WAY_OUT
+        for b, v in enumerate(n):
+            if v < self.K or v > N_max:
+                return f"cloud {b}: {v} points; a ragged batch needs K = {self.K} <= n_b <= N_max = {N_max}." + self._RAGGED_WAY_OUT
+        return self._ragged_patch_refusal([v * self.ALPHA // self.K for v in n])
+
+    def ragged_decode_refusal(self, S):
+        """Why decompress_ragged cannot take clouds of these patch counts: the same rule seen from the decoder, which knows S_b alone
+        (ragged_patch_range) -- a file compress.py --ragged sent the existing way is sent the existing way by decompress.py --ragged
+        too, and a file it wrote through compress_ragged comes back through decompress_ragged.  A message or None; host only."""
+        return self.ragged_config_refusal() or self._ragged_patch_refusal(S)
+
+    def compress_ragged(self, pc, n_points, start_idx, keep_extras=False):
+        """compress for clouds of different sizes in ONE launch sequence (opt-in; octree_mode "full").  pc (B,N_max,3) f32 on the
+        GPU, cloud b in its first n_points[b] rows (a host sequence, K <= n_b <= N_max <= 32768); the rows behind them are padding
+        that reaches no result (pad_clouds fills them with NaN).  start_idx (B,) as compress.  -> Compressed with n_points a (B,)
+        tensor, its rows sized for S_pad = 16*ceil(max S_b / 16) patches (ragged_plan).
+
+        A cloud's three streams do not depend on the batch it travels in, on N_max, S_pad or its position.  Where S_b is a multiple
+        of 16 they are byte for byte those of compress(cloud[None], [start]).  For every other S_b, .s.bin and .c.bin (and the FPS
+        indices, patches and latent_q) still are, but the integer CDF is DEFINED as rows [0, S_b) of the fused probability kernel's
+        table on the decoded centres padded to a multiple of 16 with repeats of the last one, where compress evaluates the generic
+        layers at such S (ConditionalProbabilityModel.fused_ok) and may differ in the last unit of a table entry: as with p_split,
+        BOTH sides must then use the ragged path (decompress_ragged) for such a cloud.  DESIGN.md section 4.5 has the measured count.
+        Refused with ValueError before any launch: what ragged_refusal names.  extras: (B, ..._max) arrays plus S and n_points."""
+        B, N_max, _ = pc.shape
+        n = [int(v) for v in n_points]
+        if len(n) != B:
+            raise ValueError(f"compress_ragged: {len(n)} point counts for {B} clouds")
+        why = self.ragged_refusal(n, N_max)
+        if why:
+            raise ValueError("compress_ragged: " + why)
+        d, L = self.ae.d, self.ae.L
+        plan = ragged_plan(n, self.K, self.ALPHA, self.N0, d)
+        S_pad, dev = plan.S_pad, pc.device
+        n_dev, S_dev = ops.counts(n, B, dev, "n_points"), ops.counts(plan.S, B, dev, "S")
+        scale = torch.tensor(plan.scale_compress, dtype=torch.float32).to(dev)
+        with stage("normalize"):
+            pcn, center, longest = ops.normalize_n(pc, n_dev, self.margin)
+        with stage("fps"):
+            fps_idx = ops.farthest_point_sample_n(pcn, n_dev, S_pad, S_dev, start_idx)
+        with stage("gather"):
+            sampled = ops.index_points(pcn, fps_idx)
+        comp = Compressed.alloc(B, plan.s_stride, plan.p_cap, n_dev.to(torch.int64), dev)
+        with stage("octree_encode"):
+            oc = ops.octree_encode_n(sampled, S_dev, n_dev, ops.OCTREE_BPP_DICT[self.K], out_bytes=comp.s_bytes, out_nbytes=comp.s_nbytes)
+        with stage("octree_decode"):
+            rec, _ = ops.octree_decode(oc["bytes"], oc["nbytes"], "full", S_pad)      # the centres past S_b repeat the last one ...
+        groups = ops.patch_groups(rec)                                                # ... and so are its duplicates: never transformed
+        with stage("knn_patches"):
+            nn = ops.knn_points_n(rec, pcn, n_dev, self.K, scale, rep=groups.rep)
+        patches = nn.knn.view(B * S_pad, self.K, 3)
+        ops.replicate_rows(groups, patches)               # only the f16x2 kernels walk the list; the others read every patch's rows
+        raw, latent, q = self.ae.encode(patches, sa_matmul=self.sa_matmul, pn_matmul=self.pn_matmul, groups=groups)
+        with stage("prob"):
+            cdf_int = self.prob.run(rec, ("cdf_int",), **self._prob_kw)["cdf_int"]
+        with stage("range_encode"):
+            models.range_encode_n(cdf_int, q.view(B, S_pad * d), [s * d for s in plan.S], L, out=comp.p_bytes, nb=comp.p_nbytes)
+        comp.c[:, :3].copy_(center)
+        comp.c[:, 3].copy_(longest)
+        if keep_extras:
+            comp.extras = dict(pcn=pcn, fps_idx=fps_idx, sampled=sampled, octree=oc, rec_sampled=rec, patches=patches, latent_raw=raw,
+                               latent=latent, latent_q=q, cdf_int=cdf_int, S=list(plan.S), n_points=n)
+        return comp
+
+    def decompress_ragged(self, comp, S):
+        """The inverse of compress_ragged -> a list of B tensors (S_b*k, 3) f32, views of one allocation.  S: a host sequence, the
+        patches of every cloud (n_b*ALPHA // K); each must equal the number of centres its .s.bin holds, else PccxError names the
+        cloud (one read-back of the B counts, the only synchronisation).  The probability tables are those compress_ragged coded
+        with (see there), so a cloud whose S_b is no multiple of 16 must have been written by compress_ragged."""
+        B = comp.s_bytes.shape[0]
+        S = [int(v) for v in S]
+        if len(S) != B:
+            raise ValueError(f"decompress_ragged: {len(S)} patch counts for {B} clouds")
+        from ._lib import PccxError
+        bad = [b for b, v in enumerate(S) if v < 1]
+        if bad:
+            raise PccxError(f"decompress_ragged: clouds {bad} have S={[S[b] for b in bad]}: every cloud needs at least one patch")
+        why = self.ragged_decode_refusal(S)
+        if why:
+            raise ValueError("decompress_ragged: " + why)
+        d, L, dev = self.ae.d, self.ae.L, comp.s_bytes.device
+        S_pad = 16 * -(-max(S) // 16)
+        with stage("octree_decode"):
+            rec, cnt = ops.octree_decode(comp.s_bytes, comp.s_nbytes, "full", S_pad)
+            cnt = cnt.cpu().tolist()
+        bad = [b for b in range(B) if cnt[b] != S[b]]
+        if bad:
+            raise PccxError("decompress_ragged: " + "; ".join(f"cloud {b}: S={S[b]} given but its .s.bin holds {cnt[b]} centres" for b in bad))
+        with stage("prob"):
+            cdf_int = self.prob.run(rec, ("cdf_int",), **self._prob_kw)["cdf_int"]
+        with stage("range_decode"):
+            q = models.range_decode_n(cdf_int, comp.p_bytes, comp.p_nbytes, [s * d for s in S], L)
+        scale = torch.tensor([float((s * self.k / self.N0) ** (1 / 3)) for s in S], dtype=torch.float32).to(dev)
+        with stage("ae_decode"):
+            # the padded patches of a cloud share their key (last centre, zero latents): one of them is decoded, none is reassembled
+            groups = ops.patch_groups(rec, q.view(B, S_pad, d)) if self.decoder_matmul == "f16x2" and self.ae.fused_d else None
+            raw = self.ae.decode(q.view(B * S_pad, d), matmul=self.decoder_matmul, groups=groups)
+        with stage("reassemble"):
+            out = ops.reassemble_n(raw, S, self.k, scale, rec, comp.c[:, :3].contiguous(), comp.c[:, 3].contiguous(), self.margin)
+        return [out[b, :S[b] * self.k] for b in range(B)]
 
     def build_index(self, comp, S=64):
         """The entry-point index of a Compressed that has none (files written without p_index, the reference's own included): the

@@ -451,7 +451,8 @@ class AE(nn.Module):
             outs.append(self.inv_mlp(mlp_in).transpose(2, 1).contiguous())                         # :101-102
         return torch.cat(outs) if outs else torch.empty(0, self.k, 3, device=q.device)
 
-    def decode(self, latent_q, centres=None, center=None, longest=None, S=None, scale=None, margin=0.01, matmul=None, group=False, short_list=False):
+    def decode(self, latent_q, centres=None, center=None, longest=None, S=None, scale=None, margin=0.01, matmul=None, group=False, short_list=False,
+               groups=None):
         """latent_q (BS,d) -> decoded patches (BS,k,3) (AE.py:48-53).  With centres/center/longest/S/scale
         it returns instead the reassembled, denormalised cloud (B,S*k,3) of decompress.py:104-116.
         matmul="bf16x3" / "f16x2" evaluate the matrix products as fp32 products of three bf16 / two exactly scaled fp16 pieces
@@ -459,7 +460,9 @@ class AE(nn.Module):
         group=True (reassembling form, "f16x2"): patches of a cloud with the same (centre row, latent_q row) decode to the same 3 k floats, so
         the decoder runs once per distinct pair (ops.patch_groups) and the copies are filled from it; the other modes decode every patch.
         short_list=True (with group): the caller expects far fewer distinct pairs than patches (octree_mode "reference"), and the head runs in
-        its one-tile-per-workgroup form; same result."""
+        its one-tile-per-workgroup form; same result.
+        groups (raw-patches form, "f16x2"; the ragged path): ops.patch_groups the caller made over its (centre row, latent_q row) keys --
+        the listed patches are decoded and the copies filled from them; the other modes decode every patch."""
         matmul = matmul or _pccx_default_matmul()
         q = _f32c(latent_q, "AE.decode")
         P = q.shape[0]
@@ -485,8 +488,12 @@ class AE(nn.Module):
         _, dec = self._blobs(q.device)
         extra = (self._derived(blob, q.device).data_ptr(),) if blob else ()
         ws = workspace(ws_tag, getattr(_lib.load(), ws_floats)(P), q.device)
-        groups, lists = None, ()
-        if matmul == "f16x2":
+        groups, lists = (None if reassemble else groups), ()
+        if groups is not None and groups.rep.numel() != P:
+            raise _lib.PccxError(f"AE.decode: groups of {groups.rep.numel()} patches for {P} patches")
+        if matmul != "f16x2":
+            groups = None
+        else:
             if group and reassemble:
                 from .ops import patch_groups, replicate_rows
                 groups = patch_groups(centres.view(B, S, 3), q.view(B, S, self.d))
@@ -497,6 +504,7 @@ class AE(nn.Module):
             fn = "pccx_ae_decode_h2_short_list"
         _lib.call(fn, q.data_ptr(), P, self.d, self.k, dec.data_ptr(), *extra, ws.data_ptr(), *dest, *lists, _stream())
         if groups is not None:
+            from .ops import replicate_rows
             replicate_rows(groups, result)
         return result
 
@@ -704,6 +712,33 @@ def range_decode(cdf_int, bytes_, nbytes, L):
     B, nsym, bytes_, nbytes, q, _ = _decoder_args(cdf_int, bytes_, nbytes, L)
     _lib.call("pccx_range_decode", cdf_int.contiguous().data_ptr(), bytes_.data_ptr(), bytes_.shape[1], nbytes.data_ptr(), B, nsym, int(L),
               q.data_ptr(), _stream())
+    return q
+
+
+def _nsym_of(nsym_of, B, device):
+    t = nsym_of if isinstance(nsym_of, torch.Tensor) else torch.as_tensor(list(nsym_of), dtype=torch.int32)
+    t = t.to(device=device, dtype=torch.int32).contiguous()
+    if tuple(t.shape) != (B,):
+        raise _lib.PccxError(f"nsym_of: one int per cloud is expected, got {tuple(t.shape)} for {B} clouds")
+    return t
+
+
+def range_encode_n(cdf_int, latent_q, nsym_of, L, cap=None, out=None, nb=None):
+    """range_encode for a ragged batch (pccx_range_encode_n): the rows of cdf_int (B,nsym,L+1) / latent_q (B,nsym) are nsym symbols
+    apart and cloud b codes its first nsym_of[b] (a (B,) sequence or int32 tensor).  The bytes of cloud b are range_encode's on its
+    own rows alone."""
+    B, nsym, q, out, nb = _encoder_args("range_encode_n", cdf_int, latent_q, L, out, nb, lambda n: cap or range_cap(n))
+    _lib.call("pccx_range_encode_n", cdf_int.contiguous().data_ptr(), q.data_ptr(), B, nsym, _nsym_of(nsym_of, B, q.device).data_ptr(), int(L),
+              out.data_ptr(), out.shape[1], nb.data_ptr(), _stream())
+    return out, nb
+
+
+def range_decode_n(cdf_int, bytes_, nbytes, nsym_of, L):
+    """range_decode for a ragged batch (pccx_range_decode_n) -> latent_q (B,nsym) f32: cloud b's first nsym_of[b] symbols, zeros
+    behind them.  Foreign bytes are taken as range_decode takes them: nbytes cut to the row, bits past the stream read as zero."""
+    B, nsym, bytes_, nbytes, q, _ = _decoder_args(cdf_int, bytes_, nbytes, L)
+    _lib.call("pccx_range_decode_n", cdf_int.contiguous().data_ptr(), bytes_.data_ptr(), bytes_.shape[1], nbytes.data_ptr(), B, nsym,
+              _nsym_of(nsym_of, B, bytes_.device).data_ptr(), int(L), q.data_ptr(), _stream())
     return q
 
 

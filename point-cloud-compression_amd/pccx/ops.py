@@ -86,6 +86,29 @@ def normalize(pc, margin=0.01):
     return out, center, longest
 
 
+def counts(v, B, device, name):
+    """A per-cloud count table of a ragged batch as the kernels take it: (B,) int32 on the device, from a host sequence or a tensor."""
+    t = v if isinstance(v, torch.Tensor) else torch.as_tensor([int(x) for x in v], dtype=torch.int32)
+    t = t.to(device=device, dtype=torch.int32).contiguous()
+    if tuple(t.shape) != (B,):
+        raise _lib.PccxError(f"{name}: one int per cloud is expected, got {tuple(t.shape)} for {B} clouds")
+    return t
+
+
+def normalize_n(pc, n, margin=0.01):
+    """normalize for a ragged batch (pccx_normalize_n): pc (B,N_max,3), cloud b in its first n[b] rows.  The box is taken over those
+    rows only -- cloud b's results are normalize's on the unpadded cloud, bit for bit -- and the rows behind them come out as zeros."""
+    pc = _f32c(pc, "normalize_n")
+    B, N, _ = pc.shape
+    n = counts(n, B, pc.device, "normalize_n.n")
+    out = torch.empty_like(pc)
+    center = torch.empty(B, 3, device=pc.device, dtype=torch.float32)
+    longest = torch.empty(B, device=pc.device, dtype=torch.float32)
+    _lib.call("pccx_normalize_n", pc.data_ptr(), B, N, n.data_ptr(), float(margin), out.data_ptr(), center.data_ptr(), longest.data_ptr(),
+              _stream())
+    return out, center, longest
+
+
 def denormalize(pc, center, longest, margin=0.01):
     """pn_kit.denormalize (pn_kit.py:62-66), batched."""
     pc = _f32c(pc, "denormalize")
@@ -245,6 +268,21 @@ def farthest_point_sample_batch(xyz, npoint, start_idx=None, workgroups=None, wo
     return out
 
 
+def farthest_point_sample_n(xyz, n, npoint_max, npoint, start_idx=None):
+    """farthest_point_sample_batch for a ragged batch (pccx_fps_n): cloud b samples npoint[b] <= npoint_max of its first n[b] points
+    -> (B, npoint_max) int64, the indices of farthest_point_sample_batch on the unpadded cloud and then the last of them repeated
+    (a gather over the whole row reads real points).  N_max <= KNN_BRUTE_MAX_N = 32768.  start_idx: (B,) or "zero"."""
+    xyz = _f32c(xyz, "farthest_point_sample_n")
+    B, N, _ = xyz.shape
+    n, npoint = counts(n, B, xyz.device, "farthest_point_sample_n.n"), counts(npoint, B, xyz.device, "farthest_point_sample_n.npoint")
+    start = None if start_idx is None or (isinstance(start_idx, str) and start_idx == "zero") else counts(start_idx, B, xyz.device, "farthest_point_sample_n.start_idx")
+    out = torch.empty(B, int(npoint_max), device=xyz.device, dtype=torch.int64)
+    work = torch.empty(B * N, device=xyz.device, dtype=torch.float32) if N > 16384 else None
+    _lib.call("pccx_fps_n", xyz.data_ptr(), B, N, n.data_ptr(), int(npoint_max), npoint.data_ptr(), start.data_ptr() if start is not None else None,
+              out.data_ptr(), work.data_ptr() if work is not None else None, _stream())
+    return out
+
+
 FPS_BLOCK_MIN, FPS_BLOCK_MAX = 1024, 16384   # points per block of pccx_fps_blocks: one workgroup's registers hold at most 1024 x 16
 
 
@@ -382,6 +420,28 @@ def knn_points(p1, p2, K, return_nn=True, patch_scale=0.0, return_dists=True, re
             return KNN(dists, idx, nn)
         rep = groups.rep                       # the radix-select kernel of the larger shapes skips by the table
     _lib.call("pccx_knn_list", p1.data_ptr(), B, M, p2.data_ptr(), N, int(K), ptr(dists), ptr(idx), ptr(nn), float(patch_scale), ptr(rep), _stream())
+    return KNN(dists, idx, nn)
+
+
+def knn_points_n(p1, p2, n, K, scale, rep=None, return_dists=False, return_idx=False, return_nn=True):
+    """knn_points for a ragged batch (pccx_knn_list_n), the all-pairs search: the keys of cloud b are the first n[b] >= K rows of
+    p2 (B,N_max,3), and its third field holds (nn - p1) * scale[b] (scale: (B,) f32 on the device, none of them 0 unless the points
+    themselves are wanted).  rep as knn_points.  Cloud b's rows are knn_points' on the unpadded cloud, bit for bit."""
+    p1, p2 = _f32c(p1, "knn_points_n.p1"), _f32c(p2, "knn_points_n.p2")
+    B, M, _ = p1.shape
+    N = p2.shape[1]
+    n = counts(n, B, p1.device, "knn_points_n.n")
+    scale = _f32c(scale, "knn_points_n.scale")
+    if tuple(scale.shape) != (B,):
+        raise _lib.PccxError(f"knn_points_n: scale must be (B,) float32, got {tuple(scale.shape)}")
+    if rep is not None and (rep.dtype != torch.int32 or rep.numel() != B * M or not rep.is_cuda or not rep.is_contiguous()):
+        raise _lib.PccxError("knn_points_n: rep must be the dense int32 (B*M) table of patch_groups over the queries")
+    dists = torch.empty(B, M, K, device=p1.device, dtype=torch.float32) if return_dists else None
+    idx = torch.empty(B, M, K, device=p1.device, dtype=torch.int64) if return_idx else None
+    nn = torch.empty(B, M, K, 3, device=p1.device, dtype=torch.float32) if return_nn else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    _lib.call("pccx_knn_list_n", p1.data_ptr(), B, M, p2.data_ptr(), N, n.data_ptr(), int(K), ptr(dists), ptr(idx), ptr(nn), scale.data_ptr(),
+              ptr(rep), _stream())
     return KNN(dists, idx, nn)
 
 
@@ -676,6 +736,48 @@ def octree_encode(centres, N, min_bpp, out_bytes=None, out_nbytes=None, wide=Fal
     _lib.call("pccx_octree_encode_wide" if wide or S > PATCH_GROUPS_MAX_S else "pccx_octree_encode", centres.data_ptr(), B, S, int(N), float(min_bpp), r["bits"].data_ptr(),
               r["nbits"].data_ptr(), r["depth"].data_ptr(), r["bytes"].data_ptr(), r["nbytes"].data_ptr(), _stream())
     return r
+
+
+def octree_encode_n(centres, S, N, min_bpp, out_bytes=None, out_nbytes=None):
+    """octree_encode for a ragged batch (pccx_octree_encode_n): centres (B,S_max,3), S_max <= 1024, of which cloud b codes its first
+    S[b] with its own point count N[b] in the depth search.  The same dict; the strides are those of S_max, and cloud b's
+    bytes[:nbytes] / depth are octree_encode's on its own S[b] centres."""
+    centres = _f32c(centres, "octree_encode_n")
+    B, S_max, _ = centres.shape
+    cap = octree_bits_capacity(S_max)
+    dev = centres.device
+    S, N = counts(S, B, dev, "octree_encode_n.S"), counts(N, B, dev, "octree_encode_n.N")
+    if out_bytes is None:
+        out_bytes = torch.empty(B, (cap + 7) // 8, device=dev, dtype=torch.uint8)
+    if out_nbytes is None:
+        out_nbytes = torch.empty(B, device=dev, dtype=torch.int32)
+    if (tuple(out_bytes.shape) != (B, (cap + 7) // 8) or out_bytes.dtype != torch.uint8 or not out_bytes.is_contiguous()
+            or tuple(out_nbytes.shape) != (B,) or out_nbytes.dtype != torch.int32 or not out_nbytes.is_contiguous()):
+        raise _lib.PccxError("octree_encode_n: out_bytes must be dense (B, (cap+7)//8) u8 and out_nbytes dense (B,) i32")
+    r = dict(bits=torch.empty(B, cap, device=dev, dtype=torch.uint8),
+             nbits=torch.empty(B, device=dev, dtype=torch.int32),
+             depth=torch.empty(B, device=dev, dtype=torch.int32),
+             bytes=out_bytes, nbytes=out_nbytes)
+    _lib.call("pccx_octree_encode_n", centres.data_ptr(), B, S_max, S.data_ptr(), N.data_ptr(), float(min_bpp), r["bits"].data_ptr(),
+              r["nbits"].data_ptr(), r["depth"].data_ptr(), r["bytes"].data_ptr(), r["nbytes"].data_ptr(), _stream())
+    return r
+
+
+def reassemble_n(patches, S, k, scale, centres, center, longest, margin=0.01):
+    """The reassembly step of decompress.py:104-116 for a ragged batch (pccx_reassemble_n): patches (B*S_max,k,3) raw decoder output,
+    centres (B,S_max,3), S (B,) patches per cloud, scale (B,) f32 on the device -> (B, S_max*k, 3), cloud b's first S[b]*k rows
+    filled, the rest left unwritten."""
+    centres = _f32c(centres, "reassemble_n.centres")
+    B, S_max, _ = centres.shape
+    patches = _f32c(patches, "reassemble_n.patches")
+    if patches.numel() != B * S_max * int(k) * 3:
+        raise _lib.PccxError(f"reassemble_n: patches of {tuple(patches.shape)} for {B} clouds of {S_max} patches of {k} points")
+    S = counts(S, B, centres.device, "reassemble_n.S")
+    scale, center, longest = _f32c(scale, "reassemble_n.scale"), _f32c(center.reshape(B, 3), "reassemble_n.center"), _f32c(longest.reshape(B), "reassemble_n.longest")
+    out = torch.empty(B, S_max * int(k), 3, device=centres.device, dtype=torch.float32)
+    _lib.call("pccx_reassemble_n", patches.data_ptr(), B, S_max, S.data_ptr(), int(k), scale.data_ptr(), centres.data_ptr(), center.data_ptr(),
+              longest.data_ptr(), float(margin), out.data_ptr(), _stream())
+    return out
 
 
 def octree_decode(bytes_, nbytes, mode="reference", S_out=64, wide=False):
