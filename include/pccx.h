@@ -140,6 +140,13 @@ PCCX_API int pccx_nn_dist(const float *X, int B, int P, const float *Y, int Q, f
 PCCX_API int pccx_nn_dist_split_count(int B, int P, int Q);
 PCCX_API int pccx_nn_dist_split(const float *X, int B, int P, const float *Y, int Q, int split, float *scratch_d, int32_t *scratch_nn,
                                 float *d2, int32_t *nn, void *stream);
+/* pccx_nn_dist over a ragged batch, the building block of pytorch3d chamfer_distance(x, y, x_lengths=, y_lengths=): X (B,P_max,3),
+ * Y (B,Q_max,3); p, q: (B) int32 ON THE DEVICE (a captured step may change them between replays), clamped into [0, P_max] /
+ * [0, Q_max] where they are read.  Cloud b queries its first p[b] rows against the first q[b] rows of Y; the rows behind the counts
+ * are never loaded (they may hold NaN), d2 / nn (B,P_max) behind p[b] stay unwritten, and the first p[b] entries are bit for bit
+ * pccx_nn_dist's on the unpadded pair.  A cloud with a zero count writes nothing. */
+PCCX_API int pccx_nn_dist_n(const float *X, int B, int P_max, const int32_t *p, const float *Y, int Q_max, const int32_t *q, float *d2,
+                            int32_t *nn, void *stream);
 
 /* Exact nearest-neighbour search through a uniform grid index, for whole rooms (10^5 .. 10^6 points) where the all-pairs kernels
  * above cost P * Q pairs: what open3d's KDTreeFlann.search_knn_vector_3d answers in eval.py:55-81 (30-NN for the normals, 1-NN for
@@ -194,6 +201,19 @@ PCCX_API int pccx_chamfer_grad_dev(const float *X, int B, int P, const float *Y,
 PCCX_API int pccx_chamfer_grad_dev_acc(const float *X, int B, int P, const float *Y, int Q, const int32_t *nn_xy,
                                        const int32_t *nn_yx, const float *grad_out_dev, float *gX, float *gY, int flags,
                                        void *stream);
+/* The same two for ragged batches: pytorch3d.loss.chamfer_distance's x_lengths / y_lengths (chamfer.py: "Optional LongTensor of shape
+ * (N,) giving the number of points in each cloud"), here p, q (B) int32 on the device, as pccx_nn_dist_n takes them.
+ * pccx_chamfer_mean_n: out[0] = (1/B) sum_b [ (1/p_b) sum_{i<p_b} dxy[b,i] + (1/q_b) sum_{j<q_b} dyx[b,j] ] in double; dxy (B,P_max),
+ * dyx (B,Q_max) from pccx_nn_dist_n; per_cloud: NULL or (B) f32, the bracket of each cloud (batch_reduction=None).  A zero count
+ * divides by 1, pytorch3d's clamp.  One launch.
+ * pccx_chamfer_grad_n: its backward for the argmins of pccx_nn_dist_n, wx_b = g / (B p_b), wy_b = g / (B q_b), g read from
+ * grad_out_dev.  gX (B,P_max,3), gY (B,Q_max,3): cleared here, or accumulated into when flags & 4 says the caller cleared them; rows
+ * >= p[b] of gX and >= q[b] of gY end as exact zeros.  Atomic scatter, as pccx_chamfer_grad: there is no deterministic form. */
+PCCX_API int pccx_chamfer_mean_n(const float *dxy, const float *dyx, int B, int P_max, const int32_t *p, int Q_max, const int32_t *q,
+                                 float *out, float *per_cloud, void *stream);
+PCCX_API int pccx_chamfer_grad_n(const float *X, int B, int P_max, const int32_t *p, const float *Y, int Q_max, const int32_t *q,
+                                 const int32_t *nn_xy, const int32_t *nn_yx, const float *grad_out_dev, float *gX, float *gY, int flags,
+                                 void *stream);
 
 /* D2 (point-to-plane) PSNR support (eval.py:58-60,73-81).  pccx_estimate_normals: PCA normal of
  * every point over its K neighbours nbr (B,N,K) int64 (e.g. pccx_knn with K=30, as open3d's

@@ -3,7 +3,9 @@
 pccx.train_ipdae; checkpoints carry the reference's names (ae_step{N}.pkl, prob_step{N}.pkl, optimizer_step{N}.pkl, global_step{N}.pkl,
 train.py:103-108) and the reference's state_dict keys, so compress.py / decompress.py load them unchanged.  Two flags are this
 path's own: --octree-mode (the spelling of compress.py / decompress.py; 'full' trains on the centres those decode in that mode, the
-mode is not stored in the .pkl files) and --val_glob (the real codec's bpp and D1 on held-out files at every step window)."""
+mode is not stored in the .pkl files) and --val_glob (the real codec's bpp and D1 on held-out files at every step window).
+--ragged (with --octree-mode full) trains on files of different point counts, several sizes in one step: the trainer's side of
+``compress.py --ragged``."""
 import argparse
 import os
 from glob import glob
@@ -12,7 +14,7 @@ import numpy as np
 
 import _common  # noqa: F401
 import torch
-from pccx import _lib, models, plyio, train_ipdae
+from pccx import _lib, codec, models, plyio, train_ipdae
 
 torch.manual_seed(11)                                                                  # train.py:17-19
 np.random.seed(11)
@@ -45,6 +47,9 @@ parser.add_argument('--octree-mode', choices=['reference', 'full'], default='ref
                          "decode, the centres compress.py / decompress.py --octree-mode full use (any S = N*ALPHA/K in 1..1024, at every --K of the table).")
 parser.add_argument('--val_glob', default=None, help='Point clouds glob pattern (files of --N points) run through the real codec at every --step_window.')
 parser.add_argument('--deterministic', action='store_true', help='every reduction of a step in a fixed order: the same inputs give the same bits, run after run (one GPU).')
+parser.add_argument('--ragged', action='store_true',
+                    help="files of different point counts, mixed in one step (needs --octree-mode full; --N is ignored): every file must hold "
+                         "K..32768 points and S = n*ALPHA//K patches inside the range compress.py --ragged takes; --val_glob files likewise.")
 
 
 VAL_CHUNK = 16                         # clouds per codec batch of a --val_glob pass: the validation set's size does not bound the codec's buffers
@@ -84,13 +89,108 @@ def dump_checkpoints(tr, folder, global_step=''):                               
     torch.save(global_step, os.path.join(folder, f'global_step{global_step}.pkl'))
 
 
+def window_report(tr, args, epoch, losses, fbpps, bpps, validate, n_val):
+    """the window's line, its checkpoints and, with validation files, the real codec on the current weights (validate(i): the clouds
+    [i, i + VAL_CHUNK), repacked by the trainer): means weighted by v['n']"""
+    print(f"[Epoch {epoch}] Step {tr.global_step} | Feature bpp: {np.mean(fbpps):.5f} | Bpp: {np.mean(bpps):.5f} | "
+          f"Loss: {np.mean(losses):.5f}")
+    dump_checkpoints(tr, args.model_save_folder, tr.global_step)
+    if validate is not None:
+        vs = [validate(i) for i in range(0, n_val, VAL_CHUNK)]
+        n = sum(v['n'] for v in vs)
+        print(f"[Epoch {epoch}] Step {tr.global_step} | Val bpp: {sum(v['bpp'] * v['n'] for v in vs) / n:.5f} | "
+              f"Val D1: {sum(v['d1_psnr'] * v['n'] for v in vs) / n:.3f} dB ({n} clouds)")
+
+
+def read_ragged(pattern, flag, K, ALPHA):
+    """the files of a glob, read once, each checked against the shape rule of a ragged batch (codec.ragged_shape_refusal)
+    -> (files, clouds, refusals: one line per file outside the rule)"""
+    files = sorted(glob(pattern, recursive=True))
+    clouds = [plyio.read_point_cloud(f).astype(np.float32) for f in files]
+    why = [(f, codec.ragged_shape_refusal([c.shape[0]], K, ALPHA)) for f, c in zip(files, clouds)]
+    refused = [f"{flag} {f}: {w}" for f, w in why if w] if files else [f"{flag} {pattern}: no file matches"]
+    return files, clouds, refused
+
+
+def main_ragged(args):
+    """--ragged: the loop of main() over files of different point counts.  The files live in HBM as one padded (F, N_cap, 3) tensor
+    (codec.pad_clouds) with their counts; a step takes --batch_size of them, whatever their sizes, and by default replays ONE step
+    captured at (N_cap, S_cap).  --eager, or a short last batch, goes through IpdaeTrainer.step_ragged."""
+    K = args.K
+    args.k = K // args.ALPHA
+    print(f"Training {args.model} on {args.device}")
+    print(f"autocast={args.autocast}, eager={args.eager}")
+    print("octree_mode=full: these checkpoints are for compress.py/decompress.py --octree-mode full")
+    try:
+        train_ipdae.check_selection(args.ALPHA, K, args.octree_mode)                   # --K, before anything is read or allocated
+    except _lib.PccxError as e:
+        raise SystemExit(str(e))
+    os.makedirs(args.model_save_folder, exist_ok=True)
+    files, clouds, refused = read_ragged(args.train_glob, "--train_glob", K, args.ALPHA)
+    val_files, val_clouds = [], []
+    if args.val_glob:
+        val_files, val_clouds, more = read_ragged(args.val_glob, "--val_glob", K, args.ALPHA)
+        refused += more
+    if refused:
+        raise SystemExit("--ragged: nothing is dropped silently; these files are outside what a ragged batch takes:\n" + "\n".join(refused))
+    data, counts = codec.pad_clouds(clouds, device=args.device)                        # the whole training set lives in HBM
+    N_cap, S_cap = int(data.shape[1]), codec.ragged_plan(counts, K, args.ALPHA, args.N0, args.d).S_pad
+    print(f"--ragged: --N is ignored; {len(files)} files of {min(counts)}..{max(counts)} points, N_cap={N_cap}, S_cap={S_cap}, K={K}, d={args.d}, L={args.L}")
+    val = [torch.from_numpy(c).to(args.device) for c in val_clouds]
+    if val:
+        print(f"Loaded {len(val)} validation clouds of {min(len(c) for c in val)}..{max(len(c) for c in val)} points")
+    ae = models.AE(K=K, k=args.k, d=args.d, L=args.L).to(args.device)
+    prob = models.ConditionalProbabilityModel(args.L, args.d).to(args.device)
+    tr = train_ipdae.IpdaeTrainer(ae, prob, N=N_cap, N0=args.N0, ALPHA=args.ALPHA, K=K, lr=args.lr, lamda=args.lamda,
+                                  rate_loss_enable_step=args.rate_loss_enable_step, lr_decay=args.lr_decay,
+                                  lr_decay_steps=args.lr_decay_steps, autocast=args.autocast, octree_mode=args.octree_mode)
+    if not args.reset:
+        tr.global_step = load_checkpoints(tr, args.model_save_folder)
+        print(f"Resuming from step {tr.global_step}")
+    else:
+        print("Resetting training from scratch.")
+    validate = (lambda i: tr.validate_ragged(val[i:i + VAL_CHUNK], [0] * len(val[i:i + VAL_CHUNK]))) if val else None
+    losses, fbpps, bpps = [], [], []
+    graph = None                       # train_ipdae.RaggedGraphedIpdaeStep, captured on the first full batch at the capacities
+    for epoch in range(9999):
+        order = torch.randperm(len(files))
+        for b0 in range(0, len(files), args.batch_size):
+            if tr.global_step > args.max_steps:
+                break
+            pick = order[b0:b0 + args.batch_size]
+            batch, n = data[pick.to(args.device)], [counts[i] for i in pick.tolist()]
+            lr_before = tr.lr
+            starts = torch.cat([torch.randint(0, nb, (1,), dtype=torch.long) for nb in n])   # the draw of pn_kit.py:321, inside each cloud
+            if args.eager or len(n) != args.batch_size:
+                out = tr.step_ragged(batch, n, starts, S_cap=S_cap)
+            elif graph is None:
+                graph = tr.graphed_ragged(N_cap, S_cap, args.batch_size, batch, n, starts, warmup=1)   # the warm-up iteration IS this step
+                out = {k_: float(v) for k_, v in zip(("loss", "fbpp", "bpp"), graph.warm_out)}
+            else:
+                out = graph(batch, n, starts)
+            losses.append(out["loss"]), fbpps.append(out["fbpp"]), bpps.append(out["bpp"])
+            if tr.global_step % args.step_window == 0:
+                window_report(tr, args, epoch, losses, fbpps, bpps, validate, len(val))
+                losses, fbpps, bpps = [], [], []
+            if tr.lr != lr_before:
+                print(f"LR decayed to {tr.lr} at step {tr.global_step}")
+        if tr.global_step > args.max_steps:
+            break
+    dump_checkpoints(tr, args.model_save_folder)
+
+
 def main():
     args = parser.parse_args()
     if args.model != 'AE':
         raise SystemExit(f"--model {args.model}: only AE (the IPDAE autoencoder, AE.py) trains on this path; PPPF-AE's train-mode BatchNorm "
                          f"stacks are not built (pccx/train_ipdae.py)")
+    if args.ragged and (args.octree_mode != 'full' or args.deterministic):
+        raise SystemExit("--ragged needs --octree-mode full (octree_mode 'reference' is S = 64 by definition) and excludes --deterministic "
+                         "(the ordered Chamfer scatter is dense only)")
     if not torch.cuda.is_available():
         raise SystemExit("pccx needs a ROCm GPU: there is no CPU path")
+    if args.ragged:
+        return main_ragged(args)
     N, K = args.N, args.K
     args.S, args.k = N * args.ALPHA // K, K // args.ALPHA                              # train.py:253
     print(f"Training {args.model} on {args.device}")
@@ -148,16 +248,9 @@ def main():
                 out = graph(batch, starts)
             losses.append(out["loss"]), fbpps.append(out["fbpp"]), bpps.append(out["bpp"])
             if tr.global_step % args.step_window == 0:                                 # :241-247
-                print(f"[Epoch {epoch}] Step {tr.global_step} | Feature bpp: {np.mean(fbpps):.5f} | Bpp: {np.mean(bpps):.5f} | "
-                      f"Loss: {np.mean(losses):.5f}")
+                window_report(tr, args, epoch, losses, fbpps, bpps,
+                              None if val is None else lambda i: tr.validate(val[i:i + VAL_CHUNK], val_starts[i:i + VAL_CHUNK]), 0 if val is None else len(val))
                 losses, fbpps, bpps = [], [], []
-                dump_checkpoints(tr, args.model_save_folder, tr.global_step)
-                if val is not None:
-                    # the real codec on the current weights (validate repacks them), VAL_CHUNK clouds at a time: means weighted by v['n']
-                    vs = [tr.validate(val[i:i + VAL_CHUNK], val_starts[i:i + VAL_CHUNK]) for i in range(0, len(val), VAL_CHUNK)]
-                    n = sum(v['n'] for v in vs)
-                    print(f"[Epoch {epoch}] Step {tr.global_step} | Val bpp: {sum(v['bpp'] * v['n'] for v in vs) / n:.5f} | "
-                          f"Val D1: {sum(v['d1_psnr'] * v['n'] for v in vs) / n:.3f} dB ({n} clouds)")
             if tr.lr != lr_before:
                 print(f"LR decayed to {tr.lr} at step {tr.global_step}")               # :254
         if tr.global_step > args.max_steps:

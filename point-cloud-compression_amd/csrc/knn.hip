@@ -742,16 +742,14 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // operation sequence per pair as pccx_sqdist.  Without the argmin the update is one v_min3_f32.
 // XPT queries per thread: 4 (1024 per workgroup) for the evaluation batches; 1 when the batch is too small to fill the chip that way
 // (the training step's 4 clouds: 32 workgroups become 128).  A query's scan over Y is the same sequence either way.
+// One workgroup's share of a cloud: its 256 XPT queries of the P rows at xp against the references [q_begin, q_end) of yp; d2 / nn are the
+// cloud's output rows.  nn_dist_kernel and nn_dist_n_kernel differ only in where P and the range come from.
 template <bool WANT_NN, int XPT>
-// gridDim.z > 1 (pccx_nn_dist_split): workgroup z scans only the references [z qchunk, (z + 1) qchunk) and writes its partial
-// (distance, index) to slice z of d2 / nn (B P entries each); nn_merge_kernel then takes the first minimum over the slices.
-__global__ __launch_bounds__(256) void nn_dist_kernel(const float *__restrict__ X, int P, const float *__restrict__ Y, int Q,
-                                                      float *__restrict__ d2, int32_t *__restrict__ nn, int qchunk)
+__device__ __forceinline__ void nn_dist_scan(const float *__restrict__ xp, int P, const float *__restrict__ yp, int q_begin, int q_end,
+                                             float *__restrict__ d2, int32_t *__restrict__ nn)
 {
     __shared__ __attribute__((aligned(8))) float tyx[NND_TILE], tyy[NND_TILE], tyz[NND_TILE];
-    const int b = blockIdx.y, tid = threadIdx.x;
-    const float *xp = X + (size_t)b * P * 3;
-    const float *yp = Y + (size_t)b * Q * 3;
+    const int tid = threadIdx.x;
     float x[XPT][3], best[XPT];
     int bi[XPT];
 #pragma unroll
@@ -761,8 +759,6 @@ __global__ __launch_bounds__(256) void nn_dist_kernel(const float *__restrict__ 
         x[j][0] = xp[3 * ii]; x[j][1] = xp[3 * ii + 1]; x[j][2] = xp[3 * ii + 2];
         best[j] = INFINITY; bi[j] = -1;
     }
-    const int q_begin = blockIdx.z * qchunk, q_end = q_begin + qchunk < Q ? q_begin + qchunk : Q;
-    const size_t slice = (size_t)blockIdx.z * gridDim.y * P;
     for (int base = q_begin; base < q_end; base += NND_TILE) {
         const int cnt = q_end - base < NND_TILE ? q_end - base : NND_TILE;
         const int cnt2 = (cnt + 1) & ~1;                  // an odd tail repeats its last point: no effect on min / first argmin
@@ -792,10 +788,39 @@ __global__ __launch_bounds__(256) void nn_dist_kernel(const float *__restrict__ 
     for (int j = 0; j < XPT; ++j) {
         int i = blockIdx.x * (256 * XPT) + j * 256 + tid;
         if (i < P) {
-            d2[slice + (size_t)b * P + i] = best[j];
-            if (WANT_NN) nn[slice + (size_t)b * P + i] = bi[j];
+            d2[i] = best[j];
+            if (WANT_NN) nn[i] = bi[j];
         }
     }
+}
+
+template <bool WANT_NN, int XPT>
+// gridDim.z > 1 (pccx_nn_dist_split): workgroup z scans only the references [z qchunk, (z + 1) qchunk) and writes its partial
+// (distance, index) to slice z of d2 / nn (B P entries each); nn_merge_kernel then takes the first minimum over the slices.
+__global__ __launch_bounds__(256) void nn_dist_kernel(const float *__restrict__ X, int P, const float *__restrict__ Y, int Q,
+                                                      float *__restrict__ d2, int32_t *__restrict__ nn, int qchunk)
+{
+    const int b = blockIdx.y;
+    const int q_begin = blockIdx.z * qchunk, q_end = q_begin + qchunk < Q ? q_begin + qchunk : Q;
+    const size_t row = (size_t)blockIdx.z * gridDim.y * P + (size_t)b * P;
+    nn_dist_scan<WANT_NN, XPT>(X + (size_t)b * P * 3, P, Y + (size_t)b * Q * 3, q_begin, q_end, d2 + row, WANT_NN ? nn + row : nullptr);
+}
+
+// Ragged batches (pytorch3d chamfer_distance's x_lengths / y_lengths): cloud b queries its first p[b] rows of X (B,P_max,3) against the
+// first q[b] rows of Y (B,Q_max,3), both counts read on the device and clamped into their capacities here.  The rows behind the counts
+// are never loaded (pad_clouds leaves NaN there), the outputs behind p[b] stay unwritten, and a query's scan is nn_dist_scan's: cloud
+// b's d2 / nn are those of pccx_nn_dist on the unpadded cloud, bit for bit.  A workgroup with no query of its own leaves before any
+// barrier; a cloud with a zero count forms no address.
+template <bool WANT_NN, int XPT>
+__global__ __launch_bounds__(256) void nn_dist_n_kernel(const float *__restrict__ X, int P_max, const int32_t *__restrict__ p,
+                                                        const float *__restrict__ Y, int Q_max, const int32_t *__restrict__ q,
+                                                        float *__restrict__ d2, int32_t *__restrict__ nn)
+{
+    const int b = blockIdx.y;
+    const int pb = min(max(p[b], 0), P_max), qb = min(max(q[b], 0), Q_max);
+    if ((int)blockIdx.x * (256 * XPT) >= pb || qb == 0) return;
+    const size_t row = (size_t)b * P_max;
+    nn_dist_scan<WANT_NN, XPT>(X + row * 3, pb, Y + (size_t)b * Q_max * 3, 0, qb, d2 + row, WANT_NN ? nn + row : nullptr);
 }
 
 extern "C" int pccx_nn_dist(const float *X, int B, int P, const float *Y, int Q, float *d2, int32_t *nn, void *stream)
@@ -814,6 +839,30 @@ extern "C" int pccx_nn_dist(const float *X, int B, int P, const float *Y, int Q,
     } else {
         if (small) hipLaunchKernelGGL((nn_dist_kernel<false, 1>), dim3(gx, B), dim3(256), 0, st, X, P, Y, Q, d2, nn, Q);
         else hipLaunchKernelGGL((nn_dist_kernel<false, 4>), dim3(gx, B), dim3(256), 0, st, X, P, Y, Q, d2, nn, Q);
+    }
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+// pccx_nn_dist with per-cloud counts p, q (B) int32 on the device; the grid and the queries per thread are chosen from the capacities
+// as pccx_nn_dist chooses them from the shape (the results do not depend on either)
+extern "C" int pccx_nn_dist_n(const float *X, int B, int P_max, const int32_t *p, const float *Y, int Q_max, const int32_t *q, float *d2,
+                              int32_t *nn, void *stream)
+{
+    if (B == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
+    PCCX_CHECK_ARG(X && Y && p && q && d2, "pccx_nn_dist_n: null pointer");
+    PCCX_CHECK_ARG(B >= 0 && P_max >= 1 && Q_max >= 1, "pccx_nn_dist_n: bad shape");
+    PCCX_CHECK_ARG(B <= 65535, "pccx_nn_dist_n: B=%d > 65535 unsupported", B);
+    const bool small = (long long)B * ((P_max + 1023) / 1024) < 512;
+    const int xpt = small ? 1 : 4;
+    const int gx = (P_max + 256 * xpt - 1) / (256 * xpt);
+    hipStream_t st = (hipStream_t)stream;
+    if (nn) {
+        if (small) hipLaunchKernelGGL((nn_dist_n_kernel<true, 1>), dim3(gx, B), dim3(256), 0, st, X, P_max, p, Y, Q_max, q, d2, nn);
+        else hipLaunchKernelGGL((nn_dist_n_kernel<true, 4>), dim3(gx, B), dim3(256), 0, st, X, P_max, p, Y, Q_max, q, d2, nn);
+    } else {
+        if (small) hipLaunchKernelGGL((nn_dist_n_kernel<false, 1>), dim3(gx, B), dim3(256), 0, st, X, P_max, p, Y, Q_max, q, d2, nn);
+        else hipLaunchKernelGGL((nn_dist_n_kernel<false, 4>), dim3(gx, B), dim3(256), 0, st, X, P_max, p, Y, Q_max, q, d2, nn);
     }
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
@@ -1024,21 +1073,18 @@ __device__ __forceinline__ void scatter3_combined(float *dst, int j, bool on, fl
     }
 }
 
-__global__ void chamfer_grad_kernel(const float *__restrict__ X, int P, const float *__restrict__ Y, int Q,
-                                    const int32_t *__restrict__ nn_xy, const int32_t *__restrict__ nn_yx, float wx, float wy,
-                                    const float *__restrict__ g_dev, float *__restrict__ gX, float *__restrict__ gY)
+// one cloud's share of a thread: point t of x (P rows) and point t of y (Q rows), nxy / nyx / gx / gy the cloud's own rows
+__device__ __forceinline__ void chamfer_grad_cloud(const float *__restrict__ x, int P, const float *__restrict__ y, int Q,
+                                                   const int32_t *__restrict__ nxy, const int32_t *__restrict__ nyx, float wx, float wy,
+                                                   float *__restrict__ gx, float *__restrict__ gy)
 {
-    if (g_dev) { wx *= *g_dev; wy *= *g_dev; }        // upstream gradient read on the device (no host sync; hipGraph capture)
-    const int b = blockIdx.y;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const float *x = X + (size_t)b * P * 3, *y = Y + (size_t)b * Q * 3;
-    float *gx = gX + (size_t)b * P * 3, *gy = gY + (size_t)b * Q * 3;
     {
         const bool on = t < P;
         int j = 0;
         float d[3] = {0.f, 0.f, 0.f};
         if (on) {
-            j = nn_xy[(size_t)b * P + t];
+            j = nxy[t];
             for (int a = 0; a < 3; ++a) {
                 d[a] = 2.f * wx * (x[3 * t + a] - y[3 * j + a]);
                 atomicAdd(&gx[3 * t + a], d[a]);
@@ -1051,7 +1097,7 @@ __global__ void chamfer_grad_kernel(const float *__restrict__ X, int P, const fl
         int i = 0;
         float d[3] = {0.f, 0.f, 0.f};
         if (on) {
-            i = nn_yx[(size_t)b * Q + t];
+            i = nyx[t];
             for (int a = 0; a < 3; ++a) {
                 d[a] = 2.f * wy * (y[3 * t + a] - x[3 * i + a]);
                 atomicAdd(&gy[3 * t + a], d[a]);
@@ -1059,6 +1105,33 @@ __global__ void chamfer_grad_kernel(const float *__restrict__ X, int P, const fl
         }
         scatter3_combined(gx, i, on, -d[0], -d[1], -d[2]);
     }
+}
+
+__global__ void chamfer_grad_kernel(const float *__restrict__ X, int P, const float *__restrict__ Y, int Q,
+                                    const int32_t *__restrict__ nn_xy, const int32_t *__restrict__ nn_yx, float wx, float wy,
+                                    const float *__restrict__ g_dev, float *__restrict__ gX, float *__restrict__ gY)
+{
+    if (g_dev) { wx *= *g_dev; wy *= *g_dev; }        // upstream gradient read on the device (no host sync; hipGraph capture)
+    const size_t b = blockIdx.y;
+    chamfer_grad_cloud(X + b * P * 3, P, Y + b * Q * 3, Q, nn_xy + b * P, nn_yx + b * Q, wx, wy, gX + b * P * 3, gY + b * Q * 3);
+}
+
+// Ragged batches: cloud b's loss term is mean_{i < p[b]} + mean_{j < q[b]} (pccx_chamfer_mean_n), so wx_b = g / (B p[b]) and
+// wy_b = g / (B q[b]) -- formed as chamfer_grad_launch forms them, one float division, then times the upstream gradient -- and only the
+// first p[b] / q[b] rows take part.  nn_xy (B,P_max) / nn_yx (B,Q_max) come from pccx_nn_dist_n with the same counts.  Rows behind the
+// counts receive nothing: they keep the zeros the buffers were cleared to.  A cloud with a zero count forms no address.
+__global__ void chamfer_grad_n_kernel(const float *__restrict__ X, int B, int P_max, const int32_t *__restrict__ p,
+                                      const float *__restrict__ Y, int Q_max, const int32_t *__restrict__ q,
+                                      const int32_t *__restrict__ nn_xy, const int32_t *__restrict__ nn_yx,
+                                      const float *__restrict__ g_dev, float *__restrict__ gX, float *__restrict__ gY)
+{
+    const size_t b = blockIdx.y;
+    const int pb = min(max(p[b], 0), P_max), qb = min(max(q[b], 0), Q_max);
+    if (pb == 0 || qb == 0 || (int)(blockIdx.x * blockDim.x) >= max(pb, qb)) return;
+    const float g = *g_dev;
+    const float wx = 1.0f / ((float)B * pb) * g, wy = 1.0f / ((float)B * qb) * g;
+    chamfer_grad_cloud(X + b * P_max * 3, pb, Y + b * Q_max * 3, qb, nn_xy + b * P_max, nn_yx + b * Q_max, wx, wy, gX + b * P_max * 3,
+                       gY + b * Q_max * 3);
 }
 
 // chamfer_distance's value from the two nearest-neighbour passes (pytorch3d defaults: point_reduction = batch_reduction = "mean"):
@@ -1089,6 +1162,45 @@ extern "C" int pccx_chamfer_mean(const float *dxy, const float *dyx, int B, int 
 {
     PCCX_CHECK_ARG(dxy && dyx && out && B >= 1 && P >= 1 && Q >= 1, "pccx_chamfer_mean: bad arguments");
     hipLaunchKernelGGL(chamfer_mean_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, dxy, dyx, B, P, Q, out);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+// The same value over ragged clouds (pytorch3d's x_lengths / y_lengths): cloud b's point means run over its first p[b] / q[b] entries
+// and are divided by those counts (by 1 for a zero count, pytorch3d's clamp: such a direction adds 0),
+//   out = (1/B) sum_b [ (1/p_b) sum_{i<p_b} dxy[b,i] + (1/q_b) sum_{j<q_b} dyx[b,j] ]   in double; per_cloud (B) f32: each bracket, or null.
+// One workgroup, one reduction per cloud (the bracket is wanted per cloud); entries behind the counts are not read.
+__global__ __launch_bounds__(1024) void chamfer_mean_n_kernel(const float *__restrict__ dxy, const float *__restrict__ dyx, int B, int P_max,
+                                                              const int32_t *__restrict__ p, int Q_max, const int32_t *__restrict__ q,
+                                                              float *__restrict__ out, float *__restrict__ per_cloud)
+{
+    __shared__ double red[16];
+    double tot = 0;                                       // thread 0's: the sum of the brackets
+    for (int b = 0; b < B; ++b) {
+        const int pb = min(max(p[b], 0), P_max), qb = min(max(q[b], 0), Q_max);
+        double sx = 0, sy = 0;
+        for (int i = threadIdx.x; i < pb; i += 1024) sx += (double)dxy[(size_t)b * P_max + i];
+        for (int i = threadIdx.x; i < qb; i += 1024) sy += (double)dyx[(size_t)b * Q_max + i];
+        double v = sx / (double)(pb > 0 ? pb : 1) + sy / (double)(qb > 0 ? qb : 1);
+        for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+        __syncthreads();                                  // red is free again: thread 0 has read the previous cloud's
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double t = 0;
+            for (int w = 0; w < 16; ++w) t += red[w];
+            if (per_cloud) per_cloud[b] = (float)t;
+            tot += t;
+        }
+    }
+    if (threadIdx.x == 0) out[0] = (float)(tot / (double)B);
+}
+
+extern "C" int pccx_chamfer_mean_n(const float *dxy, const float *dyx, int B, int P_max, const int32_t *p, int Q_max, const int32_t *q,
+                                   float *out, float *per_cloud, void *stream)
+{
+    PCCX_CHECK_ARG(dxy && dyx && p && q && out && B >= 1 && P_max >= 1 && Q_max >= 1, "pccx_chamfer_mean_n: bad arguments");
+    hipLaunchKernelGGL(chamfer_mean_n_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, dxy, dyx, B, P_max, p, Q_max, q, out, per_cloud);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }
@@ -1131,6 +1243,27 @@ static int chamfer_grad_launch(const float *X, int B, int P, const float *Y, int
     const int n = P > Q ? P : Q;
     hipLaunchKernelGGL(chamfer_grad_kernel, dim3((n + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, X, P, Y, Q, nn_xy, nn_yx,
                        grad_out / ((float)B * P), grad_out / ((float)B * Q), g_dev, gX, gY);
+    PCCX_CHECK_LAUNCH();
+    return PCCX_OK;
+}
+
+// Backward of pccx_chamfer_mean_n's `out`: gX (B,P_max,3), gY (B,Q_max,3), the upstream gradient read on the device.  flags & 4: the
+// caller hands both over cleared (the step arena) and they are accumulated into; otherwise they are cleared here first, whole -- either
+// way rows >= p[b] of gX and >= q[b] of gY are exact zeros.
+extern "C" int pccx_chamfer_grad_n(const float *X, int B, int P_max, const int32_t *p, const float *Y, int Q_max, const int32_t *q,
+                                   const int32_t *nn_xy, const int32_t *nn_yx, const float *grad_out_dev, float *gX, float *gY, int flags,
+                                   void *stream)
+{
+    if (B == 0) return PCCX_OK;   // empty batch: nothing to do, pointers may be null
+    PCCX_CHECK_ARG(X && Y && p && q && nn_xy && nn_yx && grad_out_dev && gX && gY, "pccx_chamfer_grad_n: null pointer");
+    PCCX_CHECK_ARG(P_max >= 1 && Q_max >= 1 && B >= 0 && B <= 65535, "pccx_chamfer_grad_n: bad shape");
+    if (!(flags & 4)) {
+        PCCX_CHECK_HIP(pccx_zero_async(gX, sizeof(float) * (size_t)B * P_max * 3, (hipStream_t)stream));
+        PCCX_CHECK_HIP(pccx_zero_async(gY, sizeof(float) * (size_t)B * Q_max * 3, (hipStream_t)stream));
+    }
+    const int n = P_max > Q_max ? P_max : Q_max;
+    hipLaunchKernelGGL(chamfer_grad_n_kernel, dim3((n + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, X, B, P_max, p, Y, Q_max, q,
+                       nn_xy, nn_yx, grad_out_dev, gX, gY);
     PCCX_CHECK_LAUNCH();
     return PCCX_OK;
 }

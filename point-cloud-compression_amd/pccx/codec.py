@@ -227,6 +227,44 @@ def ragged_plan(n_points, K=256, ALPHA=2, N0=1024, d=16):
                       (1 + 8 * S_pad * 16 + 7) // 8, models.range_cap(S_pad * d))
 
 
+RAGGED_WAY_OUT = " Such clouds go through compress / decompress, one size per call."
+
+
+def ragged_patch_range(K, ALPHA):
+    """(lo, hi): the patch counts S_b a cloud of a ragged batch may have, the ONE rule both sides route by.  lo = ALPHA is n_b = K;
+    hi is OCTREE_MAX_S or, where that comes first, the S of KNN_BRUTE_MAX_N points.  A decoder sees S_b only, so where clouds above
+    and below KNN_BRUTE_MAX_N points share that last S, and it is no multiple of 16 (the tables of the two paths differ there),
+    it is left to the one-cloud path on both sides.  No K that is a power of two is affected."""
+    s_lim = KNN_BRUTE_MAX_N * ALPHA // K
+    hi = min(OCTREE_MAX_S, s_lim)
+    if hi == s_lim and hi % 16 and ((hi + 1) * K - 1) // ALPHA > KNN_BRUTE_MAX_N:
+        hi -= 1
+    return ALPHA, hi
+
+
+def ragged_patch_refusal(S, K, ALPHA):
+    lo, hi = ragged_patch_range(K, ALPHA)
+    for b, v in enumerate(S):
+        if not lo <= int(v) <= hi:
+            return (f"cloud {b}: S={int(v)} patches; a ragged batch takes {lo} <= S_b <= {hi} at K={K}, ALPHA={ALPHA} "
+                    f"(n_b >= K points; OCTREE_MAX_S = {OCTREE_MAX_S} patches; KNN_BRUTE_MAX_N = {KNN_BRUTE_MAX_N} points)." + RAGGED_WAY_OUT)
+    return None
+
+
+def ragged_shape_refusal(n_points, K, ALPHA, N_max=None):
+    """The shape rule of a ragged batch, stated once for the codec (Codec.ragged_refusal) and the trainer (IpdaeTrainer.step_ragged):
+    why clouds of these point counts cannot share a slab of N_max rows (default: the largest count) -- a message naming the limit
+    and the way out, or None.  Host only."""
+    n = [int(v) for v in n_points]
+    N_max = max(n) if N_max is None else int(N_max)
+    if N_max > KNN_BRUTE_MAX_N:
+        return f"a ragged batch holds clouds of at most KNN_BRUTE_MAX_N = {KNN_BRUTE_MAX_N} points, got N_max={N_max}." + RAGGED_WAY_OUT
+    for b, v in enumerate(n):
+        if v < K or v > N_max:
+            return f"cloud {b}: {v} points; a ragged batch needs K = {K} <= n_b <= N_max = {N_max}." + RAGGED_WAY_OUT
+    return ragged_patch_refusal([v * ALPHA // K for v in n], K, ALPHA)
+
+
 def pad_clouds(clouds, device=None):
     """A list of (n_b, 3) arrays or tensors -> (pc (B, N_max, 3) f32, n_points list): every cloud in the first rows of its slab, the
     rows behind it NaN -- no kernel of the ragged path lets them reach a result, and a NaN would show it.  device: where pc goes
@@ -429,7 +467,7 @@ class Codec:
                                   comp.c[:, 3].contiguous(), S=S, scale=scale, margin=self.margin,
                                   matmul=self.decoder_matmul, group=self.group_duplicates, short_list=self._distinct())
 
-    _RAGGED_WAY_OUT = " Such clouds go through compress / decompress, one size per call."
+    _RAGGED_WAY_OUT = RAGGED_WAY_OUT
 
     def ragged_config_refusal(self):
         """Why this Codec's configuration cannot run ragged batches at all, whatever the clouds: a message naming the setting and the
@@ -450,39 +488,17 @@ class Codec:
         return None
 
     def ragged_patch_range(self):
-        """(lo, hi): the patch counts S_b a cloud of a ragged batch may have, the ONE rule both sides route by.  lo = ALPHA is n_b = K;
-        hi is OCTREE_MAX_S or, where that comes first, the S of KNN_BRUTE_MAX_N points.  A decoder sees S_b only, so where clouds above
-        and below KNN_BRUTE_MAX_N points share that last S, and it is no multiple of 16 (the tables of the two paths differ there),
-        it is left to the one-cloud path on both sides.  No K that is a power of two is affected."""
-        s_lim = KNN_BRUTE_MAX_N * self.ALPHA // self.K
-        hi = min(OCTREE_MAX_S, s_lim)
-        if hi == s_lim and hi % 16 and ((hi + 1) * self.K - 1) // self.ALPHA > KNN_BRUTE_MAX_N:
-            hi -= 1
-        return self.ALPHA, hi
+        """ragged_patch_range(K, ALPHA) of this Codec: the patch counts S_b a cloud of a ragged batch may have."""
+        return ragged_patch_range(self.K, self.ALPHA)
 
     def _ragged_patch_refusal(self, S):
-        lo, hi = self.ragged_patch_range()
-        for b, v in enumerate(S):
-            if not lo <= int(v) <= hi:
-                return (f"cloud {b}: S={int(v)} patches; a ragged batch takes {lo} <= S_b <= {hi} at K={self.K}, ALPHA={self.ALPHA} "
-                        f"(n_b >= K points; OCTREE_MAX_S = {OCTREE_MAX_S} patches; KNN_BRUTE_MAX_N = {KNN_BRUTE_MAX_N} points)." + self._RAGGED_WAY_OUT)
-        return None
+        return ragged_patch_refusal(S, self.K, self.ALPHA)
 
     def ragged_refusal(self, n_points, N_max=None):
         """Why compress_ragged cannot take a batch of these point counts (N_max: the rows of its slab, default the largest count): a
         message naming the limit and the way out, or None.  Host only; compress_ragged raises it as ValueError before anything is
         launched, and compress.py --ragged sends a refused file the existing way."""
-        why = self.ragged_config_refusal()
-        if why:
-            return why
-        n = [int(v) for v in n_points]
-        N_max = max(n) if N_max is None else int(N_max)
-        if N_max > KNN_BRUTE_MAX_N:
-            return f"a ragged batch holds clouds of at most KNN_BRUTE_MAX_N = {KNN_BRUTE_MAX_N} points, got N_max={N_max}." + self._RAGGED_WAY_OUT
-        for b, v in enumerate(n):
-            if v < self.K or v > N_max:
-                return f"cloud {b}: {v} points; a ragged batch needs K = {self.K} <= n_b <= N_max = {N_max}." + self._RAGGED_WAY_OUT
-        return self._ragged_patch_refusal([v * self.ALPHA // self.K for v in n])
+        return self.ragged_config_refusal() or ragged_shape_refusal(n_points, self.K, self.ALPHA, N_max)
 
     def ragged_decode_refusal(self, S):
         """Why decompress_ragged cannot take clouds of these patch counts: the same rule seen from the decoder, which knows S_b alone

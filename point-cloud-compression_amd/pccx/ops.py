@@ -592,6 +592,34 @@ def nn_dist(x, y, return_idx=False, search=None):
     return (d2, nn) if return_idx else d2
 
 
+def checked_counts(v, B, cap, device, name):
+    """pytorch3d's x_lengths / y_lengths as the kernels take them (``counts``).  A host sequence is checked against [1, cap] here,
+    before any launch; a device tensor is not read back -- the kernels clamp it into [0, cap] where they read it."""
+    if not isinstance(v, torch.Tensor) or not v.is_cuda:
+        host = [int(c) for c in (v.tolist() if isinstance(v, torch.Tensor) else v)]
+        bad = [(b, c) for b, c in enumerate(host) if not 1 <= c <= cap]
+        if bad:
+            raise _lib.PccxError(f"{name}: every length must lie in [1, {cap}] (the padded size), got " +
+                                 ", ".join(f"{c} for cloud {b}" for b, c in bad[:4]))
+        v = host
+    return counts(v, B, device, name)
+
+
+def nn_dist_n(x, y, x_lengths, y_lengths, return_idx=False):
+    """nn_dist over a ragged batch (pccx_nn_dist_n): x (B,P_max,3), y (B,Q_max,3), cloud b in its first x_lengths[b] / y_lengths[b]
+    rows; what lies behind them is never read (pad_clouds' NaN).  d2 (B,P_max) [, idx (B,P_max) int32]: the first x_lengths[b] entries
+    of cloud b are nn_dist's on the unpadded pair, bit for bit; the entries behind them are left unwritten."""
+    x, y = _f32c(x, "nn_dist_n.x"), _f32c(y, "nn_dist_n.y")
+    B, P, _ = x.shape
+    Q = int(y.shape[1])
+    p, q = checked_counts(x_lengths, B, P, x.device, "nn_dist_n.x_lengths"), checked_counts(y_lengths, B, Q, x.device, "nn_dist_n.y_lengths")
+    d2 = torch.empty(B, P, device=x.device, dtype=torch.float32)
+    nn = torch.empty(B, P, device=x.device, dtype=torch.int32) if return_idx else None
+    _lib.call("pccx_nn_dist_n", x.data_ptr(), B, P, p.data_ptr(), y.data_ptr(), Q, q.data_ptr(), d2.data_ptr(),
+              nn.data_ptr() if nn is not None else None, _stream())
+    return (d2, nn) if return_idx else d2
+
+
 def estimate_normals(xyz, knn=30, search=None, index=None):
     """open3d estimate_normals(KDTreeSearchParamKNN(knn)) (eval.py:59-60): unoriented PCA normals (B,N,3).  search="grid": the
     neighbours come from a GridIndex of xyz (``index``: one the caller already built over xyz), same normals."""
@@ -668,6 +696,43 @@ class _ChamferFn(torch.autograd.Function):
         return gx, gy
 
 
+def _chamfer_n(x, y, p, q, per_cloud):
+    """Both nn_dist_n passes and pccx_chamfer_mean_n: (value (), per-cloud brackets (B,) or None, nxy, nyx)."""
+    B, P, Q = x.shape[0], x.shape[1], y.shape[1]
+    dxy, nxy = nn_dist_n(x, y, p, q, return_idx=True)
+    dyx, nyx = nn_dist_n(y, x, q, p, return_idx=True)
+    out = torch.empty((), device=x.device, dtype=torch.float32)
+    per = torch.empty(B, device=x.device, dtype=torch.float32) if per_cloud else None
+    _lib.call("pccx_chamfer_mean_n", dxy.data_ptr(), dyx.data_ptr(), B, P, p.data_ptr(), Q, q.data_ptr(), out.data_ptr(),
+              per.data_ptr() if per is not None else None, _stream())
+    return out, per, nxy, nyx
+
+
+class _ChamferNFn(torch.autograd.Function):
+    """_ChamferFn for ragged batches: p, q (B,) int32 on the device are pytorch3d's x_lengths / y_lengths.  forward = two nn_dist_n
+    launches and pccx_chamfer_mean_n, backward = pccx_chamfer_grad_n with the argmins saved from the forward; the rows of the
+    gradients behind the lengths are exact zeros."""
+
+    @staticmethod
+    def forward(ctx, x, y, p, q):
+        out, _, nxy, nyx = _chamfer_n(x, y, p, q, False)
+        ctx.save_for_backward(x, y, p, q, nxy, nyx)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, p, q, nxy, nyx = ctx.saved_tensors
+        gd = g.detach().to(torch.float32).reshape(1).contiguous()        # stays on the device: no sync inside backward
+        if zeros_hook is not None:          # inside a training step: cleared by the step's arena, accumulated into (flags & 4)
+            gx, gy = zeros_hook(tuple(x.shape), torch.float32, x.device)[0], zeros_hook(tuple(y.shape), torch.float32, y.device)[0]
+            flags = 4
+        else:
+            gx, gy, flags = torch.empty_like(x), torch.empty_like(y), 0
+        _lib.call("pccx_chamfer_grad_n", x.data_ptr(), x.shape[0], x.shape[1], p.data_ptr(), y.data_ptr(), y.shape[1], q.data_ptr(),
+                  nxy.data_ptr(), nyx.data_ptr(), gd.data_ptr(), gx.data_ptr(), gy.data_ptr(), flags, _stream())
+        return gx, gy, None, None
+
+
 class _STERound(torch.autograd.Function):
     """AE.STEQuantize (AE.py:72-85): forward x.round() (pccx_round: round half to even, as torch.round), backward the
     incoming gradient unchanged (straight-through estimator)."""
@@ -692,10 +757,31 @@ def ste_round(x):
     return _STERound.apply(x)
 
 
-def chamfer_distance(x, y, batch_reduction="mean"):
+def chamfer_distance(x, y, x_lengths=None, y_lengths=None, batch_reduction="mean"):
     """pytorch3d.loss.chamfer_distance defaults (AE.py:67, eval.py:204): squared distances,
     point mean, both directions summed; returns (value, None).  Differentiable w.r.t. x and y for
-    batch_reduction="mean" (the loss of AE.py:57-70 / pppe_pcd_ae.py:817-838)."""
+    batch_reduction="mean" (the loss of AE.py:57-70 / pppe_pcd_ae.py:817-838).
+
+    x_lengths / y_lengths (pytorch3d's names and pytorch3d's positions, third and fourth: batch_reduction is passed by keyword, as
+    every caller in the tree does; either alone means the other cloud is full): cloud b is the first x_lengths[b] rows of
+    x (B,P_max,3) and the first y_lengths[b] of y, each point mean is over those rows, and what lies behind them is never read.  Host
+    sequences are checked against [1, P_max] before any launch; device tensors are read by the kernels only.  Differentiable for
+    "mean" (gradient rows behind the lengths are exact zeros); batch_reduction=None returns the (B,) per-cloud values.  The
+    deterministic mode has no ragged form (pccx_chamfer_grad_det is dense): inside a deterministic step this raises."""
+    if x_lengths is not None or y_lengths is not None:
+        if deterministic_hook is not None and deterministic_hook():
+            raise _lib.PccxError("chamfer_distance: x_lengths / y_lengths cannot be combined with the deterministic mode -- the ordered "
+                                 "scatter of pccx_chamfer_grad_det is dense only; run the step with deterministic=False, or pad to one size")
+        if batch_reduction not in ("mean", "sum", None):
+            raise _lib.PccxError(f"chamfer_distance: batch_reduction must be 'mean', 'sum' or None, got {batch_reduction!r}")
+        x, y = _f32c(x, "chamfer.x"), _f32c(y, "chamfer.y")
+        B, P, Q = x.shape[0], x.shape[1], y.shape[1]
+        p = checked_counts(x_lengths if x_lengths is not None else [P] * B, B, P, x.device, "chamfer.x_lengths")
+        q = checked_counts(y_lengths if y_lengths is not None else [Q] * B, B, Q, x.device, "chamfer.y_lengths")
+        if batch_reduction == "mean" and (x.requires_grad or y.requires_grad):
+            return _ChamferNFn.apply(x, y, p, q), None
+        out, per, _, _ = _chamfer_n(x.detach(), y.detach(), p, q, batch_reduction != "mean")
+        return (out if batch_reduction == "mean" else per.double().sum().float() if batch_reduction == "sum" else per), None
     if batch_reduction == "mean" and (x.requires_grad or y.requires_grad):
         return _ChamferFn.apply(_f32c(x, "chamfer.x"), _f32c(y, "chamfer.y")), None
     dxy, dyx = nn_dist(x, y), nn_dist(y, x)

@@ -20,6 +20,8 @@ AE.py has no BatchNorm on this path (bn=False at AE.py:16-27).  ``--model PPPF-A
 octree_mode="full" (select_patches, forward_loss, IpdaeTrainer; train.py --octree-mode full) replaces :184 by the intended decode and
 normalises every cloud by its own box: the trainer then selects, bit for bit, the patches ``compress.py --octree-mode full`` codes, for
 any S = N * ALPHA / K up to 1024 (clouds above 32768 points through the grid's wide-K walk, as the codec), and IpdaeTrainer.validate runs the current weights through that codec.
+Clouds of different sizes in one step (train.py --ragged; "full" mode only): select_patches_ragged, forward_loss_ragged,
+IpdaeTrainer.step_ragged / graphed_ragged / validate_ragged, the trainer's side of Codec.compress_ragged.
 """
 import torch
 
@@ -201,6 +203,56 @@ def forward_loss(ae, prob, batch_x, starts, lam, S, K, N, N0, octree_mode="refer
     return d + lam * fbpp, fbpp, bpp                                                  # AE.py:68-70
 
 
+def select_patches_ragged(pc, n_dev, S_dev, scale_dev, S_cap, K, starts):
+    """select_patches(octree_mode="full") for clouds of different sizes in one launch sequence: pc (B, N_cap, 3) with cloud b in its
+    first n[b] rows (the rows behind them reach no result), cloud b sampling S[b] <= S_cap centres and scaling its patches by scale[b].
+    It is the selection of Codec.compress_ragged without the duplicate table: every one of the B * S_cap patches is searched, and
+    the patches behind S[b] -- centred on repeats of the cloud's last decoded centre -- are copies of its last real one.
+    -> (x normalised (B,N_cap,3), zeros behind n[b]; rec (B,S_cap,3); patches (B*S_cap,K,3); nbits (B,) int32: the octree stream of
+    every cloud in bits, not their sum).  For every cloud x, the first S[b] centres and the first S[b] patches are bit for bit the pcn,
+    rec_sampled and patches of Codec(octree_mode="full").compress_ragged(keep_extras=True).
+    n_dev, S_dev (B,) int32, scale_dev (B,) float32 and starts (B,) int32 are device buffers: nothing is read back, and a captured
+    step (RaggedGraphedIpdaeStep) changes them between replays."""
+    B = pc.shape[0]
+    x, _, _ = ops.normalize_n(pc, n_dev, margin=0.01)
+    sampled = ops.index_points(x, ops.farthest_point_sample_n(x, n_dev, S_cap, S_dev, starts))
+    enc = ops.octree_encode_n(sampled, S_dev, n_dev, OCTREE_BPP_DICT[K])
+    rec, _ = ops.octree_decode(enc["bytes"], enc["nbytes"], "full", S_cap)            # the centres past S[b] repeat the last one
+    patches = ops.knn_points_n(rec, x, n_dev, K, scale_dev).knn.view(B * S_cap, K, 3)
+    return x, rec, patches, enc["nbits"]
+
+
+def forward_loss_ragged(ae, prob, pc, n_dev, S_dev, scale_dev, starts, lam, S_cap, K):
+    """forward_loss(octree_mode="full") over a ragged batch -> (loss, fbpp, bpp) with the graph of loss recorded.
+
+    The networks run on all B * S_cap patches through ae_forward_train / prob_forward_train unchanged: there is no BatchNorm on this
+    path, a padded patch is a copy of its cloud's last real one, and the probability model's group max over repeats of the last centre
+    is the max over the real ones.  Cloud b's prediction is its first S[b] * k rows; with n_b points, S_b patches and nbits_b octree bits
+      chamfer_b = mean_{i < S_b k} min_j |pred_i - x_j|^2 + mean_{j < n_b} min_i |pred_i - x_j|^2      (ops.chamfer_distance by length)
+      bits_b    = sum_{s < S_b} sum_c -log2 clamp(pmf[b, s, c, sym], 1e-3)                            (padded patches masked out)
+      fb_b = bits_b / n_b,   fbpp_b = fb_b / n_b,   bpp_b = (nbits_b + fb_b) / n_b
+      loss = mean_b chamfer_b + lam * mean_b fbpp_b;   reported fbpp = mean_b fbpp_b, bpp = mean_b bpp_b
+    that is the mean over the clouds of what forward_loss computes for each cloud alone at B = 1.  It keeps the double division of
+    train.py:208-212, so a one-cloud ragged step is the dense step.  For B > 1 clouds of equal size the rate term is B times the dense
+    step's: that one divides by B * N twice, inherited from a script that says its batch size must be 1 (train.py:40)."""
+    B = pc.shape[0]
+    x, rec, patches, nbits = select_patches_ragged(pc, n_dev, S_dev, scale_dev, S_cap, K, starts)
+    patches_pred, _, q = ae_forward_train(ae, patches)                                # :200
+    patches_pred = patches_pred.view(B, S_cap, -1, 3) / scale_dev.view(B, 1, 1, 1)    # :201, every cloud by its own scale
+    pmf = prob_forward_train(prob, rec)                                               # :204
+    sym = (q.detach().view(B, S_cap, ae.d) + ae.L // 2).long().clamp(0, ae.L - 1)     # :205-206
+    p = torch.gather(pmf.reshape(-1, ae.L), 1, sym.reshape(-1, 1)).view(B, S_cap, ae.d)
+    real = torch.arange(S_cap, device=pc.device, dtype=torch.int32).view(1, S_cap) < S_dev.view(B, 1)
+    bits = ((-torch.log2(p.clamp(min=1e-3))).sum(dim=2) * real).sum(dim=1)            # pn_kit.py:439-450 over the cloud's own patches
+    nf = n_dev.to(torch.float32)
+    fb = bits / nf                                                                    # :208
+    bpp = ((nbits.to(torch.float32) + fb) / nf).mean()                                # :211
+    fbpp = (fb / nf).mean()                                                           # :212
+    pc_pred = (patches_pred + rec.view(B, S_cap, 1, 3)).reshape(B, -1, 3)             # :214-216
+    d, _ = ops.chamfer_distance(pc_pred, x, x_lengths=S_dev * int(ae.k), y_lengths=n_dev)
+    return d + lam * fbpp, fbpp, bpp
+
+
 class IpdaeTrainer:
     """The state of train.py's loop for ``--model AE``: the two models, Adam over both (train.py:131-134), the step counter with the
     rate term switched on at rate_loss_enable_step (:218-221) and the learning-rate decay (:250-254)."""
@@ -239,6 +291,87 @@ class IpdaeTrainer:
             self.lr *= self.lr_decay
             self.opt.set_lr(self.lr)
         return dict(loss=float(loss.detach()), fbpp=float(fbpp.detach()), bpp=float(bpp.detach()))
+
+    def ragged_refusal(self, n_points, B, N_cap, S_cap=None):
+        """Why step_ragged / RaggedGraphedIpdaeStep cannot take B clouds of these point counts in a slab of N_cap rows and S_cap
+        patches per cloud: a message naming the limit and the way out, or None.  Host only, before any launch.  The shape rule is the
+        codec's own (codec.ragged_shape_refusal)."""
+        from . import codec
+        if self.octree_mode != "full":
+            return (f"ragged training needs octree_mode='full' (octree_mode='reference' is S = 64 by definition), got "
+                    f"{self.octree_mode!r}: build the trainer with octree_mode='full' (train.py --octree-mode full)")
+        if self.deterministic:
+            return ("ragged training has no deterministic form (the ordered scatter of pccx_chamfer_grad_det is dense only): build the "
+                    "trainer with deterministic=False, or train on one size per step")
+        n = [int(v) for v in n_points]
+        if len(n) != B:
+            return f"{len(n)} point counts for {B} clouds: one count per cloud is expected"
+        why = codec.ragged_shape_refusal(n, self.K, self.ALPHA, N_cap)
+        if why is None and S_cap is not None and max(v * self.ALPHA // self.K for v in n) > S_cap:
+            why = (f"a cloud of {max(n)} points has {max(n) * self.ALPHA // self.K} patches, the step holds S_cap = {S_cap} per cloud: "
+                   f"build it with a larger S_cap, or send such clouds through step_ragged")
+        return why
+
+    def _ragged_tables(self, n_points):
+        """(n, S, scale, plan) of a ragged batch: host tensors (int32, int32, float32) and the codec.ragged_plan they come from"""
+        from . import codec
+        plan = codec.ragged_plan(n_points, self.K, self.ALPHA, self.N0, self.ae.d)
+        return (torch.tensor([int(v) for v in n_points], dtype=torch.int32), torch.tensor(plan.S, dtype=torch.int32),
+                torch.tensor(plan.scale_compress, dtype=torch.float32), plan)
+
+    def step_ragged(self, pc, n_points, starts, S_cap=None):
+        """step for clouds of different sizes: pc (B, N_cap, 3) on the device with cloud b in its first n_points[b] rows (codec.pad_clouds),
+        n_points a host sequence, starts the FPS start index per cloud in [0, n_b).  S_cap: the patches every cloud is padded to
+        (default 16 * ceil(max S_b / 16), codec.ragged_plan's S_pad); a cloud's figures do not depend on it, nor on N_cap or the
+        batch.  The loss is forward_loss_ragged's.  Same bookkeeping as step.  Refused with PccxError before any launch: what
+        ragged_refusal names."""
+        if pc.dim() != 3 or pc.shape[2] != 3:
+            raise _lib.PccxError(f"train_ipdae: a ragged batch must be (B, N_cap, 3), got {tuple(pc.shape)}")
+        B, N_cap = int(pc.shape[0]), int(pc.shape[1])
+        why = self.ragged_refusal(n_points, B, N_cap, S_cap)
+        if why:
+            raise _lib.PccxError("train_ipdae: step_ragged: " + why)
+        n, S, scale, plan = self._ragged_tables(n_points)
+        S_cap = plan.S_pad if S_cap is None else int(S_cap)
+        dev = pc.device
+        n, S, scale = n.to(dev), S.to(dev), scale.to(dev)
+        starts = ops.counts(starts, B, dev, "step_ragged.starts")
+        lam = 0.0 if self.global_step < self.rate_loss_enable_step else self.lamda    # :218-221
+        with train.step_scope(dev, None, self.autocast, self.opt.params) as forward_done:
+            loss, fbpp, bpp = forward_loss_ragged(self.ae, self.prob, pc, n, S, scale, starts, lam, S_cap, self.K)
+            forward_done()
+            loss.backward()                                                           # :229
+            self.opt.step(max_norm=None)                                              # :230
+        self.global_step += 1                                                         # :236
+        if self.global_step % self.lr_decay_steps == 0:                               # :250-254
+            self.lr *= self.lr_decay
+            self.opt.set_lr(self.lr)
+        return dict(loss=float(loss.detach()), fbpp=float(fbpp.detach()), bpp=float(bpp.detach()))
+
+    def graphed_ragged(self, N_cap, S_cap, B, pc, n_points, starts, warmup=2, keep_graph=False):
+        """-> RaggedGraphedIpdaeStep at the capacities (N_cap points, S_cap patches, B clouds); the warm-up iterations are real steps
+        on (pc, n_points, starts)"""
+        return RaggedGraphedIpdaeStep(self, N_cap, S_cap, B, pc, n_points, starts, warmup, keep_graph)
+
+    def validate_ragged(self, clouds, starts, **codec_kw):
+        """validate for clouds of different sizes: clouds a list of (n_b, 3) device tensors, starts the FPS start index per cloud ->
+        dict(bpp = the mean true rate of compress_ragged's three files, d1_psnr = the mean over the clouds of codec.d1_psnr on the
+        unpadded pair (cloud, its decompress_ragged), n = B).  Repacks first, as validate explains."""
+        from . import codec
+        comp, outs = self.validation_pass_ragged(clouds, starts, **codec_kw)
+        psnr = [float(codec.d1_psnr(c[None].to(torch.float32).contiguous(), o[None].contiguous())[0]) for c, o in zip(clouds, outs)]
+        return dict(bpp=float(comp.bpp().mean()), d1_psnr=sum(psnr) / len(psnr), n=len(clouds))
+
+    def validation_pass_ragged(self, clouds, starts, **codec_kw):
+        """validate_ragged's codec run itself -> (the Compressed, the list of decompressed clouds (S_b*k, 3)); repacks first"""
+        from . import codec
+        pc, n = codec.pad_clouds(clouds)
+        with torch.no_grad():
+            self.ae.pack(pc.device)
+            self.prob.pack(pc.device)
+            cd = codec.Codec(self.ae, self.prob, self.K, self.ALPHA, self.N0, octree_mode=self.octree_mode, **codec_kw)
+            comp = cd.compress_ragged(pc, n, starts)
+            return comp, cd.decompress_ragged(comp, [v * self.ALPHA // self.K for v in n])
 
     def validate(self, clouds, starts, **codec_kw):
         """The current weights through the real codec: clouds (B, N, 3) on the device, starts the FPS start index per cloud ->
@@ -319,6 +452,76 @@ class GraphedIpdaeStep:
             self.x.copy_(batch_x)
         if starts is not None:
             self.starts.copy_(torch.as_tensor(starts).to(self.x.device, torch.int32))
+        self._set_lam()
+        self.graph.replay()
+        self.tr.opt.t += 1
+        self._advance()
+        keys = ("loss", "fbpp", "bpp")
+        return {k: float(v) for k, v in zip(keys, self.out)} if sync else dict(zip(keys, self.out))
+
+
+class RaggedGraphedIpdaeStep:
+    """IpdaeTrainer.step_ragged captured ONCE at capacities (B clouds of up to N_cap points and S_cap patches) and replayed on any batch
+    with n_b <= N_cap and S_b <= S_cap.  The batch, the per-cloud tables n / S / scale, the start indices, lambda and Adam's scalars
+    live in buffers the graph reads; shapes, grids and S_cap are fixed at construction, so every replay does the matrix work of
+    B * S_cap patches whatever the clouds hold.  Built on train.capture_step / step_scope as GraphedIpdaeStep is."""
+
+    def __init__(self, trainer, N_cap, S_cap, B, pc, n_points, starts, warmup=2, keep_graph=False):
+        tr = self.tr = trainer
+        self.N_cap, self.S_cap, self.B = int(N_cap), int(S_cap), int(B)
+        why = tr.ragged_refusal(n_points, self.B, self.N_cap, self.S_cap)
+        if why:
+            raise _lib.PccxError("train_ipdae: graphed_ragged: " + why)
+        dev = pc.device
+        self.arena = train.StepArena()
+        tr.opt.make_capturable(dev)
+        self.x = torch.zeros(self.B, self.N_cap, 3, device=dev, dtype=torch.float32)
+        self.n = torch.zeros(self.B, device=dev, dtype=torch.int32)
+        self.S = torch.zeros(self.B, device=dev, dtype=torch.int32)
+        self.scale = torch.ones(self.B, device=dev, dtype=torch.float32)
+        self.starts = torch.zeros(self.B, device=dev, dtype=torch.int32)
+        self.lam = torch.zeros((), device=dev, dtype=torch.float32)
+        self.warm_out = None
+        self._load(pc, n_points, starts)
+
+        def warm():
+            self._set_lam()
+            self.warm_out = self._body()                             # (loss, fbpp, bpp) of the last warm-up iteration, device scalars
+            self._advance()
+        self.graph, self.out, self._grads, _, _ = train.capture_step(dev, tr.opt, warmup, warm, self._body, keep_graph=keep_graph)
+
+    def _load(self, pc, n_points, starts):
+        """a batch into the buffers the graph reads; refused on the host, before any copy, as step_ragged refuses"""
+        tr = self.tr
+        if pc.dim() != 3 or pc.shape[0] != self.B or pc.shape[1] > self.N_cap or pc.shape[2] != 3:
+            raise _lib.PccxError(f"train_ipdae: this captured step takes ({self.B}, <= {self.N_cap}, 3), got {tuple(pc.shape)}")
+        why = tr.ragged_refusal(n_points, self.B, int(pc.shape[1]), self.S_cap)
+        if why:
+            raise _lib.PccxError("train_ipdae: graphed_ragged: " + why)
+        n, S, scale, _ = tr._ragged_tables(n_points)
+        self.x[:, :pc.shape[1]].copy_(pc)
+        self.n.copy_(n)
+        self.S.copy_(S)
+        self.scale.copy_(scale)
+        self.starts.copy_(torch.as_tensor(starts).to(self.x.device, torch.int32))
+
+    _set_lam = GraphedIpdaeStep._set_lam
+    _advance = GraphedIpdaeStep._advance
+
+    def _body(self):
+        tr = self.tr
+        with train.step_scope(self.x.device, self.arena, tr.autocast, tr.opt.params) as forward_done:
+            loss, fbpp, bpp = forward_loss_ragged(tr.ae, tr.prob, self.x, self.n, self.S, self.scale, self.starts, self.lam, self.S_cap, tr.K)
+            forward_done()
+            loss.backward()
+            tr.opt.step(max_norm=None)
+        return loss.detach(), fbpp.detach(), bpp.detach()
+
+    def __call__(self, pc=None, n_points=None, starts=None, sync=True):
+        """one iteration on (pc, n_points, starts) (None = the buffers' current content) -> dict of floats, or of device scalars
+        (sync=False)"""
+        if pc is not None:
+            self._load(pc, n_points, starts)
         self._set_lam()
         self.graph.replay()
         self.tr.opt.t += 1
