@@ -1020,6 +1020,22 @@ PCCX_API size_t pccx_chamfer_grad_det_workspace_ints(int B, int P, int Q);
 PCCX_API int pccx_chamfer_grad_det(const float *X, int B, int P, const float *Y, int Q, const int32_t *nn_xy, const int32_t *nn_yx,
                                    const float *grad_out_dev, float *gX, float *gY, float *ws_floats, int32_t *ws_ints, void *stream);
 
+/* ---- training crops (csrc/crop.hip) --------------------------------------------------------------------------------------
+ * Stands in for the reference's loader (train.py:110-123: every file holds exactly N points and is one sample); the reference itself
+ * has no crop.  The store: every training cloud concatenated, points (M_total,3) f32, with offsets (F+1) int64 (cloud c = rows
+ * offsets[c]..offsets[c+1]).  Slot b cuts from cloud cloud[b] the n[b] points with the smallest keys
+ * (__float_as_uint(squared distance to point seed[b] of that cloud), index) -- ties in distance go to the lower index -- and writes
+ * them in ascending index: out (B,N_cap,3) f32 with the rows behind n[b] NaN (codec.pad_clouds' convention), out_idx (B,N_cap) int32
+ * with -1 behind n[b] (may be NULL).  cloud / seed / n: (B) int32 on the device, never read back, clamped where they are read (cloud
+ * into [0,F-1], seed into [0,M-1], n into [1,min(N_cap,M)]); M_max: the largest cloud's point count, it sizes the grids together with B.
+ * Limits, checked before any launch: M_max <= 16777216, N_cap <= 131072, B <= 1024.  Integer atomics only: the result does not depend
+ * on scheduling.  No memset / memcpy: capturable, and every grid depends on (B, M_max) alone, so a captured call replays on other
+ * tables.  workspace: pccx_crop_nearest_workspace_bytes(B, M_max) bytes, 8-byte aligned; its content on entry does not matter. */
+PCCX_API size_t pccx_crop_nearest_workspace_bytes(int B, int M_max);
+PCCX_API int pccx_crop_nearest(const float *points, int64_t M_total, const int64_t *offsets, int F, const int32_t *cloud,
+                               const int32_t *seed, const int32_t *n, int B, int N_cap, int M_max, float *out, int32_t *out_idx,
+                               void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

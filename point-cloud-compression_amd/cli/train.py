@@ -5,7 +5,7 @@ train.py:103-108) and the reference's state_dict keys, so compress.py / decompre
 path's own: --octree-mode (the spelling of compress.py / decompress.py; 'full' trains on the centres those decode in that mode, the
 mode is not stored in the .pkl files) and --val_glob (the real codec's bpp and D1 on held-out files at every step window).
 --ragged (with --octree-mode full) trains on files of different point counts, several sizes in one step: the trainer's side of
-``compress.py --ragged``."""
+``compress.py --ragged``.  --crop trains either step on compact crops cut on the GPU from files of any size (whole rooms)."""
 import argparse
 import os
 from glob import glob
@@ -14,7 +14,7 @@ import numpy as np
 
 import _common  # noqa: F401
 import torch
-from pccx import _lib, codec, models, plyio, train_ipdae
+from pccx import _lib, codec, models, ops, plyio, train_ipdae
 
 torch.manual_seed(11)                                                                  # train.py:17-19
 np.random.seed(11)
@@ -50,6 +50,13 @@ parser.add_argument('--deterministic', action='store_true', help='every reductio
 parser.add_argument('--ragged', action='store_true',
                     help="files of different point counts, mixed in one step (needs --octree-mode full; --N is ignored): every file must hold "
                          "K..32768 points and S = n*ALPHA//K patches inside the range compress.py --ragged takes; --val_glob files likewise.")
+parser.add_argument('--crop', action='store_true',
+                    help="files of any size >= --N (with --ragged: >= --K): every step trains on --batch_size compact crops cut on the GPU, each the "
+                         "points nearest to a seed point drawn uniformly over all points of all files (--N points; with --ragged a size drawn "
+                         "in --crop-min..--crop-max).  --val_glob files are cropped once, around their first point.")
+parser.add_argument('--crop-min', type=int, default=None, help='--crop --ragged: the smallest crop, in points.')
+parser.add_argument('--crop-max', type=int, default=None, help='--crop --ragged: the largest crop, in points (the step is built for it).')
+parser.add_argument('--crop-seed', type=int, default=11, help='--crop: seed of the generator the seed points, crop sizes and FPS starts are drawn from.')
 
 
 VAL_CHUNK = 16                         # clouds per codec batch of a --val_glob pass: the validation set's size does not bound the codec's buffers
@@ -179,6 +186,135 @@ def main_ragged(args):
     dump_checkpoints(tr, args.model_save_folder)
 
 
+def read_crop_store(pattern, flag, least, what):
+    """the files of a glob for --crop, read once -> (files, clouds, refusals: one line per file below `least` points)"""
+    files = sorted(glob(pattern, recursive=True))
+    clouds = [plyio.read_point_cloud(f).astype(np.float32) for f in files]
+    refused = [f"{flag} {f}: {c.shape[0]} points, below {what} = {least}" for f, c in zip(files, clouds) if c.shape[0] < least]
+    return files, clouds, refused if files else [f"{flag} {pattern}: no file matches"]
+
+
+def main_crop(args):
+    """--crop: the loops of main() and main_ragged() over crops instead of files.  The files, of any size, live in HBM one behind the
+    other (codec.pack_clouds); a step takes --batch_size crops cut in front of it on the same stream (train_ipdae.CropSampler), --N
+    points each, or with --ragged a size drawn in --crop-min..--crop-max, and is the dense / ragged step as it stands, captured or
+    eager.  Everything that can be refused is refused before the GPU check."""
+    K, ragged = args.K, args.ragged
+    args.k = K // args.ALPHA
+    if not args.crop:
+        raise SystemExit("--crop-min / --crop-max size the crops of --crop --ragged: they need --crop")
+    if not ragged and (args.crop_min is not None or args.crop_max is not None):
+        raise SystemExit("--crop-min / --crop-max need --ragged (with --octree-mode full): without it every crop holds exactly --N points")
+    if ragged:
+        if args.crop_min is None or args.crop_max is None or not 1 <= args.crop_min <= args.crop_max:
+            raise SystemExit(f"--crop --ragged needs --crop-min <= --crop-max, got {args.crop_min} and {args.crop_max}")
+        why = codec.ragged_shape_refusal([args.crop_min, args.crop_max], K, args.ALPHA)
+        if why:
+            raise SystemExit(f"--crop-min {args.crop_min} --crop-max {args.crop_max}: the crops are outside what a ragged batch takes: {why}")
+        n_lo, n_hi, least, what = args.crop_min, args.crop_max, K, "--K"
+    else:
+        n_lo = n_hi = least = args.N
+        what = "--N"
+        args.S = args.N * args.ALPHA // K
+    n_mean = (n_lo + n_hi) // 2
+    try:                                                                               # --K (and S), before anything is read or allocated
+        if ragged:
+            train_ipdae.check_selection(args.ALPHA, K, args.octree_mode)
+        elif args.octree_mode == 'full':
+            train_ipdae.check_selection(args.S, K, args.octree_mode)
+    except _lib.PccxError as e:
+        raise SystemExit(str(e))
+    files, clouds, refused = read_crop_store(args.train_glob, "--train_glob", least, what)
+    val_files, val_clouds = [], []
+    if args.val_glob:
+        val_files, val_clouds, more = read_crop_store(args.val_glob, "--val_glob", least, what)
+        refused += more
+    big = [f"{f}: {c.shape[0]} points, a crop is cut from at most {ops.CROP_MAX_M} per file" for f, c in zip(files + val_files, clouds + val_clouds)
+           if c.shape[0] > ops.CROP_MAX_M]
+    if refused or big:
+        raise SystemExit("--crop: nothing is dropped silently; these files cannot be cropped:\n" + "\n".join(refused + big))
+    if not torch.cuda.is_available():
+        raise SystemExit("pccx needs a ROCm GPU: there is no CPU path")
+    print(f"Training {args.model} on {args.device}")
+    if ragged:
+        print(f"autocast={args.autocast}, eager={args.eager}")
+    else:
+        print(f"N={args.N}, K={K}, S={args.S}, d={args.d}, L={args.L}")
+        print(f"deterministic={args.deterministic}, autocast={args.autocast}, eager={args.eager}")
+    if args.octree_mode == 'full':
+        print("octree_mode=full: these checkpoints are for compress.py/decompress.py --octree-mode full")
+    os.makedirs(args.model_save_folder, exist_ok=True)
+    gen = torch.Generator()
+    gen.manual_seed(args.crop_seed)
+    points, offsets, sizes = codec.pack_clouds(clouds, device=args.device)            # the whole training set lives in HBM
+    sampler = train_ipdae.CropSampler(points, offsets, sizes, args.batch_size, n_hi, gen)
+    N_cap, S_cap = n_hi, codec.ragged_plan([n_hi], K, args.ALPHA, args.N0, args.d).S_pad
+    per_epoch = -(-sampler.M_total // (args.batch_size * n_mean))
+    print(f"--crop: {len(files)} files of {min(sizes)}..{max(sizes)} points, {sampler.M_total} in all; crops of "
+          f"{n_lo if n_lo == n_hi else f'{n_lo}..{n_hi}'} points, {per_epoch} steps per epoch" + (f", N_cap={N_cap}, S_cap={S_cap}" if ragged else ""))
+    val = None
+    if val_files:                                                                      # one fixed crop per file, cut once: the same clouds at every window
+        vp, vo, vs = codec.pack_clouds(val_clouds, device=args.device)
+        cuts = [ops.crop_nearest(vp, vo, list(range(i, min(i + ops.CROP_MAX_B, len(vs)))), [0] * len(vs[i:i + ops.CROP_MAX_B]),
+                                 [min(n_hi, m) for m in vs[i:i + ops.CROP_MAX_B]], n_hi, sizes=vs) for i in range(0, len(vs), ops.CROP_MAX_B)]
+        val = torch.cat(cuts)
+        if ragged:
+            val = [v[:min(n_hi, m)].contiguous() for v, m in zip(val, vs)]
+            print(f"Loaded {len(val)} validation crops of {min(len(c) for c in val)}..{max(len(c) for c in val)} points")
+        else:
+            print(f"Loaded {tuple(val.shape)} validation points")
+    ae = models.AE(K=K, k=args.k, d=args.d, L=args.L).to(args.device)
+    prob = models.ConditionalProbabilityModel(args.L, args.d).to(args.device)
+    tr = train_ipdae.IpdaeTrainer(ae, prob, N=N_cap, N0=args.N0, ALPHA=args.ALPHA, K=K, lr=args.lr, lamda=args.lamda,
+                                  rate_loss_enable_step=args.rate_loss_enable_step, lr_decay=args.lr_decay,
+                                  lr_decay_steps=args.lr_decay_steps, autocast=args.autocast, deterministic=args.deterministic,
+                                  octree_mode=args.octree_mode)
+    if not args.reset:
+        tr.global_step = load_checkpoints(tr, args.model_save_folder)
+        print(f"Resuming from step {tr.global_step}")
+    else:
+        print("Resetting training from scratch.")
+    if val is None:
+        validate = None
+    elif ragged:
+        validate = lambda i: tr.validate_ragged(val[i:i + VAL_CHUNK], [0] * len(val[i:i + VAL_CHUNK]))
+    else:
+        validate = lambda i: tr.validate(val[i:i + VAL_CHUNK], torch.zeros(len(val[i:i + VAL_CHUNK]), dtype=torch.long))
+    losses, fbpps, bpps = [], [], []
+    graph = None                       # the step as one hipGraph, captured on the first batch; the crop runs in front of every replay
+    for epoch in range(9999):
+        for _ in range(per_epoch):
+            if tr.global_step > args.max_steps:
+                break
+            want = torch.randint(n_lo, n_hi + 1, (args.batch_size,), generator=gen).tolist() if ragged else n_hi
+            batch, n, starts = sampler.draw(want)                                      # on the current stream, into the sampler's buffer
+            lr_before = tr.lr
+            if ragged:
+                if args.eager:
+                    out = tr.step_ragged(batch, n, starts, S_cap=S_cap)
+                elif graph is None:
+                    graph = tr.graphed_ragged(N_cap, S_cap, args.batch_size, batch, n, starts, warmup=1)
+                    out = {k_: float(v) for k_, v in zip(("loss", "fbpp", "bpp"), graph.warm_out)}
+                else:
+                    out = graph(batch, n, starts)
+            elif args.eager:
+                out = tr.step(batch, starts)
+            elif graph is None:
+                graph = tr.graphed(batch, starts, warmup=1)                            # the warm-up iteration IS this step
+                out = {k_: float(v) for k_, v in zip(("loss", "fbpp", "bpp"), graph.warm_out)}
+            else:
+                out = graph(batch, starts)
+            losses.append(out["loss"]), fbpps.append(out["fbpp"]), bpps.append(out["bpp"])
+            if tr.global_step % args.step_window == 0:
+                window_report(tr, args, epoch, losses, fbpps, bpps, validate, 0 if val is None else len(val))
+                losses, fbpps, bpps = [], [], []
+            if tr.lr != lr_before:
+                print(f"LR decayed to {tr.lr} at step {tr.global_step}")
+        if tr.global_step > args.max_steps:
+            break
+    dump_checkpoints(tr, args.model_save_folder)
+
+
 def main():
     args = parser.parse_args()
     if args.model != 'AE':
@@ -187,6 +323,8 @@ def main():
     if args.ragged and (args.octree_mode != 'full' or args.deterministic):
         raise SystemExit("--ragged needs --octree-mode full (octree_mode 'reference' is S = 64 by definition) and excludes --deterministic "
                          "(the ordered Chamfer scatter is dense only)")
+    if args.crop or args.crop_min is not None or args.crop_max is not None:
+        return main_crop(args)
     if not torch.cuda.is_available():
         raise SystemExit("pccx needs a ROCm GPU: there is no CPU path")
     if args.ragged:

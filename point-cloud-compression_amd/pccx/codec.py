@@ -283,6 +283,23 @@ def pad_clouds(clouds, device=None):
     return pc, n
 
 
+def pack_clouds(clouds, device=None):
+    """pad_clouds' sibling for a training set that does not fit a padded slab: a list of (n_b, 3) arrays or tensors -> (points
+    (M_total, 3) f32 = the clouds one behind the other, offsets (F+1,) int64 on the same device with cloud c in rows
+    offsets[c]..offsets[c+1], sizes = the host list of the n_b): the store ops.crop_nearest / train_ipdae.CropSampler cut from."""
+    if not len(clouds):
+        raise ValueError("pack_clouds: at least one cloud is expected")
+    ts = [c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c, dtype=np.float32)) for c in clouds]
+    for b, t in enumerate(ts):
+        if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+            raise ValueError(f"pack_clouds: cloud {b} must be (n, 3) with n >= 1, got {tuple(t.shape)}")
+    sizes = [int(t.shape[0]) for t in ts]
+    device = device if device is not None else ts[0].device
+    points = torch.cat([t.to(device=device, dtype=torch.float32) for t in ts]).contiguous()
+    offsets = torch.tensor([0] + list(np.cumsum(sizes)), dtype=torch.int64).to(device)
+    return points, offsets, sizes
+
+
 def _check_patches(ae, name, G, unit):
     if G is None:
         return

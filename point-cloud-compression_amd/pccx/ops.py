@@ -605,6 +605,92 @@ def checked_counts(v, B, cap, device, name):
     return counts(v, B, device, name)
 
 
+CROP_MAX_M, CROP_MAX_NCAP, CROP_MAX_B = 1 << 24, 131072, 1024       # csrc/crop.hip: points per cloud, points per crop, crops per call
+
+
+def crop_sizes(offsets, name="crop_nearest.offsets"):
+    """The point count of every cloud of a store from its (F+1,) int64 offset table (codec.pack_clouds), on the host -- ONE read-back
+    when the table lives on the device: callers that crop every step keep the list (CropSampler does)."""
+    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 2:
+        got = f"{tuple(offsets.shape)} {offsets.dtype}" if isinstance(offsets, torch.Tensor) else type(offsets).__name__
+        raise _lib.PccxError(f"{name}: an (F+1,) int64 tensor with F >= 1 is expected (codec.pack_clouds), got {got}")
+    o = offsets.tolist()
+    return [b - a for a, b in zip(o[:-1], o[1:])]
+
+
+def crop_nearest(points, offsets, cloud, seed, n, N_cap, return_idx=False, workspace=None, sizes=None, out=None, out_idx=None):
+    """Nearest-n crops of a store of clouds (pccx_crop_nearest, csrc/crop.hip): points (M_total,3) f32 and offsets (F+1,) int64 as
+    codec.pack_clouds makes them; slot b keeps, of cloud cloud[b], the n[b] points with the smallest keys (bits of the squared distance
+    to that cloud's point seed[b], index) in ascending index.  -> out (B,N_cap,3), rows behind n[b] NaN [, idx (B,N_cap) int32, -1
+    behind n[b]].  cloud / seed / n: host sequences, range-checked here before any launch, or device int32 tensors, taken as they are
+    and clamped where the kernels read them (never read back).  sizes: the host list of point counts (pack_clouds' third result); None
+    reads it from offsets, one read-back.  workspace: a uint8 device tensor of at least pccx_crop_nearest_workspace_bytes(B,
+    max(sizes)) bytes whose content does not matter (default: allocated here).  out / out_idx: buffers of the result's shapes to write
+    into (default: allocated here).  With sizes given the call only enqueues kernels on the current stream: it can be captured, and a
+    captured call replays on other table contents."""
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+        raise _lib.PccxError(f"crop_nearest.points: (M_total, 3) with M_total >= 1 is expected, got "
+                             f"{tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__}")
+    if points.dtype != torch.float32:
+        raise _lib.PccxError(f"crop_nearest.points: expected float32, got {points.dtype}")
+    sizes = crop_sizes(offsets) if sizes is None else [int(v) for v in sizes]
+    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or tuple(offsets.shape) != (len(sizes) + 1,):
+        raise _lib.PccxError(f"crop_nearest.offsets: an ({len(sizes) + 1},) int64 tensor is expected for {len(sizes)} clouds")
+    F, M_total, M_max = len(sizes), int(points.shape[0]), max(sizes)
+    if min(sizes) < 1 or sum(sizes) != M_total:
+        raise _lib.PccxError(f"crop_nearest: the store holds {M_total} points, its {F} clouds {sum(sizes)} (every cloud needs at least one)")
+    if M_max > CROP_MAX_M:
+        raise _lib.PccxError(f"crop_nearest: a cloud of {M_max} points; a crop is cut from at most CROP_MAX_M = {CROP_MAX_M} points per cloud")
+    N_cap = int(N_cap)
+    if not 1 <= N_cap <= CROP_MAX_NCAP:
+        raise _lib.PccxError(f"crop_nearest: N_cap={N_cap}; a crop holds 1..CROP_MAX_NCAP = {CROP_MAX_NCAP} points")
+    B = int(cloud.shape[0]) if isinstance(cloud, torch.Tensor) and cloud.dim() == 1 else len(cloud)
+    if not 1 <= B <= CROP_MAX_B:
+        raise _lib.PccxError(f"crop_nearest: {B} crops; one call cuts 1..CROP_MAX_B = {CROP_MAX_B}")
+    host = [None if isinstance(v, torch.Tensor) and v.is_cuda else [int(x) for x in (v.tolist() if isinstance(v, torch.Tensor) else v)]
+            for v in (cloud, seed, n)]
+    for name, v in zip(("cloud", "seed", "n"), host):
+        if v is not None and len(v) != B:
+            raise _lib.PccxError(f"crop_nearest.{name}: one int per crop is expected, got {len(v)} for {B} crops")
+    if host[0] is not None:
+        bad = [(b, c) for b, c in enumerate(host[0]) if not 0 <= c < F]
+        if bad:
+            raise _lib.PccxError(f"crop_nearest.cloud: every cloud index must lie in [0, {F - 1}], got " + ", ".join(f"{c} for crop {b}" for b, c in bad[:4]))
+    m_of = [sizes[c] for c in host[0]] if host[0] is not None else [M_max] * B        # device cloud table: the loosest bound
+    if host[1] is not None:
+        bad = [(b, s) for b, s in enumerate(host[1]) if not 0 <= s < m_of[b]]
+        if bad:
+            raise _lib.PccxError("crop_nearest.seed: a seed index must lie inside its cloud, got " +
+                                 ", ".join(f"{s} for crop {b} (cloud of {m_of[b]} points)" for b, s in bad[:4]))
+    if host[2] is not None:
+        bad = [(b, v) for b, v in enumerate(host[2]) if not 1 <= v <= min(N_cap, m_of[b])]
+        if bad:
+            raise _lib.PccxError("crop_nearest.n: every count must lie in [1, min(N_cap, its cloud's size)], got " +
+                                 ", ".join(f"{v} for crop {b} (N_cap={N_cap}, cloud of {m_of[b]} points)" for b, v in bad[:4]))
+    points = _f32c(points, "crop_nearest.points")
+    dev = points.device
+    if not offsets.is_cuda:
+        raise _lib.PccxError("crop_nearest.offsets: expected a tensor on the GPU (pccx has no CPU fallback)")
+    offsets = offsets.contiguous()
+    cloud_t = counts(cloud if host[0] is None else host[0], B, dev, "crop_nearest.cloud")
+    seed_t = counts(seed if host[1] is None else host[1], B, dev, "crop_nearest.seed")
+    n_t = counts(n, B, dev, "crop_nearest.n") if host[2] is None else checked_counts(host[2], B, N_cap, dev, "crop_nearest.n")
+    need = int(_lib.load().pccx_crop_nearest_workspace_bytes(B, M_max))
+    if workspace is None:
+        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+    elif (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.dtype != torch.uint8 or not workspace.is_contiguous()
+          or workspace.numel() < need or workspace.data_ptr() % 8):
+        raise _lib.PccxError(f"crop_nearest.workspace: a contiguous, 8-byte aligned uint8 device tensor of at least {need} bytes is expected")
+    for name, t, shape, dtype in (("out", out, (B, N_cap, 3), torch.float32), ("out_idx", out_idx, (B, N_cap), torch.int32)):
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise _lib.PccxError(f"crop_nearest.{name}: a contiguous {shape} {dtype} device tensor is expected")
+    out = torch.empty(B, N_cap, 3, device=dev, dtype=torch.float32) if out is None else out
+    idx = out_idx if out_idx is not None else torch.empty(B, N_cap, device=dev, dtype=torch.int32) if return_idx else None
+    _lib.call("pccx_crop_nearest", points.data_ptr(), M_total, offsets.data_ptr(), F, cloud_t.data_ptr(), seed_t.data_ptr(), n_t.data_ptr(),
+              B, N_cap, M_max, out.data_ptr(), idx.data_ptr() if idx is not None else None, workspace.data_ptr(), _stream())
+    return (out, idx) if return_idx or out_idx is not None else out
+
+
 def nn_dist_n(x, y, x_lengths, y_lengths, return_idx=False):
     """nn_dist over a ragged batch (pccx_nn_dist_n): x (B,P_max,3), y (B,Q_max,3), cloud b in its first x_lengths[b] / y_lengths[b]
     rows; what lies behind them is never read (pad_clouds' NaN).  d2 (B,P_max) [, idx (B,P_max) int32]: the first x_lengths[b] entries

@@ -123,6 +123,19 @@ def _(x, y):
     return x.new_empty(B, P), x.new_empty(B, P, dtype=torch.int32)
 
 
+@_op("crop_nearest")
+def crop_nearest(points: Tensor, offsets: Tensor, cloud: Tensor, seed: Tensor, n: Tensor, N_cap: int, sizes: list[int]) -> tuple[Tensor, Tensor]:
+    """ops.crop_nearest with device tables: nearest-n crops of a store of clouds -> (out (B,N_cap,3) NaN-padded, idx (B,N_cap) i32,
+    -1 padded); sizes: the host list of the clouds' point counts (codec.pack_clouds)."""
+    return _ops.crop_nearest(points, offsets, cloud, seed, n, N_cap, return_idx=True, sizes=sizes)
+
+
+@crop_nearest.register_fake
+def _(points, offsets, cloud, seed, n, N_cap, sizes):
+    B = cloud.shape[0]
+    return points.new_empty(B, N_cap, 3), points.new_empty(B, N_cap, dtype=torch.int32)
+
+
 # ---- differentiable ops --------------------------------------------------------------------------------------
 @_op("chamfer_distance")
 def chamfer_distance(x: Tensor, y: Tensor) -> tuple[Tensor, Tensor, Tensor]:
@@ -318,4 +331,4 @@ def _(sampled_xyz, prob_blob, d, L):
 
 
 OPS = ("sa_forward", "pn_forward", "ae_decode", "prob_cdf", "normalize", "denormalize", "fps", "index_points", "knn_points", "ball_query", "nn_dist", "chamfer_distance",
-       "chamfer_grad", "ste_round", "octree_encode", "octree_decode", "range_encode", "range_decode", "fps_blocks")
+       "chamfer_grad", "ste_round", "octree_encode", "octree_decode", "range_encode", "range_decode", "fps_blocks", "crop_nearest")

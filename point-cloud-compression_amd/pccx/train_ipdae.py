@@ -22,6 +22,7 @@ normalises every cloud by its own box: the trainer then selects, bit for bit, th
 any S = N * ALPHA / K up to 1024 (clouds above 32768 points through the grid's wide-K walk, as the codec), and IpdaeTrainer.validate runs the current weights through that codec.
 Clouds of different sizes in one step (train.py --ragged; "full" mode only): select_patches_ragged, forward_loss_ragged,
 IpdaeTrainer.step_ragged / graphed_ragged / validate_ragged, the trainer's side of Codec.compress_ragged.
+Files of any size (train.py --crop): CropSampler cuts every step's batch as nearest-n crops of a store of clouds.
 """
 import torch
 
@@ -528,3 +529,81 @@ class RaggedGraphedIpdaeStep:
         self._advance()
         keys = ("loss", "fbpp", "bpp")
         return {k: float(v) for k, v in zip(keys, self.out)} if sync else dict(zip(keys, self.out))
+
+
+def crop_locate(sizes, draws):
+    """(cloud, index inside it) of global point indices into a store whose clouds hold ``sizes`` points, in store order (host only):
+    a draw uniform over all points of the store lands in a cloud in proportion to its size."""
+    import bisect
+    ends, total = [], 0
+    for s in sizes:
+        total += int(s)
+        ends.append(total)
+    out = []
+    for g in (int(v) for v in draws):
+        if not 0 <= g < total:
+            raise _lib.PccxError(f"crop_locate: point {g} is outside a store of {total} points")
+        c = bisect.bisect_right(ends, g)
+        out.append((c, g - (ends[c] - int(sizes[c]))))
+    return [c for c, _ in out], [i for _, i in out]
+
+
+class CropSampler:
+    """Training crops of a store of clouds of any size (codec.pack_clouds): every draw cuts B compact crops, each the n points nearest
+    to a seed point (ops.crop_nearest: exact, ties to the lower index, the file's own order), on the current stream into ONE buffer
+    this sampler owns, (B, N_cap, 3) with NaN behind each crop -- the batch IpdaeTrainer.step (n = N_cap) and step_ragged /
+    RaggedGraphedIpdaeStep take as it is.  The seed points are drawn on the host from ``generator`` (a CPU torch.Generator), uniformly
+    over ALL points of the store, so a room contributes in proportion to its size; two samplers seeded alike draw the same crops."""
+
+    def __init__(self, points, offsets, sizes, B, N_cap, generator):
+        self.sizes = [int(v) for v in sizes]
+        self.B, self.N_cap = int(B), int(N_cap)
+        if not isinstance(generator, torch.Generator) or generator.device.type != "cpu":
+            raise _lib.PccxError("CropSampler: generator must be a CPU torch.Generator (the seed points are drawn on the host)")
+        if not 1 <= self.B <= ops.CROP_MAX_B:
+            raise _lib.PccxError(f"CropSampler: B={self.B}; one draw cuts 1..CROP_MAX_B = {ops.CROP_MAX_B} crops")
+        if not 1 <= self.N_cap <= ops.CROP_MAX_NCAP:
+            raise _lib.PccxError(f"CropSampler: N_cap={self.N_cap}; a crop holds 1..CROP_MAX_NCAP = {ops.CROP_MAX_NCAP} points")
+        if not self.sizes or min(self.sizes) < 1 or max(self.sizes) > ops.CROP_MAX_M:
+            raise _lib.PccxError(f"CropSampler: every cloud must hold 1..CROP_MAX_M = {ops.CROP_MAX_M} points, got "
+                                 f"{min(self.sizes) if self.sizes else 'no cloud'}..{max(self.sizes) if self.sizes else ''}")
+        if (not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32
+                or points.shape[0] != sum(self.sizes)):
+            raise _lib.PccxError(f"CropSampler: points must be ({sum(self.sizes)}, 3) float32 for clouds of these sizes (codec.pack_clouds), got "
+                                 f"{tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__}")
+        if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or tuple(offsets.shape) != (len(self.sizes) + 1,):
+            raise _lib.PccxError(f"CropSampler: offsets must be ({len(self.sizes) + 1},) int64 (codec.pack_clouds)")
+        self.points, self.offsets, self.generator = ops._f32c(points, "CropSampler.points"), offsets, generator
+        self.M_total = int(points.shape[0])
+        dev = points.device
+        self.batch = torch.empty(self.B, self.N_cap, 3, device=dev, dtype=torch.float32)
+        self.idx = torch.empty(self.B, self.N_cap, device=dev, dtype=torch.int32)
+        self.workspace = torch.empty(int(_lib.load().pccx_crop_nearest_workspace_bytes(self.B, max(self.sizes))), device=dev, dtype=torch.uint8)
+
+    def _counts(self, n):
+        n = [int(n)] * self.B if isinstance(n, int) else [int(v) for v in n]
+        if len(n) != self.B:
+            raise _lib.PccxError(f"CropSampler: {len(n)} counts for {self.B} crops: one int, or one per crop, is expected")
+        return n
+
+    def _starts(self, n):
+        # the draw of pn_kit.py:321 inside each crop, as cli/train.py draws it for a ragged batch
+        return torch.cat([torch.randint(0, nb, (1,), dtype=torch.long, generator=self.generator) for nb in n])
+
+    def draw_fixed(self, cloud_ids, seeds, n):
+        """the crops of caller-chosen seed points: cloud_ids / seeds host lists of B ints, n one int or B -> (batch, n list, starts);
+        everything is range-checked on the host before the launch (ops.crop_nearest), nothing is capped"""
+        n = self._counts(n)
+        ops.crop_nearest(self.points, self.offsets, [int(c) for c in cloud_ids], [int(s) for s in seeds], n, self.N_cap,
+                         workspace=self.workspace, sizes=self.sizes, out=self.batch, out_idx=self.idx)
+        return self.batch, n, self._starts(n)
+
+    def draw(self, n):
+        """B crops of n points (one int, or a list of B) around seed points drawn uniformly over all points of the store: ONE
+        torch.randint over M_total, mapped to (cloud, index) by crop_locate; a count above its cloud's size is capped at it.
+        -> (batch (B, N_cap, 3): the sampler's own buffer, overwritten by the next draw; n list; starts: the FPS start index of
+        each crop, (B,) int64 on the host)"""
+        n = self._counts(n)
+        g = torch.randint(0, self.M_total, (self.B,), dtype=torch.long, generator=self.generator)
+        cloud_ids, seeds = crop_locate(self.sizes, g.tolist())
+        return self.draw_fixed(cloud_ids, seeds, [min(v, self.sizes[c]) for v, c in zip(n, cloud_ids)])
