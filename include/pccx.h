@@ -1036,6 +1036,31 @@ PCCX_API int pccx_crop_nearest(const float *points, int64_t M_total, const int64
                                const int32_t *seed, const int32_t *n, int B, int N_cap, int M_max, float *out, int32_t *out_idx,
                                void *workspace, void *stream);
 
+/* ---- ragged evaluation (csrc/eval_metrics.hip) ---------------------------------------------------------------------------
+ * eval.py's metrics over a padded slab of clouds of different sizes.  Every count table is (B) int32 ON THE DEVICE, never read back,
+ * and clamped into [0, capacity] where a kernel reads it; rows behind a count are never loaded (they may hold NaN), outputs behind a
+ * count stay unwritten, and a zero count forms no address into the slab.  B = 0 returns PCCX_OK with nothing launched; a null
+ * pointer or a bad shape returns PCCX_ERR_ARG before any launch.  B <= 65535.
+ * pccx_minmax_n: out (B,2,3) f32 = per-axis min (row 0) and max (row 1) of the first p[b] rows of X (B,P_max,3): amin / amax of the
+ *   unpadded cloud, bit for bit.  A zero count gives (+inf, -inf).
+ * pccx_query_rep_n: rep (B*M) int32 with rep[b*M+i] = b*M+i for i < n[b], else b*M -- handed to pccx_knn_list_n it keeps the padded
+ *   queries of a slab from being searched (their output rows stay unwritten).  B*M < 2^31.
+ * pccx_estimate_normals_n: pccx_estimate_normals on the rows < n[b] of xyz (B,N_max,3) with nbr (B,N_max,K) int64, whose rows behind
+ *   n[b] are never read: cloud b's normals are the dense entry's on the unpadded cloud, bit for bit.
+ * pccx_point_errors_n: D1 and D2 from one all-pairs scan.  d2 (B,P_max): pccx_nn_dist_n's values.  normals_Y (B,Q_max,3) and plane
+ *   (B,P_max) come together or are both NULL: plane[b,i] = pccx_point_plane_err's value for the nearest row of Y (first minimum, lowest
+ *   index among equal distances), taken from the scan's registers -- no argmin table is written.
+ * pccx_mean_var_n: out (B,2) f64 = mean and population variance of the first p[b] entries of v (B,P_max) f32; two passes in double,
+ *   one workgroup per cloud, a summation order fixed by p[b] alone (no atomics): a cloud's two numbers do not depend on the batch, its
+ *   position in it or P_max.  A zero count gives NaN. */
+PCCX_API int pccx_minmax_n(const float *X, int B, int P_max, const int32_t *p, float *out, void *stream);
+PCCX_API int pccx_query_rep_n(const int32_t *n, int B, int M, int32_t *rep, void *stream);
+PCCX_API int pccx_estimate_normals_n(const float *xyz, int B, int N_max, const int32_t *n, const int64_t *nbr, int K, float *normals,
+                                     void *stream);
+PCCX_API int pccx_point_errors_n(const float *X, int B, int P_max, const int32_t *p, const float *Y, const float *normals_Y, int Q_max,
+                                 const int32_t *q, float *d2, float *plane, void *stream);
+PCCX_API int pccx_mean_var_n(const float *v, int B, int P_max, const int32_t *p, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

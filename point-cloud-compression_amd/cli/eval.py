@@ -23,6 +23,10 @@ parser.add_argument('--device', default='cuda')
 parser.add_argument('--search', choices=['brute', 'grid'], default='brute',
                     help='nearest-neighbour search of the metrics: all-pairs kernels (files of at most 32768 points), or the exact grid index '
                          '(same values, files of any size)')
+parser.add_argument('--ragged', action='store_true',
+                    help='score the files in chunks: every chunk in one launch sequence and one read-back (codec.evaluate_ragged), whatever the '
+                         'point counts; a file outside its limits (an original below 30 or any cloud above 32768 points) is scored the usual way')
+parser.add_argument('--ragged-batch', type=int, default=64, help='files per chunk of --ragged')
 
 
 KNN_POINTS_MAX = 32768          # reference points pccx_knn takes (csrc/knn.hip)
@@ -61,24 +65,47 @@ def calc_uc(input_pc, decomp_pc, search='brute'):
 
 def main():
     args = parser.parse_args()
+    if args.ragged and args.search == 'grid':
+        parser.error("--ragged excludes --search grid: the ragged evaluation runs the all-pairs kernels")
+    if args.ragged_batch < 1:
+        parser.error("--ragged-batch needs at least one file per chunk")
     print(f"Processing on device (gpu/cpu): {args.device}")
     files = sorted(glob(args.input_glob, recursive=True))
     rank, world = _common.setup_ranks(args)
-    rows = []
+    pairs = []
     for f in [files[i] for i in dist.shard_indices(len(files), rank, world)]:                 # file i -> rank i mod world
         name = os.path.split(f)[1]
         cand = [os.path.join(args.decompressed_path, name + '.bin.ply'), os.path.join(args.decompressed_path, name)]
         decomp_f = next((c for c in cand if os.path.exists(c)), None)                # eval.py:172 vs decompress.py:121
-        if decomp_f is None:
-            continue
-        a = torch.from_numpy(plyio.read_point_cloud(f))[None].to(args.device)
-        b = torch.from_numpy(plyio.read_point_cloud(decomp_f))[None].to(args.device)
-        bits = sum(os.stat(os.path.join(args.compressed_path, name + e)).st_size * 8 for e in ('.s.bin', '.p.bin', '.c.bin'))
-        rows.append(dict(filename=name, p2pointPSNR=round(float(codec.d1_psnr(a, b, search=args.search)[0]), 3),
-                         p2planePSNR=round(float(codec.d2_psnr(a, b, search=args.search)[0]), 3),
-                         chamfer_distance=float(codec.normalized_chamfer(a, b, search=args.search)[0]), n_points_input=a.shape[1],
-                         n_points_output=b.shape[1], bpp=bits / a.shape[1],                 # eval.py:189
-                         **{'uniformity coefficient': round(calc_uc(a, b, args.search), 3)}))
+        if decomp_f is not None:
+            pairs.append((name, f, decomp_f))
+    rows = []
+    step = args.ragged_batch if args.ragged else 1
+    for c0 in range(0, len(pairs), step):
+        chunk = pairs[c0:c0 + step]
+        clouds = [(torch.from_numpy(plyio.read_point_cloud(f)), torch.from_numpy(plyio.read_point_cloud(g))) for _, f, g in chunk]
+        # --ragged: every pair eval_ragged_refusal lets through is scored in ONE evaluate_ragged call and read back once; the others,
+        # and every pair without the flag, go file by file
+        inside = [i for i, (a, b) in enumerate(clouds)
+                  if args.ragged and codec.eval_ragged_refusal([a.shape[0]], [b.shape[0]]) is None]
+        scores = {}
+        if inside:
+            pa, na = codec.pad_clouds([clouds[i][0] for i in inside], device=args.device)
+            pb, nb = codec.pad_clouds([clouds[i][1] for i in inside], device=args.device)
+            res = codec.evaluate_ragged(pa, na, pb, nb)
+            table = torch.stack([res[k] for k in ('d1_psnr', 'd2_psnr', 'chamfer', 'uc')]).cpu().tolist()
+            scores = {i: [col[j] for col in table] for j, i in enumerate(inside)}
+        for i, ((name, _, _), (a, b)) in enumerate(zip(chunk, clouds)):
+            if i in scores:
+                d1, d2, cd, uc = scores[i]
+            else:
+                a, b = a[None].to(args.device), b[None].to(args.device)
+                d1, d2 = float(codec.d1_psnr(a, b, search=args.search)[0]), float(codec.d2_psnr(a, b, search=args.search)[0])
+                cd, uc = float(codec.normalized_chamfer(a, b, search=args.search)[0]), calc_uc(a, b, args.search)
+            bits = sum(os.stat(os.path.join(args.compressed_path, name + e)).st_size * 8 for e in ('.s.bin', '.p.bin', '.c.bin'))
+            rows.append(dict(filename=name, p2pointPSNR=round(d1, 3), p2planePSNR=round(d2, 3), chamfer_distance=cd,
+                             n_points_input=a.shape[-2], n_points_output=b.shape[-2], bpp=bits / a.shape[-2],     # eval.py:189
+                             **{'uniformity coefficient': round(uc, 3)}))
     if world > 1:                                            # per-file rows travel to rank 0 (a few hundred bytes per file)
         import torch.distributed as tdist
         gathered = [None] * world

@@ -742,3 +742,100 @@ def normalized_chamfer(orig, recon, search=None):
     a = ((orig - lo) / (hi - lo)).contiguous()
     b = ((recon - lo) / (hi - lo)).contiguous()
     return ops.nn_dist(b, a, search=search).double().mean(dim=1) + ops.nn_dist(a, b, search=search).double().mean(dim=1)
+
+
+EVAL_RAGGED_WAY_OUT = " Such pairs go through d1_psnr / d2_psnr / normalized_chamfer, one pair per call."
+
+
+def eval_ragged_refusal(n_orig, n_recon, knn=30):
+    """Why these pairs cannot be scored by evaluate_ragged -- a message naming the limit and the way out, or None.  Host only.  Every
+    original needs knn <= n <= KNN_BRUTE_MAX_N points (each point's knn nearest, the all-pairs kernels' limit); every reconstruction
+    2 <= m <= KNN_BRUTE_MAX_N (the uniformity coefficient takes a 2-NN distance)."""
+    way_out = EVAL_RAGGED_WAY_OUT
+    n, m = [int(v) for v in n_orig], [int(v) for v in n_recon]
+    if len(n) != len(m):
+        return f"{len(n)} originals against {len(m)} reconstructions; a ragged evaluation scores pairs." + way_out
+    for b, (v, w) in enumerate(zip(n, m)):
+        if not knn <= v <= KNN_BRUTE_MAX_N:
+            return (f"pair {b}: the original holds {v} points; a ragged evaluation needs knn = {knn} <= n_b <= KNN_BRUTE_MAX_N = "
+                    f"{KNN_BRUTE_MAX_N}." + way_out)
+        if not 2 <= w <= KNN_BRUTE_MAX_N:
+            return (f"pair {b}: the reconstruction holds {w} points; a ragged evaluation needs 2 <= m_b <= KNN_BRUTE_MAX_N = "
+                    f"{KNN_BRUTE_MAX_N}." + way_out)
+    return None
+
+
+def _mask_rows(pc, n):
+    """pc (B,N_max,3) with every row behind n[b] (device int32) set to NaN, whatever it held: an elementwise select, no read-back."""
+    rows = torch.arange(pc.shape[1], device=pc.device, dtype=torch.int32)
+    return torch.where((rows[None, :] < n[:, None])[..., None], pc, torch.full((), float("nan"), device=pc.device, dtype=pc.dtype))
+
+
+def _nn_distance_var(pc, n, region):
+    """calc_uc's inner value for every cloud of a slab: population variance of the distance to the nearest other point inside the
+    min(region, n_b) points nearest to point 0 -> (B,) f64.  The region is ops.crop_nearest's: its key (bits of pccx_sqdist to the
+    seed, index) picks the SET pccx_knn picks; it comes in ascending index, not nearest first, which a variance does not see.  The
+    slab is the store (every cloud N_max rows long), so the rows behind n[b] must be NaN -- the largest keys -- and _mask_rows makes
+    them so, whatever the caller left there."""
+    B, N, _ = pc.shape
+    dev = pc.device
+    R = min(int(region), N)
+    r = torch.clamp(n, max=R)
+    masked = _mask_rows(pc, n)
+    out = []
+    for b0 in range(0, B, ops.CROP_MAX_B):                                           # pccx_crop_nearest cuts 1024 crops per call
+        b1 = min(b0 + ops.CROP_MAX_B, B)
+        nb = b1 - b0
+        offsets = torch.arange(nb + 1, device=dev, dtype=torch.int64) * N
+        crop = ops.crop_nearest(masked[b0:b1].reshape(-1, 3), offsets, torch.arange(nb, device=dev, dtype=torch.int32),
+                                torch.zeros(nb, device=dev, dtype=torch.int32), r[b0:b1], R, sizes=[N] * nb)
+        reg = crop - pc[b0:b1, :1]                                                   # centred on point 0 in fp32, as knn_points' patch form
+        d2 = ops.knn_points_n(reg, reg, r[b0:b1], 2, torch.zeros(nb, device=dev, dtype=torch.float32),
+                              rep=ops.query_rep_n(r[b0:b1], nb, R, dev), return_dists=True, return_nn=False).dists[..., 1]
+        out.append(ops.mean_var_n(torch.sqrt(d2), r[b0:b1])[:, 1])
+    return out[0] if len(out) == 1 else torch.cat(out)
+
+
+def evaluate_ragged(orig, n_orig, recon, n_recon, knn=30, region=1024):
+    """eval.py's four metrics for B pairs of clouds of different sizes in one launch sequence: orig (B,N_max,3) and recon (B,M_max,3)
+    are padded slabs as pad_clouds makes them, pair b in the first n_orig[b] / n_recon[b] rows.  -> dict of (B,) f64 device tensors
+    d1_psnr, d2_psnr, chamfer, uc, pair b's values those of d1_psnr / d2_psnr / normalized_chamfer / eval.py's calc_uc on the unpadded
+    pair: every per-point intermediate is bit-identical (bounding box, normals, the squared distances and plane errors, the normalised
+    clouds and their two scans, the 2-NN distances of the regions), only the order of the fp64 sums differs (ops.mean_var_n's fixed
+    order), so a result is inf or NaN exactly where the per-file one is (mse == 0).  A pair's four values do not depend on the batch,
+    its position in it or the slabs' sizes.
+
+    The call only enqueues work on the current stream -- no read-back, no float(): the caller reads the four vectors once.  Counts
+    follow ops.checked_counts: host sequences are checked (eval_ragged_refusal) before any launch, device int32 tensors are taken as
+    they are.  Padding: no row behind a count reaches a result and it need not be pad_clouds' NaN -- the one step that would need it,
+    the region cut of uc (ops.crop_nearest over the slab as its store), works on a copy whose padding is overwritten with NaN here."""
+    from ._lib import PccxError
+    (B, N), (Br, M) = ops._slab_shape(orig, "evaluate_ragged.orig"), ops._slab_shape(recon, "evaluate_ragged.recon")
+    if Br != B:
+        raise PccxError(f"evaluate_ragged: {B} originals against {Br} reconstructions")
+    host = [None if isinstance(v, torch.Tensor) and v.is_cuda else [int(c) for c in (v.tolist() if isinstance(v, torch.Tensor) else v)]
+            for v in (n_orig, n_recon)]
+    if host[0] is not None and host[1] is not None:
+        why = eval_ragged_refusal(host[0], host[1], knn)
+        if why:
+            raise ValueError("evaluate_ragged: " + why)
+    if max(N, M) > KNN_BRUTE_MAX_N or N < knn or M < 2:
+        raise PccxError(f"evaluate_ragged: slabs of {N} and {M} rows; a ragged evaluation needs knn = {knn} <= N_max and 2 <= M_max, both "
+                        f"at most KNN_BRUTE_MAX_N = {KNN_BRUTE_MAX_N}")
+    n = ops.checked_counts(n_orig if host[0] is None else host[0], B, N, orig.device, "evaluate_ragged.n_orig")
+    m = ops.checked_counts(n_recon if host[1] is None else host[1], B, M, orig.device, "evaluate_ragged.n_recon")
+    orig, recon = ops._f32c(orig, "evaluate_ragged.orig"), ops._f32c(recon, "evaluate_ragged.recon")
+    box = ops.minmax_n(orig, n)                                                      # (B,2,3)
+    rng = box[:, 1].double() - box[:, 0].double()
+    diag2 = rng[:, 0] * rng[:, 0] + rng[:, 1] * rng[:, 1] + rng[:, 2] * rng[:, 2]
+    with ops.stage("eval_normals"):
+        normals = ops.estimate_normals_n(orig, n, knn)
+    with ops.stage("eval_scans"):
+        d2, plane = ops.point_errors_n(recon, orig, m, n, normals)                   # D1 and D2 from one scan
+        lo, hi = box[:, 0].amin(dim=1)[:, None, None], box[:, 1].amax(dim=1)[:, None, None]
+        a, b = ((orig - lo) / (hi - lo)).contiguous(), ((recon - lo) / (hi - lo)).contiguous()
+        cd = ops.mean_var_n(ops.nn_dist_n(b, a, m, n), m)[:, 0] + ops.mean_var_n(ops.nn_dist_n(a, b, n, m), n)[:, 0]
+    with ops.stage("eval_regions"):
+        uc = _nn_distance_var(recon, m, region) / _nn_distance_var(orig, n, region)
+    return dict(d1_psnr=10 * torch.log10(diag2 / ops.mean_var_n(d2, m)[:, 0]), d2_psnr=10 * torch.log10(diag2 / ops.mean_var_n(plane, m)[:, 0]),
+                chamfer=cd, uc=uc)

@@ -734,6 +734,91 @@ def point_plane_err(x, y, normals_y, search=None, index=None):
     return err
 
 
+def _slab_shape(t, name, last=3):
+    """(B, rows) of a padded slab (B,rows,3) -- or (B,rows) with last=None -- read before anything else, so that a wrapper can check its
+    host counts first and touch the device after."""
+    want = 3 if last else 2
+    if not isinstance(t, torch.Tensor) or t.dim() != want or (last and t.shape[2] != last) or t.shape[1] < 1:
+        raise _lib.PccxError(f"{name}: a padded slab (B, rows{', 3' if last else ''}) with at least one row is expected, got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def minmax_n(x, n):
+    """Per-axis bounding box of a ragged batch (pccx_minmax_n): x (B,P_max,3), cloud b in its first n[b] rows -> (B,2,3) f32, row 0 the
+    minima and row 1 the maxima: amin / amax of the unpadded cloud, bit for bit.  n as checked_counts takes it."""
+    B, P = _slab_shape(x, "minmax_n")
+    n = checked_counts(n, B, P, x.device, "minmax_n.n")
+    x = _f32c(x, "minmax_n")
+    out = torch.empty(B, 2, 3, device=x.device, dtype=torch.float32)
+    _lib.call("pccx_minmax_n", x.data_ptr(), B, P, n.data_ptr(), out.data_ptr(), _stream())
+    return out
+
+
+def query_rep_n(n, B, M, device):
+    """The rep table that makes knn_points_n skip the padded queries of a slab (pccx_query_rep_n): (B*M,) int32, rep[b*M+i] = b*M+i for
+    i < n[b], else b*M.  n: (B,) int32 on the device."""
+    n = counts(n, B, device, "query_rep_n.n")
+    rep = torch.empty(B * M, device=device, dtype=torch.int32)
+    _lib.call("pccx_query_rep_n", n.data_ptr(), B, M, rep.data_ptr(), _stream())
+    return rep
+
+
+def estimate_normals_n(xyz, n, knn=30):
+    """estimate_normals over a ragged batch: xyz (B,N_max,3), cloud b in its first n[b] >= knn rows -> normals (B,N_max,3) whose first
+    n[b] rows are estimate_normals' on the unpadded cloud, bit for bit; the rows behind them are left unwritten.  The 30-NN comes from
+    knn_points_n with the padded queries skipped (query_rep_n), the PCA from pccx_estimate_normals_n.  A host n is checked against
+    [knn, N_max] before any launch; a device tensor is taken as it is."""
+    B, N = _slab_shape(xyz, "estimate_normals_n")
+    knn = int(knn)
+    if not 1 <= knn <= N:
+        raise _lib.PccxError(f"estimate_normals_n: knn={knn} neighbours in a slab of {N} rows")
+    if not isinstance(n, torch.Tensor) or not n.is_cuda:
+        host = [int(c) for c in (n.tolist() if isinstance(n, torch.Tensor) else n)]
+        bad = [(b, c) for b, c in enumerate(host) if c < knn]
+        if bad:
+            raise _lib.PccxError(f"estimate_normals_n.n: every cloud needs at least knn = {knn} points, got " +
+                                 ", ".join(f"{c} for cloud {b}" for b, c in bad[:4]))
+        n = host
+    n = checked_counts(n, B, N, xyz.device, "estimate_normals_n.n")
+    xyz = _f32c(xyz, "estimate_normals_n")
+    idx = knn_points_n(xyz, xyz, n, knn, torch.zeros(B, device=xyz.device, dtype=torch.float32), rep=query_rep_n(n, B, N, xyz.device),
+                       return_idx=True, return_nn=False).idx
+    out = torch.empty(B, N, 3, device=xyz.device, dtype=torch.float32)
+    _lib.call("pccx_estimate_normals_n", xyz.data_ptr(), B, N, n.data_ptr(), idx.data_ptr(), knn, out.data_ptr(), _stream())
+    return out
+
+
+def point_errors_n(x, y, x_lengths, y_lengths, normals_y=None):
+    """D1 and D2 errors of a ragged batch from ONE all-pairs scan (pccx_point_errors_n): x (B,P_max,3), y (B,Q_max,3), normals_y
+    (B,Q_max,3) or None -> d2 (B,P_max) = nn_dist_n's values [, plane (B,P_max) = point_plane_err's values for the same nearest
+    neighbour].  The first x_lengths[b] entries of cloud b are those of nn_dist / point_plane_err on the unpadded pair, bit for bit; the
+    entries behind them are left unwritten.  Without normals_y only d2 is returned."""
+    (B, P), (By, Q) = _slab_shape(x, "point_errors_n.x"), _slab_shape(y, "point_errors_n.y")
+    if By != B or (normals_y is not None and (not isinstance(normals_y, torch.Tensor) or tuple(normals_y.shape) != tuple(y.shape))):
+        raise _lib.PccxError(f"point_errors_n: y (and normals_y, one normal per row of y) must hold {B} clouds, got {tuple(y.shape)}" +
+                             (f" and {tuple(normals_y.shape)}" if isinstance(normals_y, torch.Tensor) else ""))
+    p, q = checked_counts(x_lengths, B, P, x.device, "point_errors_n.x_lengths"), checked_counts(y_lengths, B, Q, x.device, "point_errors_n.y_lengths")
+    x, y = _f32c(x, "point_errors_n.x"), _f32c(y, "point_errors_n.y")
+    normals_y = _f32c(normals_y, "point_errors_n.normals_y") if normals_y is not None else None
+    d2 = torch.empty(B, P, device=x.device, dtype=torch.float32)
+    plane = torch.empty(B, P, device=x.device, dtype=torch.float32) if normals_y is not None else None
+    _lib.call("pccx_point_errors_n", x.data_ptr(), B, P, p.data_ptr(), y.data_ptr(), normals_y.data_ptr() if normals_y is not None else None,
+              Q, q.data_ptr(), d2.data_ptr(), plane.data_ptr() if plane is not None else None, _stream())
+    return (d2, plane) if plane is not None else d2
+
+
+def mean_var_n(v, n):
+    """Mean and population variance of the first n[b] entries of every row of v (B,P_max) f32 (pccx_mean_var_n) -> (B,2) f64.  Two
+    passes in double in an order fixed by n[b] alone: a cloud's two numbers do not depend on the batch around it."""
+    B, P = _slab_shape(v, "mean_var_n", last=None)
+    n = checked_counts(n, B, P, v.device, "mean_var_n.n")
+    v = _f32c(v, "mean_var_n")
+    out = torch.empty(B, 2, device=v.device, dtype=torch.float64)
+    _lib.call("pccx_mean_var_n", v.data_ptr(), B, P, n.data_ptr(), out.data_ptr(), _stream())
+    return out
+
+
 zeros_hook = None       # pccx.train installs its arena's allocator here: (shape, dtype, device) -> (zero tensor, from-arena?)
 deterministic_hook = None    # pccx.train: () -> True while a deterministic step runs (train.step_scope(deterministic=True))
 
