@@ -1061,6 +1061,43 @@ PCCX_API int pccx_point_errors_n(const float *X, int B, int P_max, const int32_t
                                  const int32_t *q, float *d2, float *plane, void *stream);
 PCCX_API int pccx_mean_var_n(const float *v, int B, int P_max, const int32_t *p, double *out, void *stream);
 
+/* ---- PLY files in and out (csrc/ply_host.h, csrc/hostio.hip, csrc/plyio.hip) ----------------------------------
+ * Stands in for pn_kit.read_point_cloud / save_point_cloud (pn_kit.py:25-42) over a batch of files: headers and raw vertex blocks on
+ * host threads, conversion to float32 on the GPU, the same arrays and the same files bit for bit.
+ * Paths and names are packed as the stream functions take names: zero-terminated strings in one block, path_off[b] = where b's begins.
+ * table (B, PCCX_PLY_ROW) int64 on the HOST, one row per file: 0 status (0 = good, else csrc/ply_host.h PlyStatus), 1 format (0 ascii,
+ *   1 binary_little_endian, 2 binary_big_endian), 2 n_vertex, 3 record stride in bytes, 4 byte offset of the vertex data, 5 file size,
+ *   6..8 byte offset of x y z inside a record, 9..11 their type codes (0 int8, 1 uint8, 2 int16, 3 uint16, 4 int32, 5 uint32, 6 float32,
+ *   7 float64), 12 scalar properties per vertex, 13..15 property index of x y z.  msgs (B, msg_stride) chars: the cause, for every row
+ *   whose status is not 0.  A file that fails does not stop the others, and both calls return PCCX_OK then: the caller reads the statuses.
+ * pccx_ply_scan_host: opens every file, parses its header (limits: 1 <= n_vertex <= 2^31 - 1, stride <= 4096, the vertex block must
+ *   fit the file, no element in front of vertex, no list property on it, no property name twice in a binary file) and fills its row.
+ *   A header longer than the 4 KiB read first is read again, four times as far, up to 16 MiB.
+ * pccx_ply_load_host: for every row with status 0, the vertex block -- n_vertex * stride bytes, nothing else, unconverted -- to
+ *   staging_host + dst_off[b] (dst_off[b] a multiple of 16; staging_host 16-byte aligned).  An ASCII file is parsed by its thread (every
+ *   token to double, then rounded to float, as np.loadtxt + astype do; no locale; inf and nan accepted) into n_vertex records of 12 bytes,
+ *   float32 x y z, and its row is rewritten to say so (format 1, stride 12, offsets 0 4 8, type 6); fewer than n_vertex complete rows
+ *   are refused.  Nothing outside [dst_off[b], dst_off[b] + n_vertex * (12 or stride)) is written.
+ * pccx_ply_write_host: <dir>/<name><suffix> for B clouds, cloud b = rows first_row[b] .. + count[b] of rows_host (rows, 3) f32 on the
+ *   HOST: plyio.save_point_cloud's bytes (its four header lines, little-endian float32), an existing file opened first as the stream
+ *   files are.
+ * threads: 0 = min(8, hardware threads), as above.
+ * pccx_ply_unpack (GPU): staging = the device copy of the staging buffer (16-byte aligned, staging_bytes a multiple of 16); table
+ *   (B, 12) int64 ON THE DEVICE: source byte offset, stride, byte offset of x y z, type code of x y z, big endian (0 / 1), n, dst_row,
+ *   cap; tile_prefix (B + 1) int32 on the device = exclusive prefix of ceil(cap[b] / 256), total_tiles = its last entry.  Writes rows
+ *   dst_row[b] .. + n[b] of out (rows, 3) f32 with cloud b's x y z converted as numpy's astype(float32) does (float32 copied bit for bit,
+ *   float64 / int32 / uint32 rounded to nearest even) and rows n[b] .. cap[b] with the quiet NaN 0x7FC00000 of codec.pad_clouds.  dst_row
+ *   = b * N_cap, cap = N_cap gives the padded slab; dst_row = offsets[b], cap = n[b] the packed store of codec.pack_clouds.  Every table
+ *   field is clamped where it is read, against staging_bytes and rows too.  One kernel, no memset / memcpy: capturable. */
+#define PCCX_PLY_ROW 16
+PCCX_API int pccx_ply_scan_host(int B, const char *paths, const int64_t *path_off, int64_t *table, char *msgs, int msg_stride, int threads);
+PCCX_API int pccx_ply_load_host(int B, const char *paths, const int64_t *path_off, int64_t *table, void *staging_host,
+                                int64_t staging_bytes, const int64_t *dst_off, char *msgs, int msg_stride, int threads);
+PCCX_API int pccx_ply_write_host(const float *rows_host, int64_t rows, const int64_t *first_row, const int64_t *count, int B,
+                                 const char *dir, const char *names, const int64_t *name_off, const char *suffix, int threads);
+PCCX_API int pccx_ply_unpack(const void *staging, int64_t staging_bytes, const int64_t *table, const int32_t *tile_prefix, int B,
+                             int64_t total_tiles, float *out, int64_t rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

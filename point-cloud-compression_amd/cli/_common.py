@@ -66,6 +66,53 @@ def load_models(args, need_gpu=True):
     return ae.pack(args.device), prob.pack(args.device)
 
 
+def add_ply_io_flag(parser):
+    parser.add_argument('--ply-io', choices=['python', 'threads'], default='python',
+                        help="How .ply files are read and written: 'python' = one file at a time (plyio.read_point_cloud / save_point_cloud); "
+                             "'threads' = a batch at a time on the library's host threads, unpacked to float32 on the GPU "
+                             "(plyio.read_point_clouds / save_point_clouds).  The same arrays and the same files, bit for bit.")
+
+
+def scan_plys(files):
+    """--ply-io threads: the headers of `files` on the host threads (plyio.scan_point_clouds) -> their table; a file that cannot be read
+    ends the tool, naming every such file and its cause -- called before any GPU work."""
+    from pccx import plyio
+    try:
+        return plyio.scan_point_clouds(files)
+    except ValueError as e:
+        raise SystemExit(str(e))
+
+
+class ScannedClouds(list):
+    """--ply-io threads: what a tool knows of the files of a glob before it reads them -- one entry per file with the .shape its array
+    will have, from the headers alone -- and the two calls that read them all at once (plyio.read_point_clouds)."""
+
+    class Entry:
+        def __init__(self, n):
+            self.shape = (int(n), 3)
+
+    def __init__(self, files):
+        from pccx import plyio
+        self.files = list(files)
+        self.table = scan_plys(self.files)
+        super().__init__(self.Entry(n) for n in self.table[:, plyio.N_VERTEX])
+
+    def padded(self, device):
+        """codec.pad_clouds of the files: (pc (F, N_max, 3), n list)"""
+        return self._read(device, "padded")
+
+    def packed(self, device):
+        """codec.pack_clouds of the files: (points (M_total, 3), offsets (F + 1,), sizes list)"""
+        return self._read(device, "packed")
+
+    def _read(self, device, layout):
+        # a whole set in one call, once: the pinned staging buffer of its size is not kept beside the copy in HBM
+        from pccx import plyio
+        out = plyio.read_point_clouds(self.files, device, layout, table=self.table)
+        plyio.release_pinned()
+        return out
+
+
 def add_codec_flags(parser):
     parser.add_argument('--N0', type=int, help='Scale Transformation constant.', default=1024)
     parser.add_argument('--ALPHA', type=int, help='The factor of patch coverage ratio.', default=2)
@@ -100,4 +147,5 @@ def add_codec_flags(parser):
                              "probability tables are the fused kernel's on the centres padded to a multiple of 16, which may differ in the "
                              "last unit from the tables used without the flag: such files must be written AND read with --ragged.")
     parser.add_argument('--batch', type=int, default=256, help='Clouds per launch sequence.')
+    add_ply_io_flag(parser)
     parser.add_argument('--seed', type=int, default=11, help='Seed of the per-file FPS start index.')

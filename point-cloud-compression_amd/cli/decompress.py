@@ -59,6 +59,8 @@ def main():
                      p_split=args.p_split or None, p_index=args.p_index or None,
                      prob_path=args.prob)         # decompress, --build-index, and --region's fallback through decompress()
     times, index_bits, points = [], 0, 0
+    # --ply-io threads: the decoded clouds stay on the device until the chunk's one copy (plyio.save_point_clouds)
+    to_host = (lambda t: t.contiguous()) if args.ply_io == 'threads' else (lambda t: t.cpu().numpy())
     with torch.no_grad():
         for b0 in range(0, len(names), args.batch):
             chunk = names[b0:b0 + args.batch]
@@ -142,7 +144,7 @@ def main():
                         print(f"{n}: no point in the region ({reg.segments.numel()} of {reg.n_segments_total} segments touched), skipped")
                         continue
                     print(f"{n}: {reg.patch_idx.numel()} patches from {reg.segments.numel()} of {reg.n_segments_total} segments")
-                    clouds[j] = pts.cpu().numpy()
+                    clouds[j] = to_host(pts)
             else:
                 usual = np.ones(len(chunk), dtype=bool)
                 if args.ragged:
@@ -157,20 +159,29 @@ def main():
                         sel = torch.from_numpy(np.flatnonzero(~usual)).to(args.device)
                         pcs = cd.decompress_ragged(codec.Compressed(s_b[sel], s_n[sel], p_b[sel], p_n[sel], c[sel], 0), S_of[~usual].tolist())
                         for j, pts in zip(sel.cpu().tolist(), pcs):
-                            clouds[j] = pts.cpu().numpy()
+                            clouds[j] = to_host(pts)
                 for S in sorted(set(S_of[usual].tolist())):                                      # one launch sequence per S
                     sel = torch.from_numpy(np.flatnonzero((S_of == S) & usual)).to(args.device)
                     comp = codec.Compressed(s_b[sel], s_n[sel], p_b[sel], p_n[sel], c[sel], 0)
                     if side is not None:
                         comp.p_index = side[int(S)][0]                                           # rows in the order of `sel`: ascending j
-                    pc = cd.decompress(comp, S=int(S)).cpu().numpy()
+                    pc = to_host(cd.decompress(comp, S=int(S)))
                     for j, cloud in zip(sel.cpu().tolist(), pc):
                         clouds[j] = cloud
+            if args.ply_io == 'threads':
+                # the window ends with the points decoded on the device: their read-back (decompress.py:116, inside the window without
+                # the flag) is the one copy of save_point_clouds below, outside it
+                torch.cuda.synchronize()
             times += [(time.time() - t0) / len(chunk)] * len(chunk)                              # decompress.py:118
-            for n, cloud in zip(chunk, clouds):
-                if cloud is None:                                                                # --region: nothing of this file in the box
-                    continue
-                plyio.save_point_cloud(cloud, os.path.join(args.decompressed_path, n + ('.bin.ply' if args.bin_ply_suffix else '')))
+            suffix = '.bin.ply' if args.bin_ply_suffix else ''
+            kept = [(n, cloud) for n, cloud in zip(chunk, clouds) if cloud is not None]         # --region: None = nothing of this file in the box
+            if args.ply_io == 'threads' and kept:
+                # the clouds are rows of the decoders' slabs: each slab's span travels once, as it lies, into pinned memory (no gathering
+                # copy on the device), and the host threads write the files
+                plyio.save_point_clouds([cloud for _, cloud in kept], None, args.decompressed_path, [n for n, _ in kept], suffix)
+            else:
+                for n, cloud in kept:
+                    plyio.save_point_cloud(cloud, os.path.join(args.decompressed_path, n + suffix))
     # the six-slot vector of dist.SUMMARY_FIELDS; this tool has no PSNR to report, so slot 2 ("psnr_sum") carries the sidecars' bits and
     # slot 1 the points they index.  Summed over ranks here, never passed to dist.reduce_summaries.
     g = dist.gather_summaries([0.0, points, index_bits, 0.0, len(times), float(np.sum(times))], _common.summary_device(args))

@@ -27,6 +27,7 @@ parser.add_argument('--ragged', action='store_true',
                     help='score the files in chunks: every chunk in one launch sequence and one read-back (codec.evaluate_ragged), whatever the '
                          'point counts; a file outside its limits (an original below 30 or any cloud above 32768 points) is scored the usual way')
 parser.add_argument('--ragged-batch', type=int, default=64, help='files per chunk of --ragged')
+_common.add_ply_io_flag(parser)
 
 
 KNN_POINTS_MAX = 32768          # reference points pccx_knn takes (csrc/knn.hip)
@@ -81,9 +82,19 @@ def main():
             pairs.append((name, f, decomp_f))
     rows = []
     step = args.ragged_batch if args.ragged else 1
+    # --ply-io threads: the headers of both sides of every pair first (a file that cannot be read ends the run here, before any GPU work)
+    tables = [_common.scan_plys([p[side] for p in pairs]) for side in (1, 2)] if args.ply_io == 'threads' else None
     for c0 in range(0, len(pairs), step):
         chunk = pairs[c0:c0 + step]
-        clouds = [(torch.from_numpy(plyio.read_point_cloud(f)), torch.from_numpy(plyio.read_point_cloud(g))) for _, f, g in chunk]
+        if tables is not None:
+            # a chunk's originals in one call, its reconstructions in another: each cloud a slice of the packed rows on the device
+            sides = []
+            for side in (1, 2):
+                pts, _, sizes = plyio.read_point_clouds([p[side] for p in chunk], args.device, "packed", table=tables[side - 1][c0:c0 + step])
+                sides.append(pts.split(sizes))
+            clouds = list(zip(*sides))
+        else:
+            clouds = [(torch.from_numpy(plyio.read_point_cloud(f)), torch.from_numpy(plyio.read_point_cloud(g))) for _, f, g in chunk]
         # --ragged: every pair eval_ragged_refusal lets through is scored in ONE evaluate_ragged call and read back once; the others,
         # and every pair without the flag, go file by file
         inside = [i for i, (a, b) in enumerate(clouds)

@@ -56,6 +56,7 @@ parser.add_argument('--crop', action='store_true',
                          "in --crop-min..--crop-max).  --val_glob files are cropped once, around their first point.")
 parser.add_argument('--crop-min', type=int, default=None, help='--crop --ragged: the smallest crop, in points.')
 parser.add_argument('--crop-max', type=int, default=None, help='--crop --ragged: the largest crop, in points (the step is built for it).')
+_common.add_ply_io_flag(parser)
 parser.add_argument('--crop-seed', type=int, default=11, help='--crop: seed of the generator the seed points, crop sizes and FPS starts are drawn from.')
 
 
@@ -109,11 +110,27 @@ def window_report(tr, args, epoch, losses, fbpps, bpps, validate, n_val):
               f"Val D1: {sum(v['d1_psnr'] * v['n'] for v in vs) / n:.3f} dB ({n} clouds)")
 
 
-def read_ragged(pattern, flag, K, ALPHA):
+def read_clouds(files, ply_io):
+    """the clouds of `files`: arrays read one by one, or with --ply-io threads their headers only (_common.ScannedClouds: the shapes now,
+    the points in one call once nothing is left to refuse)"""
+    if ply_io == 'threads':
+        return _common.ScannedClouds(files)
+    return [plyio.read_point_cloud(f).astype(np.float32) for f in files]
+
+
+def pad_all(clouds, device):
+    return clouds.padded(device) if isinstance(clouds, _common.ScannedClouds) else codec.pad_clouds(clouds, device=device)
+
+
+def pack_all(clouds, device):
+    return clouds.packed(device) if isinstance(clouds, _common.ScannedClouds) else codec.pack_clouds(clouds, device=device)
+
+
+def read_ragged(pattern, flag, K, ALPHA, ply_io='python'):
     """the files of a glob, read once, each checked against the shape rule of a ragged batch (codec.ragged_shape_refusal)
     -> (files, clouds, refusals: one line per file outside the rule)"""
     files = sorted(glob(pattern, recursive=True))
-    clouds = [plyio.read_point_cloud(f).astype(np.float32) for f in files]
+    clouds = read_clouds(files, ply_io)
     why = [(f, codec.ragged_shape_refusal([c.shape[0]], K, ALPHA)) for f, c in zip(files, clouds)]
     refused = [f"{flag} {f}: {w}" for f, w in why if w] if files else [f"{flag} {pattern}: no file matches"]
     return files, clouds, refused
@@ -133,17 +150,21 @@ def main_ragged(args):
     except _lib.PccxError as e:
         raise SystemExit(str(e))
     os.makedirs(args.model_save_folder, exist_ok=True)
-    files, clouds, refused = read_ragged(args.train_glob, "--train_glob", K, args.ALPHA)
+    files, clouds, refused = read_ragged(args.train_glob, "--train_glob", K, args.ALPHA, args.ply_io)
     val_files, val_clouds = [], []
     if args.val_glob:
-        val_files, val_clouds, more = read_ragged(args.val_glob, "--val_glob", K, args.ALPHA)
+        val_files, val_clouds, more = read_ragged(args.val_glob, "--val_glob", K, args.ALPHA, args.ply_io)
         refused += more
     if refused:
         raise SystemExit("--ragged: nothing is dropped silently; these files are outside what a ragged batch takes:\n" + "\n".join(refused))
-    data, counts = codec.pad_clouds(clouds, device=args.device)                        # the whole training set lives in HBM
+    data, counts = pad_all(clouds, args.device)                                        # the whole training set lives in HBM
     N_cap, S_cap = int(data.shape[1]), codec.ragged_plan(counts, K, args.ALPHA, args.N0, args.d).S_pad
     print(f"--ragged: --N is ignored; {len(files)} files of {min(counts)}..{max(counts)} points, N_cap={N_cap}, S_cap={S_cap}, K={K}, d={args.d}, L={args.L}")
-    val = [torch.from_numpy(c).to(args.device) for c in val_clouds]
+    if val_files and args.ply_io == 'threads':
+        vp, _, vs = val_clouds.packed(args.device)
+        val = list(vp.split(vs))
+    else:
+        val = [torch.from_numpy(c).to(args.device) for c in val_clouds]
     if val:
         print(f"Loaded {len(val)} validation clouds of {min(len(c) for c in val)}..{max(len(c) for c in val)} points")
     ae = models.AE(K=K, k=args.k, d=args.d, L=args.L).to(args.device)
@@ -186,10 +207,10 @@ def main_ragged(args):
     dump_checkpoints(tr, args.model_save_folder)
 
 
-def read_crop_store(pattern, flag, least, what):
+def read_crop_store(pattern, flag, least, what, ply_io='python'):
     """the files of a glob for --crop, read once -> (files, clouds, refusals: one line per file below `least` points)"""
     files = sorted(glob(pattern, recursive=True))
-    clouds = [plyio.read_point_cloud(f).astype(np.float32) for f in files]
+    clouds = read_clouds(files, ply_io)
     refused = [f"{flag} {f}: {c.shape[0]} points, below {what} = {least}" for f, c in zip(files, clouds) if c.shape[0] < least]
     return files, clouds, refused if files else [f"{flag} {pattern}: no file matches"]
 
@@ -224,12 +245,12 @@ def main_crop(args):
             train_ipdae.check_selection(args.S, K, args.octree_mode)
     except _lib.PccxError as e:
         raise SystemExit(str(e))
-    files, clouds, refused = read_crop_store(args.train_glob, "--train_glob", least, what)
+    files, clouds, refused = read_crop_store(args.train_glob, "--train_glob", least, what, args.ply_io)
     val_files, val_clouds = [], []
     if args.val_glob:
-        val_files, val_clouds, more = read_crop_store(args.val_glob, "--val_glob", least, what)
+        val_files, val_clouds, more = read_crop_store(args.val_glob, "--val_glob", least, what, args.ply_io)
         refused += more
-    big = [f"{f}: {c.shape[0]} points, a crop is cut from at most {ops.CROP_MAX_M} per file" for f, c in zip(files + val_files, clouds + val_clouds)
+    big = [f"{f}: {c.shape[0]} points, a crop is cut from at most {ops.CROP_MAX_M} per file" for f, c in zip(files + val_files, list(clouds) + list(val_clouds))
            if c.shape[0] > ops.CROP_MAX_M]
     if refused or big:
         raise SystemExit("--crop: nothing is dropped silently; these files cannot be cropped:\n" + "\n".join(refused + big))
@@ -246,7 +267,7 @@ def main_crop(args):
     os.makedirs(args.model_save_folder, exist_ok=True)
     gen = torch.Generator()
     gen.manual_seed(args.crop_seed)
-    points, offsets, sizes = codec.pack_clouds(clouds, device=args.device)            # the whole training set lives in HBM
+    points, offsets, sizes = pack_all(clouds, args.device)                            # the whole training set lives in HBM
     sampler = train_ipdae.CropSampler(points, offsets, sizes, args.batch_size, n_hi, gen)
     N_cap, S_cap = n_hi, codec.ragged_plan([n_hi], K, args.ALPHA, args.N0, args.d).S_pad
     per_epoch = -(-sampler.M_total // (args.batch_size * n_mean))
@@ -254,7 +275,7 @@ def main_crop(args):
           f"{n_lo if n_lo == n_hi else f'{n_lo}..{n_hi}'} points, {per_epoch} steps per epoch" + (f", N_cap={N_cap}, S_cap={S_cap}" if ragged else ""))
     val = None
     if val_files:                                                                      # one fixed crop per file, cut once: the same clouds at every window
-        vp, vo, vs = codec.pack_clouds(val_clouds, device=args.device)
+        vp, vo, vs = pack_all(val_clouds, args.device)
         cuts = [ops.crop_nearest(vp, vo, list(range(i, min(i + ops.CROP_MAX_B, len(vs)))), [0] * len(vs[i:i + ops.CROP_MAX_B]),
                                  [min(n_hi, m) for m in vs[i:i + ops.CROP_MAX_B]], n_hi, sizes=vs) for i in range(0, len(vs), ops.CROP_MAX_B)]
         val = torch.cat(cuts)
@@ -343,17 +364,24 @@ def main():
             raise SystemExit(str(e))
     os.makedirs(args.model_save_folder, exist_ok=True)
     files = sorted(glob(args.train_glob, recursive=True))
-    points = np.stack([plyio.read_point_cloud(f) for f in files]).astype(np.float32)   # pn_kit.read_point_clouds (pn_kit.py:36-42)
-    print(f"Loaded {points.shape} points, range: [{points.min()}, {points.max()}]")
-    data = torch.from_numpy(points).to(args.device)                                    # the whole training set lives in HBM
+    if args.ply_io == 'threads':
+        clouds = _common.ScannedClouds(files)
+        if len({c.shape for c in clouds}) != 1:                                        # np.stack's refusal below, from the headers
+            raise SystemExit(f"--train_glob: the files must all hold the same number of points, got {sorted({c.shape[0] for c in clouds})}")
+        data = clouds.padded(args.device)[0]                                           # one size: the padded slab is the stack
+        print(f"Loaded {tuple(data.shape)} points, range: [{np.float32(data.min().item())}, {np.float32(data.max().item())}]")
+    else:
+        points = np.stack([plyio.read_point_cloud(f) for f in files]).astype(np.float32)   # pn_kit.read_point_clouds (pn_kit.py:36-42)
+        print(f"Loaded {points.shape} points, range: [{points.min()}, {points.max()}]")
+        data = torch.from_numpy(points).to(args.device)                                # the whole training set lives in HBM
     val = None
     if args.val_glob:
         val_files = sorted(glob(args.val_glob, recursive=True))
-        val_points = [plyio.read_point_cloud(f) for f in val_files]                    # read once
+        val_points = read_clouds(val_files, args.ply_io)                               # read once
         bad = [f for f, p in zip(val_files, val_points) if p.shape[0] != N]
         if bad or not val_files:
             raise SystemExit(f"--val_glob: {'no file matches' if not val_files else f'files without --N = {N} points: {bad}'}")
-        val = torch.from_numpy(np.stack(val_points).astype(np.float32)).to(args.device)
+        val = val_points.padded(args.device)[0] if args.ply_io == 'threads' else torch.from_numpy(np.stack(val_points).astype(np.float32)).to(args.device)
         val_starts = torch.zeros(len(val_files), dtype=torch.long)                     # the same patches at every window
         print(f"Loaded {tuple(val.shape)} validation points")
     ae = models.AE(K=K, k=args.k, d=args.d, L=args.L).to(args.device)

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.h"
+#include "ply_host.h"
 
 namespace {
 
@@ -105,7 +106,8 @@ int default_threads()
     return hw == 0 ? 4 : (hw > 8 ? 8 : (int)hw);
 }
 
-bool write_all(const char *path, const void *buf, size_t len, std::string &err)
+// head (may be empty) and then buf into one file
+bool write_all(const char *path, const void *buf, size_t len, std::string &err, const void *head = nullptr, size_t head_len = 0)
 {
     // an existing file first: O_CREAT makes the kernel take the DIRECTORY's lock exclusively for the lookup, which serialises the
     // threads of a batch that rewrites one directory (the steady state of a codec loop)
@@ -115,16 +117,19 @@ bool write_all(const char *path, const void *buf, size_t len, std::string &err)
         err = std::string("open ") + path + ": " + strerror(errno);
         return false;
     }
-    const char *p = (const char *)buf;
-    while (len > 0) {
-        ssize_t w = write(fd, p, len);
-        if (w < 0) {
-            if (errno == EINTR) continue;
-            err = std::string("write ") + path + ": " + strerror(errno);
-            close(fd);
-            return false;
+    for (int part = 0; part < 2; ++part) {
+        const char *p = (const char *)(part ? buf : head);
+        size_t left = part ? len : head_len;
+        while (left > 0) {
+            ssize_t w = write(fd, p, left);
+            if (w < 0) {
+                if (errno == EINTR) continue;
+                err = std::string("write ") + path + ": " + strerror(errno);
+                close(fd);
+                return false;
+            }
+            p += w, left -= (size_t)w;
         }
-        p += w, len -= (size_t)w;
     }
     if (close(fd) != 0) {
         err = std::string("close ") + path + ": " + strerror(errno);
@@ -317,6 +322,180 @@ extern "C" int pccx_read_index_host(void *index_host, int B, int idx_stride, int
     });
     if (!first.empty()) {
         pccx_set_error("pccx_read_index_host: %s", first.c_str());
+        return PCCX_ERR_ARG;
+    }
+    return PCCX_OK;
+}
+
+// ---- PLY files on the same threads: scan the headers of a batch into a table, load every vertex block raw into
+// one staging buffer (pccx_ply_unpack, csrc/plyio.hip, converts it on the GPU), write reconstructions.  A row of the table is
+// PCCX_PLY_ROW int64: status, format, n_vertex, stride, data offset, file size, byte offset of x y z, type code of x y z, properties
+// per record, property index of x y z (ply_host.h: PlyStatus, PlyHeader).  A file that fails keeps its status in the row and its cause
+// in msgs (B, msg_stride) chars; the others are still done, so the caller can name every bad file at once.
+namespace {
+
+void ply_row_fail(int64_t *row, char *msg, int msg_stride, int status, const std::string &text)
+{
+    row[0] = status;
+    if (msg && msg_stride > 0) snprintf(msg, (size_t)msg_stride, "%s", text.c_str());
+}
+
+void ply_row_set(int64_t *row, const PlyHeader &h, int64_t file_size)
+{
+    row[0] = PLY_OK, row[1] = h.format, row[2] = h.n_vertex, row[3] = h.stride, row[4] = h.data_offset, row[5] = file_size;
+    for (int c = 0; c < 3; ++c) row[6 + c] = h.off[c], row[9 + c] = h.type[c], row[13 + c] = h.col[c];
+    row[12] = h.n_props;
+}
+
+// exactly len bytes from offset at; false with err set on an error or a short file
+bool pread_all(int fd, void *buf, size_t len, int64_t at, std::string &err)
+{
+    char *p = (char *)buf;
+    while (len > 0) {
+        ssize_t r = pread(fd, p, len, (off_t)at);
+        if (r < 0) {
+            if (errno == EINTR) continue;
+            err = std::string("read: ") + strerror(errno);
+            return false;
+        }
+        if (r == 0) {
+            err = "the file ends inside its vertex block";
+            return false;
+        }
+        p += r, len -= (size_t)r, at += r;
+    }
+    return true;
+}
+
+void ply_scan_one(const char *path, int64_t *row, char *msg, int msg_stride)
+{
+    for (int j = 0; j < PCCX_PLY_ROW; ++j) row[j] = 0;
+    if (msg && msg_stride > 0) msg[0] = 0;
+    int fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return ply_row_fail(row, msg, msg_stride, PLY_IO, std::string("open: ") + strerror(errno));
+    struct stat st;
+    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) {
+        close(fd);
+        return ply_row_fail(row, msg, msg_stride, PLY_IO, "not a regular file");
+    }
+    const int64_t size = (int64_t)st.st_size;
+    row[5] = size;
+    std::vector<uint8_t> buf;
+    PlyHeader h;
+    char text[160];
+    int status = PLY_TRUNCATED;
+    // most headers fit the first 4 KiB; one that does not is read again, four times as far, up to 16 MiB
+    for (int64_t want = 4096; status == PLY_TRUNCATED; want *= 4) {
+        const size_t len = (size_t)(want < size ? want : size);
+        buf.resize(len);
+        std::string err;
+        if (len && !pread_all(fd, buf.data(), len, 0, err)) {
+            close(fd);
+            return ply_row_fail(row, msg, msg_stride, PLY_IO, err);
+        }
+        status = ply_parse_header(buf.data(), len, size, &h, text, sizeof(text));
+        if ((int64_t)len >= size || want >= (16ll << 20)) break;
+    }
+    close(fd);
+    if (status != PLY_OK) return ply_row_fail(row, msg, msg_stride, status, text);
+    ply_row_set(row, h, size);
+}
+
+void ply_load_one(const char *path, int64_t *row, uint8_t *staging, int64_t staging_bytes, int64_t dst, char *msg, int msg_stride)
+{
+    const int64_t format = row[1], n = row[2], stride = row[3], at = row[4], size = row[5];
+    const bool ascii = format == PLY_ASCII;
+    // the row is the caller's memory: nothing in it is trusted further than the scan's own limits
+    if (n < 1 || n > PLY_MAX_VERTICES || stride < 1 || stride > PLY_MAX_STRIDE || at < 0 || size < at || (format != PLY_ASCII && format != PLY_LE && format != PLY_BE))
+        return ply_row_fail(row, msg, msg_stride, PLY_ARG, "a table row that pccx_ply_scan_host did not fill");
+    const int64_t need = n * (ascii ? 12 : stride);
+    if (dst < 0 || dst % 16 != 0 || dst > staging_bytes || need > staging_bytes - dst)
+        return ply_row_fail(row, msg, msg_stride, PLY_ARG, "the staging range of this file is not 16-byte aligned or does not hold its " + std::to_string(need) + " bytes");
+    int fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return ply_row_fail(row, msg, msg_stride, PLY_IO, std::string("open: ") + strerror(errno));
+    std::string err;
+    if (!ascii) {
+        const bool ok = pread_all(fd, staging + dst, (size_t)need, at, err);
+        close(fd);
+        if (!ok) return ply_row_fail(row, msg, msg_stride, PLY_IO, err);
+        return;
+    }
+    PlyHeader h;
+    memset(&h, 0, sizeof(h));
+    h.format = PLY_ASCII, h.n_vertex = n, h.n_props = (int)row[12];
+    for (int c = 0; c < 3; ++c) h.col[c] = (int)row[13 + c];
+    if (row[12] < 3 || row[12] > PLY_MAX_STRIDE || h.col[0] < 0 || h.col[1] < 0 || h.col[2] < 0 || h.col[0] >= h.n_props || h.col[1] >= h.n_props ||
+        h.col[2] >= h.n_props) {
+        close(fd);
+        return ply_row_fail(row, msg, msg_stride, PLY_ARG, "a table row that pccx_ply_scan_host did not fill");
+    }
+    std::vector<uint8_t> text((size_t)(size - at));
+    const bool ok = text.empty() || pread_all(fd, text.data(), text.size(), at, err);
+    close(fd);
+    if (!ok) return ply_row_fail(row, msg, msg_stride, PLY_IO, err);
+    char why[160];
+    const int status = ply_parse_ascii_rows(text.data(), text.size(), h, (float *)(staging + dst), why, sizeof(why));
+    if (status != PLY_OK) return ply_row_fail(row, msg, msg_stride, status, why);
+    // what the staging range now holds: float32 x y z records
+    row[1] = PLY_LE, row[3] = 12;
+    for (int c = 0; c < 3; ++c) row[6 + c] = 4 * c, row[9 + c] = PLY_F4;
+}
+
+}  // namespace
+
+extern "C" int pccx_ply_scan_host(int B, const char *paths, const int64_t *path_off, int64_t *table, char *msgs, int msg_stride, int threads)
+{
+    PCCX_CHECK_ARG(B >= 0 && msg_stride >= 0, "pccx_ply_scan_host: negative size");
+    if (B == 0) return PCCX_OK;
+    PCCX_CHECK_ARG(paths && path_off && table && (msgs || msg_stride == 0), "pccx_ply_scan_host: null pointer");
+    Pool::get().run(B, threads > 0 ? threads : default_threads(), [&](int b) {
+        ply_scan_one(paths + path_off[b], table + (size_t)b * PCCX_PLY_ROW, msgs ? msgs + (size_t)b * msg_stride : nullptr, msg_stride);
+    });
+    return PCCX_OK;
+}
+
+extern "C" int pccx_ply_load_host(int B, const char *paths, const int64_t *path_off, int64_t *table, void *staging_host, int64_t staging_bytes,
+                                  const int64_t *dst_off, char *msgs, int msg_stride, int threads)
+{
+    PCCX_CHECK_ARG(B >= 0 && msg_stride >= 0 && staging_bytes >= 0, "pccx_ply_load_host: negative size");
+    if (B == 0) return PCCX_OK;
+    PCCX_CHECK_ARG(paths && path_off && table && staging_host && dst_off && (msgs || msg_stride == 0), "pccx_ply_load_host: null pointer");
+    PCCX_CHECK_ARG((uintptr_t)staging_host % 16 == 0, "pccx_ply_load_host: the staging buffer must be 16-byte aligned");
+    Pool::get().run(B, threads > 0 ? threads : default_threads(), [&](int b) {
+        int64_t *row = table + (size_t)b * PCCX_PLY_ROW;
+        if (row[0] != PLY_OK) return;                  // refused by the scan: its status and message stay
+        ply_load_one(paths + path_off[b], row, (uint8_t *)staging_host, staging_bytes, dst_off[b], msgs ? msgs + (size_t)b * msg_stride : nullptr, msg_stride);
+    });
+    return PCCX_OK;
+}
+
+extern "C" int pccx_ply_write_host(const float *rows_host, int64_t rows, const int64_t *first_row, const int64_t *count, int B, const char *dir,
+                                   const char *names, const int64_t *name_off, const char *suffix, int threads)
+{
+    PCCX_CHECK_ARG(B >= 0 && rows >= 0, "pccx_ply_write_host: negative size");
+    if (B == 0) return PCCX_OK;
+    PCCX_CHECK_ARG(rows_host && first_row && count && dir && names && name_off && suffix, "pccx_ply_write_host: null pointer");
+    for (int b = 0; b < B; ++b)                        // refused before touching the file system
+        PCCX_CHECK_ARG(first_row[b] >= 0 && count[b] >= 0 && first_row[b] <= rows && count[b] <= rows - first_row[b],
+                       "pccx_ply_write_host: cloud %d takes rows %lld .. +%lld of %lld", b, (long long)first_row[b], (long long)count[b], (long long)rows);
+    const Names nm{dir, names, name_off};
+    std::mutex emu;
+    std::string first;
+    int first_b = B;                                   // the error reported is the lowest cloud's, not the first in time: the same message
+                                                       // whatever the threads' order
+    Pool::get().run(B, threads > 0 ? threads : default_threads(), [&](int b) {
+        // plyio.save_point_cloud's bytes: its four header lines, then little-endian float32 rows
+        char head[160];
+        const int hl = snprintf(head, sizeof(head), "ply\nformat binary_little_endian 1.0\nelement vertex %lld\nproperty float x\nproperty float y\n"
+                                "property float z\nend_header\n", (long long)count[b]);
+        std::string err;
+        if (!write_all(nm.path(b, suffix).c_str(), rows_host + 3 * (size_t)first_row[b], 12 * (size_t)count[b], err, head, (size_t)hl)) {
+            std::lock_guard<std::mutex> g(emu);
+            if (b < first_b) first_b = b, first = err;
+        }
+    });
+    if (first_b < B) {
+        pccx_set_error("pccx_ply_write_host: %s", first.c_str());
         return PCCX_ERR_ARG;
     }
     return PCCX_OK;

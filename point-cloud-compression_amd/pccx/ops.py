@@ -1051,3 +1051,22 @@ def octree_decode(bytes_, nbytes, mode="reference", S_out=64, wide=False):
     _lib.call("pccx_octree_decode", bytes_.data_ptr(), stride, nbytes.data_ptr(), B,
               {"reference": 0, "full": 2 if wide else 1}[mode], int(S_out), out.data_ptr(), count.data_ptr(), _stream())
     return out, count
+
+
+def ply_unpack(staging, table, tile_prefix, out, total_tiles):
+    """pccx_ply_unpack (csrc/plyio.hip): raw PLY vertex records -> float32 x y z rows.  staging: device uint8, its memory 16-byte
+    aligned and a multiple of 16 bytes long; table (B, 12) int64 and tile_prefix (B + 1,) int32 on the device, as
+    plyio.device_tables lays them out, total_tiles the prefix's last entry (the grid); out (rows, 3) f32, written
+    in place and returned.  One kernel on the current stream."""
+    for t, name, dtype in ((staging, "staging", torch.uint8), (table, "table", torch.int64), (tile_prefix, "tile_prefix", torch.int32),
+                           (out, "out", torch.float32)):
+        if _dev(t, "ply_unpack." + name).dtype != dtype or not t.is_contiguous():
+            raise _lib.PccxError(f"ply_unpack.{name}: a contiguous {dtype} tensor is expected")
+    B = int(table.shape[0])
+    if table.dim() != 2 or table.shape[1] != 12 or tuple(tile_prefix.shape) != (B + 1,) or out.dim() != 2 or out.shape[1] != 3:
+        raise _lib.PccxError("ply_unpack: table (B, 12), tile_prefix (B + 1,) and out (rows, 3) are expected")
+    if staging.numel() % 16 or staging.data_ptr() % 16:
+        raise _lib.PccxError("ply_unpack.staging: must start at a multiple of 16 bytes and be a multiple of 16 bytes long")
+    _lib.call("pccx_ply_unpack", staging.data_ptr(), staging.numel(), table.data_ptr(), tile_prefix.data_ptr(), B, int(total_tiles),
+              out.data_ptr(), int(out.shape[0]), _stream())
+    return out
