@@ -1098,6 +1098,36 @@ PCCX_API int pccx_ply_write_host(const float *rows_host, int64_t rows, const int
 PCCX_API int pccx_ply_unpack(const void *staging, int64_t staging_bytes, const int64_t *table, const int32_t *tile_prefix, int B,
                              int64_t total_tiles, float *out, int64_t rows, void *stream);
 
+/* ---- Point clouds sampled from triangle meshes (csrc/off_host.h, csrc/hostio.hip, csrc/mesh_sample.hip) ---------
+ * Stands in for sample_modelnet.py's pyntcloud calls over a batch of OFF files: headers and bodies on host threads, the sampler on the
+ * GPU.  The sampler is defined in DESIGN.md section 4.5 ("meshes") and is exact: integer area weights, Philox4x32-10, float64 points.
+ * table (B, PCCX_OFF_ROW) int64 on the HOST, one row per file: 0 status (0 = good, else csrc/off_host.h OffStatus), 1 nv, 2 nf, 3 byte
+ *   offset of the body, 4 file size, 5 ne, 6..7 zero.  msgs, paths, threads and the return value: as for the PLY pair above.
+ * pccx_off_scan_host: opens every file, parses its header (limits: 3 <= nv <= 2^31 - 1, 1 <= nf <= 2^22, nv + nf shortest lines must
+ *   fit the file) and fills its row.
+ * pccx_off_load_host: for every row with status 0, the body parsed by its thread: nv * 3 float32 to staging_host + v_dst_off[b] and
+ *   nf * 3 int32 indices local to the mesh to staging_host + f_dst_off[b] (both multiples of 4; one after the other per file, or all
+ *   vertices in front of all faces, which is the packed form pccx_mesh_sample takes).  Refused: a polygon, an index outside 0 .. nv - 1,
+ *   a coordinate that is no number or not finite as float32, fewer lines than nv + nf.  Nothing outside the two ranges is written.
+ * pccx_mesh_sample (GPU): verts (V_total, 3) f32 and faces (F_total, 3) int32 packed mesh after mesh; v_off / f_off (B + 1) int64 ON THE
+ *   DEVICE, the exclusive prefixes of nv and nf; seeds (B) int64 on the device, one 64-bit stream per mesh.  Writes out (B, n, 3) f32:
+ *   row i of mesh b is a function of (mesh b, seeds[b], i) alone.  normalize = 1: (p - m) / M per mesh, m the minimum over its 3n
+ *   values, M the maximum of p - m (sample_modelnet.py:47-48); 0: the raw samples.  status (B) int32: 0 good, 1 no area (largest
+ *   triangle area zero or not finite, or a mesh outside the limits: its rows are NaN), 2 M == 0 (rows shifted, not scaled).
+ *   Limits: B <= 1024, 1 <= n <= 2^20, F_b <= 2^22; every offset and index is clamped where it is read.  workspace: at least
+ *   pccx_mesh_sample_workspace_bytes(B, F_total, n) bytes, 8-byte aligned, content immaterial; afterwards it begins with a_t (F_total
+ *   float64), w_t (F_total uint64) and the inclusive prefix I_t (F_total uint64).  Six kernels and an init, integer atomics only, no
+ *   memset / memcpy: capturable. */
+#define PCCX_OFF_ROW 8
+PCCX_API int pccx_off_scan_host(int B, const char *paths, const int64_t *path_off, int64_t *table, char *msgs, int msg_stride, int threads);
+PCCX_API int pccx_off_load_host(int B, const char *paths, const int64_t *path_off, int64_t *table, void *staging_host,
+                                int64_t staging_bytes, const int64_t *v_dst_off, const int64_t *f_dst_off, char *msgs, int msg_stride,
+                                int threads);
+PCCX_API size_t pccx_mesh_sample_workspace_bytes(int B, int64_t F_total, int n);
+PCCX_API int pccx_mesh_sample(const float *verts, int64_t V_total, const int32_t *faces, int64_t F_total, const int64_t *v_off,
+                              const int64_t *f_off, const int64_t *seeds, int B, int n, int normalize, float *out, int32_t *status,
+                              void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

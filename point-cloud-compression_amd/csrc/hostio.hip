@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.h"
+#include "off_host.h"
 #include "ply_host.h"
 
 namespace {
@@ -498,6 +499,100 @@ extern "C" int pccx_ply_write_host(const float *rows_host, int64_t rows, const i
         pccx_set_error("pccx_ply_write_host: %s", first.c_str());
         return PCCX_ERR_ARG;
     }
+    return PCCX_OK;
+}
+
+// ---- OFF meshes on the same threads ("meshes"): scan the headers of a batch into a table, parse every body into
+// one staging buffer.  A row of the table is PCCX_OFF_ROW int64: status (off_host.h OffStatus), nv, nf, byte offset of the body, file
+// size, ne.  As for PLY files, a file that fails keeps its status in the row and its cause in msgs; the others are still done
+// (ply_row_fail and pread_all above serve both formats).
+namespace {
+
+void off_scan_one(const char *path, int64_t *row, char *msg, int msg_stride)
+{
+    for (int j = 0; j < PCCX_OFF_ROW; ++j) row[j] = 0;
+    if (msg && msg_stride > 0) msg[0] = 0;
+    int fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return ply_row_fail(row, msg, msg_stride, OFF_IO, std::string("open: ") + strerror(errno));
+    struct stat st;
+    if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) {
+        close(fd);
+        return ply_row_fail(row, msg, msg_stride, OFF_IO, "not a regular file");
+    }
+    const int64_t size = (int64_t)st.st_size;
+    row[4] = size;
+    std::vector<uint8_t> buf;
+    OffHeader h;
+    char text[160];
+    int status = OFF_TRUNCATED;
+    // the header is the first lines with a token; comments in front of it may push it behind the 4 KiB read first
+    for (int64_t want = 4096; status == OFF_TRUNCATED; want *= 4) {
+        const size_t len = (size_t)(want < size ? want : size);
+        buf.resize(len);
+        std::string err;
+        if (len && !pread_all(fd, buf.data(), len, 0, err)) {
+            close(fd);
+            return ply_row_fail(row, msg, msg_stride, OFF_IO, err);
+        }
+        status = off_parse_header(buf.data(), len, size, &h, text, sizeof(text));
+        if ((int64_t)len >= size || want >= (16ll << 20)) break;
+    }
+    close(fd);
+    if (status != OFF_OK) return ply_row_fail(row, msg, msg_stride, status, text);
+    row[0] = OFF_OK, row[1] = h.nv, row[2] = h.nf, row[3] = h.body_offset, row[5] = h.ne;
+}
+
+void off_load_one(const char *path, int64_t *row, uint8_t *staging, int64_t staging_bytes, int64_t vdst, int64_t fdst, char *msg, int msg_stride)
+{
+    OffHeader h;
+    h.nv = row[1], h.nf = row[2], h.body_offset = row[3], h.ne = row[5];
+    const int64_t size = row[4];
+    // the row is the caller's memory: nothing in it is trusted further than the scan's own limits
+    if (h.nv < 3 || h.nv > OFF_MAX_VERTICES || h.nf < 1 || h.nf > OFF_MAX_FACES || h.body_offset < 0 || size < h.body_offset)
+        return ply_row_fail(row, msg, msg_stride, OFF_ARG, "a table row that pccx_off_scan_host did not fill");
+    const int64_t vb = 12 * h.nv, fb = 12 * h.nf;
+    if (vdst < 0 || vdst % 4 != 0 || vdst > staging_bytes || vb > staging_bytes - vdst || fdst < 0 || fdst % 4 != 0 || fdst > staging_bytes ||
+        fb > staging_bytes - fdst || (vdst < fdst + fb && fdst < vdst + vb))
+        return ply_row_fail(row, msg, msg_stride, OFF_ARG, "the staging ranges of this file are not 4-byte aligned, overlap or do not hold its " +
+                                                               std::to_string(vb) + " + " + std::to_string(fb) + " bytes");
+    int fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return ply_row_fail(row, msg, msg_stride, OFF_IO, std::string("open: ") + strerror(errno));
+    std::string err;
+    std::vector<uint8_t> text((size_t)(size - h.body_offset));
+    const bool ok = text.empty() || pread_all(fd, text.data(), text.size(), h.body_offset, err);
+    close(fd);
+    if (!ok) return ply_row_fail(row, msg, msg_stride, OFF_IO, "the body could not be read as scanned (" + err + ")");
+    char why[160];
+    const int status = off_parse_body(text.data(), text.size(), h, (float *)(staging + vdst), (int32_t *)(staging + fdst), why, sizeof(why));
+    if (status != OFF_OK) return ply_row_fail(row, msg, msg_stride, status, why);
+}
+
+}  // namespace
+
+extern "C" int pccx_off_scan_host(int B, const char *paths, const int64_t *path_off, int64_t *table, char *msgs, int msg_stride, int threads)
+{
+    PCCX_CHECK_ARG(B >= 0 && msg_stride >= 0, "pccx_off_scan_host: negative size");
+    if (B == 0) return PCCX_OK;
+    PCCX_CHECK_ARG(paths && path_off && table && (msgs || msg_stride == 0), "pccx_off_scan_host: null pointer");
+    Pool::get().run(B, threads > 0 ? threads : default_threads(), [&](int b) {
+        off_scan_one(paths + path_off[b], table + (size_t)b * PCCX_OFF_ROW, msgs ? msgs + (size_t)b * msg_stride : nullptr, msg_stride);
+    });
+    return PCCX_OK;
+}
+
+extern "C" int pccx_off_load_host(int B, const char *paths, const int64_t *path_off, int64_t *table, void *staging_host, int64_t staging_bytes,
+                                  const int64_t *v_dst_off, const int64_t *f_dst_off, char *msgs, int msg_stride, int threads)
+{
+    PCCX_CHECK_ARG(B >= 0 && msg_stride >= 0 && staging_bytes >= 0, "pccx_off_load_host: negative size");
+    if (B == 0) return PCCX_OK;
+    PCCX_CHECK_ARG(paths && path_off && table && staging_host && v_dst_off && f_dst_off && (msgs || msg_stride == 0), "pccx_off_load_host: null pointer");
+    PCCX_CHECK_ARG((uintptr_t)staging_host % 4 == 0, "pccx_off_load_host: the staging buffer must be 4-byte aligned");
+    Pool::get().run(B, threads > 0 ? threads : default_threads(), [&](int b) {
+        int64_t *row = table + (size_t)b * PCCX_OFF_ROW;
+        if (row[0] != OFF_OK) return;                  // refused by the scan: its status and message stay
+        off_load_one(paths + path_off[b], row, (uint8_t *)staging_host, staging_bytes, v_dst_off[b], f_dst_off[b], msgs ? msgs + (size_t)b * msg_stride : nullptr,
+                     msg_stride);
+    });
     return PCCX_OK;
 }
 

@@ -1070,3 +1070,45 @@ def ply_unpack(staging, table, tile_prefix, out, total_tiles):
     _lib.call("pccx_ply_unpack", staging.data_ptr(), staging.numel(), table.data_ptr(), tile_prefix.data_ptr(), B, int(total_tiles),
               out.data_ptr(), int(out.shape[0]), _stream())
     return out
+
+
+MESH_MAX_B, MESH_MAX_N, MESH_MAX_F = 1024, 1 << 20, 1 << 22         # csrc/mesh_sample.hip: meshes per call, samples per mesh, faces per mesh
+
+
+def mesh_sample_workspace_bytes(B, F_total, n):
+    return int(_lib.load().pccx_mesh_sample_workspace_bytes(int(B), int(F_total), int(n)))
+
+
+def mesh_sample(verts, faces, v_off, f_off, seeds, n, normalize=True, out=None, workspace=None):
+    """pccx_mesh_sample (csrc/mesh_sample.hip): n points on each of B triangle meshes.  verts (V_total, 3) f32 and faces (F_total, 3)
+    int32 (indices local to their mesh) hold mesh after mesh; v_off / f_off (B + 1,) int64 and seeds (B,) int64 on the device.
+    -> (out (B, n, 3) f32, status (B,) int32: 0 good, 1 no area -- NaN rows --, 2 nothing to scale by).  normalize: the unit-cube
+    normalisation of sample_modelnet.py, else the raw samples.  workspace: a uint8 device tensor of at least
+    mesh_sample_workspace_bytes(B, F_total, n) bytes whose content does not matter (default: allocated here); afterwards it begins with
+    a_t float64, w_t uint64 and the inclusive prefix I_t uint64, F_total each.  Only enqueues kernels on the current stream."""
+    for t, name, dtype, cols in ((verts, "verts", torch.float32, 3), (faces, "faces", torch.int32, 3), (v_off, "v_off", torch.int64, None),
+                                 (f_off, "f_off", torch.int64, None), (seeds, "seeds", torch.int64, None)):
+        if _dev(t, "mesh_sample." + name).dtype != dtype or not t.is_contiguous() or t.dim() != (2 if cols else 1) or (cols and t.shape[1] != cols):
+            raise _lib.PccxError(f"mesh_sample.{name}: a contiguous {dtype} tensor of shape {'(rows, 3)' if cols else '(len,)'} is expected")
+    B, n = int(seeds.shape[0]), int(n)
+    if tuple(v_off.shape) != (B + 1,) or tuple(f_off.shape) != (B + 1,):
+        raise _lib.PccxError(f"mesh_sample: {B} seeds need v_off and f_off of ({B + 1},)")
+    if not 1 <= B <= MESH_MAX_B or not 1 <= n <= MESH_MAX_N:
+        raise _lib.PccxError(f"mesh_sample: B={B}, n={n}; one call takes 1..{MESH_MAX_B} meshes and 1..{MESH_MAX_N} samples of each")
+    V_total, F_total = int(verts.shape[0]), int(faces.shape[0])
+    if V_total < 1 or F_total < 1:
+        raise _lib.PccxError("mesh_sample: empty verts or faces")
+    need = mesh_sample_workspace_bytes(B, F_total, n)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=verts.device)
+    elif _dev(workspace, "mesh_sample.workspace").dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need or workspace.data_ptr() % 8:
+        raise _lib.PccxError(f"mesh_sample.workspace: a contiguous 8-byte-aligned uint8 tensor of at least {need} bytes is expected")
+    if out is None:
+        out = torch.empty(B, n, 3, dtype=torch.float32, device=verts.device)
+    elif _dev(out, "mesh_sample.out").dtype != torch.float32 or tuple(out.shape) != (B, n, 3) or not out.is_contiguous():
+        raise _lib.PccxError(f"mesh_sample.out: a contiguous float32 tensor of ({B}, {n}, 3) is expected")
+    status = torch.empty(B, dtype=torch.int32, device=verts.device)
+    with torch.cuda.device(verts.device):
+        _lib.call("pccx_mesh_sample", verts.data_ptr(), V_total, faces.data_ptr(), F_total, v_off.data_ptr(), f_off.data_ptr(), seeds.data_ptr(), B, n,
+                  1 if normalize else 0, out.data_ptr(), status.data_ptr(), workspace.data_ptr(), _stream())
+    return out, status
